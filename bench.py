@@ -11,11 +11,18 @@ the CA step (gca_alex_step_march at 256^2: packed edge-slope layout, 23.1 B/cell
 with --step-kernel tiled) + the env step (gca_advenv_post) [+ one RCCL all_gather of the
 per-env done mask / reward when --gpus > 1]. Weak scaling: every rank owns E envs.
 
-Also reported: the WindyForestFire bulldozer env (config 2, E = 1024) as `secondary`,
-the roofline of the dominant kernel (HIP events over the timed region) and the CPU
-baseline (the oracle's C restatement, single core, bounded sample).
+A plain run does only what the headline figure needs: set-up, W warm-up steps, K timed
+steps, the result line (`value`, `ms_per_step`, the roofline figures that follow from the
+timed steps' own HIP events). `--dump-outputs DIR` also writes what the last timed step
+left in the env (DIR/<name>.npy, float32; the grids of a fixed seeded sample of envs).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+With `--full`, also reported: 5 repetitions of the K steps (the median is the headline), the
+general-terrain / tiled-kernel / access-pattern / RGB-observation / episode-start loops of the
+same env, configs 4 and 5, the 512^2 step, the WindyForestFire bulldozer env (config 2,
+E = 1024) as `secondary`, the one-env drop-ins, the live device copy rate and the CPU
+baselines (the oracle's C restatement and the scipy restatements, bounded samples).
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 """
 import argparse
 import json
@@ -68,13 +75,26 @@ def parse():
     ap.add_argument("--step-kernel", choices=["auto", "march", "tiled"], default="auto",
                     help="packed layout at W = 256: the marching kernel (auto) or the tiled one")
     ap.add_argument("--headline-only", action="store_true",
-                    help="only the headline loop (no RGB / episode-start loops): every alex_step launch is the "
+                    help="with --full: no RGB / episode-start loops of the headline env: every alex_step launch is the "
                          "dense mid-episode one, so rocprofv3 per-kernel averages match kernel_ms")
-    ap.add_argument("--reps", type=int, default=5, help="timed repetitions of K steps; the median is reported")
+    ap.add_argument("--reps", type=int, default=None,
+                    help="timed repetitions of K steps; the median is reported (default: 1, with --full 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline loop: the CPU baselines, the other loops of the headline env "
+                         "(general terrain, tiled kernel, pattern floor, RGB observation, episode start), configs 2, 4 "
+                         "and 5, the 512^2 step, the drop-ins and the device copy rate")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step of the headline loop left in the env as DIR/<name>.npy "
+                         "(float32; grid and fire age of a fixed seeded sample of envs, the per-env results of all)")
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU rehearsal of the N-rank launch: gloo ranks, env sharding and the episode-stats "
                          "all-gather of gymca_amd.distributed, no GPU touched")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.reps is None:
+        args.reps = 5 if args.full else 1
+    if not args.full:  # a plain run: the headline loop alone
+        args.no_cpu_baseline = args.no_secondary = True
+    return args
 
 
 def _free_port():
@@ -284,6 +304,32 @@ def timed_loop(step_fn, K, W, pg, device, reps=1, detail=None, prepare=None):
     return med, (sum(kern) / len(kern) if kern else None)
 
 
+DUMP_ENVS = 32  # envs whose grid and fire age --dump-outputs writes (float32: 8 MiB per array at 256^2)
+
+
+def headline_outputs(env):
+    """What the headline loop's last step left for its caller, as float32 host arrays: grid and fire age of a fixed
+    seeded sample of DUMP_ENVS envs (`env_index`, the same envs in every run) and, for every env, the cell counts and
+    the env step's results (reward, done, the episode statistics, position, wind index, time step)."""
+    import numpy as np
+
+    idx = np.sort(np.random.default_rng(0).choice(env.num_envs, size=min(env.num_envs, DUMP_ENVS), replace=False))
+    host = lambda t: t.detach().to("cpu").numpy().astype(np.float32)
+    out = {"env_index": idx.astype(np.float32),
+           "grid": host(env.grid[env.cur][idx.tolist()]), "fire_age": host(env.age[env.cur][idx.tolist()])}
+    for name in ("counts", "reward", "done", "steps_elapsed", "reward_accumulated", "pos", "wind_index", "time_step"):
+        out[name] = host(getattr(env, name))
+    return out
+
+
+def write_outputs(dirname, arrays):
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def bench_alex(args, world, rank, device, pg):
     import torch
 
@@ -323,6 +369,7 @@ def bench_alex(args, world, rank, device, pg):
     detail = {}
     prep = lambda: synthetic_state(env, rank, device)  # every repetition times K steps from the C3 state
     dt, kern = timed_loop(step, args.steps, args.warmup, pg, device, reps=args.reps, detail=detail, prepare=prep)
+    outputs = headline_outputs(env) if args.dump_outputs and rank == 0 else None  # before any other loop steps the env
     cells = world * E * N * N * args.steps
     nbytes = alex_bytes(env, args.slope_layout)
     res = {
@@ -342,7 +389,10 @@ def bench_alex(args, world, rank, device, pg):
         "kernel_key": headline_kernel_key(env),
         # N > 1: the last timed gather checked against every rank's payload over the group (None at N = 1)
         "gather_check": gd.verify_gather(stats) if args.gather != "none" else None,
+        "outputs": outputs,
     }
+    if not args.full:
+        return res
     if getattr(env, "march", False) and rank == 0:
         res["tiled_kernel_ms"] = tiled_kernel_ms(env, device)
     res["pattern_floor_ms"] = march_pattern_ms(env, device)
@@ -1301,6 +1351,9 @@ def main():
     import torch
 
     alex = bench_alex(args, world, rank, device, pg)
+    outputs = alex.pop("outputs")
+    if outputs is not None:
+        write_outputs(args.dump_outputs, outputs)
     import gc
 
     gc.collect()
@@ -1325,7 +1378,7 @@ def main():
     prof, prof_info = profile_entry(args, alex["kernel_key"])
     traffic = None if prof is None else prof.get("bytes_per_launch")
     valu_busy = None if prof is None else prof.get("valu_busy")
-    copy_gbs, copy_rates = copy_bandwidth(device)
+    copy_gbs, copy_rates = copy_bandwidth(device) if args.full else (None, None)  # a 2 GiB copy loop of its own
     if rank == 0:
         out = {
             "metric": "cell-updates/sec, 4096x(256x256) ForestFireBulldozer (Alexandridis CA), per-GPU batch",
@@ -1334,6 +1387,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": alex["ms_per_step"],
             "higher_is_better": True,
             "scaling": "weak",
@@ -1389,9 +1443,9 @@ def main():
                          "traffic_gbs": traffic / (alex["kernel_ms"] * 1e-3) / 1e9 if traffic else None,
                          "traffic_frac": traffic / (alex["kernel_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS if traffic else None,
                          "device_copy_gbs": copy_gbs,
-                         "device_copy": dict(copy_rates, kernel="gca_bench_copy: 16-B copy of 2 GiB, one element "
-                                                                "per thread, one pass"),
-                         "moved_frac_of_device_copy": alex["achieved_gbs"] / copy_gbs,
+                         "device_copy": None if copy_rates is None else dict(
+                             copy_rates, kernel="gca_bench_copy: 16-B copy of 2 GiB, one element per thread, one pass"),
+                         "moved_frac_of_device_copy": alex["achieved_gbs"] / copy_gbs if copy_gbs else None,
                          # the same run's floor of the headline kernel's own access pattern (gca_bench_march_pattern)
                          "pattern_floor_ms": alex.get("pattern_floor_ms"),
                          "kernel_over_pattern_floor": (alex["kernel_ms"] / alex["pattern_floor_ms"]

@@ -20,7 +20,7 @@ for v in $WV; do
   RC=$?; echo "pytest exit $RC" >> $O/pytest_$v.log
   [ $RC -eq 0 ] || [ $RC -eq 1 ] || exit 21
 done
-timeout -k 10 600 python bench.py > $O/bench.json 2> $O/bench.err || exit 22
+timeout -k 10 600 python bench.py --full > $O/bench.json 2> $O/bench.err || exit 22
 for pass in 1 2 3; do
   echo "$pass main $(timeout -k 10 120 python3 -u scripts/ab_march.py --only march --reps 5)" >> $O/ab.txt || exit 23
   for v in $MV; do

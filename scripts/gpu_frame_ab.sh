@@ -27,5 +27,5 @@ for PASS in "FETCH_SIZE" "WRITE_SIZE" "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_LDS SQ_WA
 done
 echo profile done > $P/done.txt
 cd $R
-if [ "$BENCH" = "1" ]; then timeout -k 10 600 python bench.py > $O/bench.json 2> $O/bench.err || exit 26; fi
+if [ "$BENCH" = "1" ]; then timeout -k 10 600 python bench.py --full > $O/bench.json 2> $O/bench.err || exit 26; fi
 echo done > $O/done.txt

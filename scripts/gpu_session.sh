@@ -24,5 +24,5 @@ for pass in 1 2 3; do
   done
 done
 if [ "$PROF" = "1" ]; then bash scripts/profile.sh $TAG || exit 25; fi
-timeout -k 10 600 python bench.py > $O/bench.json 2> $O/bench.err || exit 26
+timeout -k 10 600 python bench.py --full > $O/bench.json 2> $O/bench.err || exit 26
 echo done > $O/done.txt

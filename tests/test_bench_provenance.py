@@ -72,6 +72,46 @@ def test_profile_entry_requires_the_same_sources(tmp_path, monkeypatch):
     assert e is None
 
 
+def test_plain_run_is_the_headline_loop_alone(monkeypatch):
+    """Without --full: one repetition of exactly --steps steps, no CPU legs, no secondary sections; --full restores
+    the 5 repetitions and every section."""
+    bench = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.reps) == (7, 2, 1) and not a.full and a.dump_outputs is None
+    assert a.no_cpu_baseline and a.no_secondary
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.reps == 5 and a.dump_outputs == "d" and not a.no_cpu_baseline and not a.no_secondary
+
+
+def test_dump_outputs_writes_float32_arrays_of_a_fixed_env_sample(tmp_path):
+    """--dump-outputs: grid / fire age of the same seeded env sample on every call, the per-env results of every env,
+    all float32 .npy files."""
+    import numpy as np
+    import torch
+
+    bench = _bench()
+    E = 3 * bench.DUMP_ENVS
+    grid = torch.arange(2 * E * 4 * 4, dtype=torch.int64).reshape(2, E, 4, 4).remainder(3).to(torch.uint8)
+    age = torch.arange(2 * E * 4 * 4, dtype=torch.int64).reshape(2, E, 4, 4).remainder(673).to(torch.int16)
+    per_env = {k: torch.arange(E, dtype=dt) for k, dt in (
+        ("reward", torch.float32), ("done", torch.uint8), ("steps_elapsed", torch.float32),
+        ("reward_accumulated", torch.float32), ("wind_index", torch.int32), ("time_step", torch.int32))}
+    env = types.SimpleNamespace(num_envs=E, cur=1, grid=grid, age=age, counts=torch.ones((E, 3), dtype=torch.int32),
+                                pos=torch.zeros((E, 2), dtype=torch.int32), **per_env)
+    out = bench.headline_outputs(env)
+    idx = out["env_index"].astype(np.int64)
+    assert len(idx) == bench.DUMP_ENVS == len(set(idx.tolist())) and np.array_equal(idx, np.sort(idx))
+    assert np.array_equal(bench.headline_outputs(env)["env_index"], out["env_index"])
+    assert np.array_equal(out["grid"], grid[1].numpy()[idx]) and np.array_equal(out["fire_age"], age[1].numpy()[idx])
+    assert out["reward"].shape == (E,) and out["counts"].shape == (E, 3)
+    bench.write_outputs(str(tmp_path / "d"), out)
+    for name, a in out.items():
+        b = np.load(tmp_path / "d" / f"{name}.npy")
+        assert b.dtype == np.float32 and np.array_equal(a, b), name
+
+
 def test_algorithmic_bytes_follow_the_launched_instance():
     """roofline.algorithmic_bytes_per_cell is that of the step the env launches: the packed layout's 23.125 B, minus the
     16 B of slope planes on flat terrain, minus the layer byte with uniform layers (tiled / other layouts unchanged)."""

@@ -166,7 +166,7 @@ def _check_cpu_legs(out, measured_by):
 def test_bench_gpus2_dry_run_carries_the_cpu_baseline_to_rank0():
     """VERDICT r04 missing 3: at N > 1 the bench line carries the CPU baseline. `bench.py --gpus 2` runs the CPU legs
     in the launching parent (before any rank exists, no GPU) and hands them to rank 0, whose line reports them."""
-    rc, out, err = _bench("--gpus", "2", "--dry-run", "--envs", "7", "--cpu-seconds", "1")
+    rc, out, err = _bench("--gpus", "2", "--dry-run", "--envs", "7", "--cpu-seconds", "1", "--full")
     assert rc == 0, err[-2000:]
     assert out["n_gpus"] == 2 and out["gather_ok"]
     _check_cpu_legs(out, "parent")
@@ -183,7 +183,7 @@ def test_bench_torchrun_launch_measures_the_cpu_baseline_on_rank0():
     e = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "GCA_BENCH_CPU_JSON")}
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
                         "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(root, "bench.py"),
-                        "--gpus", "2", "--dry-run", "--envs", "5", "--cpu-seconds", "1"],
+                        "--gpus", "2", "--dry-run", "--envs", "5", "--cpu-seconds", "1", "--full"],
                        capture_output=True, text=True, timeout=240, env=e, cwd=root)
     assert p.returncode == 0, p.stderr[-2000:]
     out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
