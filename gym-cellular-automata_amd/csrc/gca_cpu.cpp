@@ -12,6 +12,7 @@
 //   gca_count_cells   ca_env.py:94-99                      (gca_util.hip)
 //   gca_move_modify   move_modify.py:37-134                (gca_env.hip move_modify_kernel)
 //   gca_ds_count_draws / gca_ds_step  ca_DrosselSchwabl.py:32-66 (gca_ds.hip), exact-stream and Philox modes
+//   gca_helicopter_step  helicopter.py:220-236 + ca_env.py:27-48 (gca_heli.hip), the batched env step's twin
 //   gca_philox        Random123 Philox4x32-10 (KAT hook)
 #include <stdarg.h>
 #include <stdint.h>
@@ -209,6 +210,95 @@ extern "C" int gca_ds_step(const uint8_t* grid_in, uint8_t* grid_out, int E, int
             counts[3 * e + 1] = cT;
             counts[3 * e + 2] = cF;
         }
+    }
+    return GCA_OK;
+}
+
+// The batched ForestFireHelicopter env step (gca_heli.hip) in plain loops: helicopter.py:220-236 + ca_env.py:27-48.
+// `meet` is not used (nothing runs in parts here) and is left as it is.
+extern "C" int gca_helicopter_step(int empty, int tree, int fire, int max_freeze, uint64_t seed, int env_offset,
+                                   const int32_t* action, uint64_t action_seed, int32_t* action_out,
+                                   const double* thresholds, int32_t* freeze, uint32_t* rng_step, uint8_t* parity,
+                                   uint8_t* buf0, uint8_t* buf1, int H, int W, int32_t* pos, int32_t* counts,
+                                   uint8_t* hit, double* reward, int64_t* steps_elapsed, uint64_t*, int E, void*) {
+    CPU_CHECK_ARG(thresholds && freeze && rng_step && parity && buf0 && buf1 && pos && counts && hit && reward &&
+                      steps_elapsed,
+                  "helicopter_step: null argument");
+    CPU_CHECK_ARG(E > 0 && H > 0 && W > 0 && max_freeze >= 0, "helicopter_step: E, H, W > 0 and max_freeze >= 0");
+    CPU_CHECK_ARG(buf0 != buf1, "helicopter_step: buf0 and buf1 must differ");
+    CPU_CHECK_ARG((int64_t)H * W < (1 << 30), "helicopter_step: grid too large");
+    CPU_CHECK_ARG(((empty | tree | fire) & ~0xFF) == 0 && empty != tree && tree != fire && empty != fire,
+                  "helicopter_step: three distinct u8 codes");
+    const int64_t HW = (int64_t)H * W;
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    gca_bulldozer_params mv = {};  // the helicopter's action sets (helicopter.py:56-62); only the masks are read
+    mv.up_mask = 0x007, mv.down_mask = 0x1C0, mv.left_mask = 0x049, mv.right_mask = 0x124;
+    for (int e = 0; e < E; ++e) {
+        const uint32_t rs = rng_step[e], env_id = (uint32_t)(env_offset + e);
+        int32_t act;
+        if (action) {
+            act = action[e];
+        } else {  // column 0 of gca_random_actions
+            const u32x4 x = philox4x32_10(u32x4{0u, env_id, rs, GCA_TAG_ACTION}, (uint32_t)action_seed,
+                                          (uint32_t)(action_seed >> 32));
+            act = (int32_t)(((uint64_t)x.x * 9u) >> 32);
+        }
+        if (action_out) action_out[e] = act;
+        int row = pos[2 * e], col = pos[2 * e + 1];
+        move_pos(act < 0 ? 0 : (act > 8 ? 8 : act), row, col, H, W, mv);
+        pos[2 * e] = row;
+        pos[2 * e + 1] = col;
+        const bool do_ca = freeze[e] == 0;
+        uint8_t* g = (parity[e] ? buf1 : buf0) + e * HW;
+        uint8_t h = 0;
+        if (do_ca) {
+            uint8_t* o = (parity[e] ? buf0 : buf1) + e * HW;
+            const double thr_fire = thresholds[2 * e], thr_tree = thresholds[2 * e + 1];
+            int32_t cE = 0, cT = 0, cF = 0;
+            for (int r = 0; r < H; ++r)
+                for (int c = 0; c < W; ++c) {
+                    const int cell = r * W + c;
+                    const int x = g[cell];
+                    int nx = x;
+                    if (x == fire) {
+                        nx = empty;
+                    } else if (x == tree && has_fire_nb(g, r, c, H, W, fire)) {
+                        nx = fire;
+                    } else if (x == tree || x == empty) {
+                        const u32x4 rx = philox4x32_10(u32x4{(uint32_t)cell, env_id, rs, GCA_TAG_DS_CELL}, k0, k1);
+                        const double u = u01_f64(rx.x, rx.y);
+                        if (x == tree) nx = u < thr_fire ? fire : tree;
+                        else nx = u < thr_tree ? tree : empty;
+                    }
+                    if (r == row && c == col && nx == fire) {  // Modify {FIRE: EMPTY} on the post-CA grid
+                        nx = empty;
+                        h = 1;
+                    }
+                    o[cell] = (uint8_t)nx;
+                    cE += nx == empty;
+                    cT += nx == tree;
+                    cF += nx == fire;
+                }
+            counts[3 * e] = cE;
+            counts[3 * e + 1] = cT;
+            counts[3 * e + 2] = cF;
+            parity[e] = parity[e] ? 0 : 1;
+            freeze[e] = max_freeze;
+        } else {
+            if (row >= 0 && row < H && col >= 0 && col < W && g[(int64_t)row * W + col] == fire) {
+                g[(int64_t)row * W + col] = (uint8_t)empty;
+                h = 1;
+                counts[3 * e] += 1;
+                counts[3 * e + 2] -= 1;
+            }
+            freeze[e] -= 1;
+        }
+        hit[e] = h;
+        const double n = (double)HW;
+        const double qt = (double)counts[3 * e + 1] / n, qf = (double)counts[3 * e + 2] / n;
+        reward[e] = qt - qf;  // helicopter.py:120-135 (built with -ffp-contract=off)
+        rng_step[e] = rs + 1u;
+        steps_elapsed[e] += 1;
     }
     return GCA_OK;
 }

@@ -1,0 +1,374 @@
+// gca_heli.hip — the whole ForestFireHelicopter env step for E envs in one launch on gfx950
+// (helicopter.py:220-236 MDP.update + ca_env.py:27-48 reward): action, Move (move_modify.py:37-67), when the env's
+// freeze countdown is 0 one Drossel–Schwabl step (ca_DrosselSchwabl.py:32-66, the Philox mode of gca_ds_step bit for
+// bit) from buf[parity] into buf[parity ^ 1], Modify {FIRE: EMPTY} at the moved position on the post-CA grid
+// (move_modify.py:128-134), freeze, counts, reward, rng_step and steps_elapsed.
+//
+// Layout: an env's rows are split over P workgroups of 4 waves (P = 1 without `meet`). W % 256 == 0: a wave takes
+// (strip of HELI_SH rows) x (256 columns), a lane 4 cells of a row as one dword; the FIRE flags are byte masks, the
+// left / right neighbours come from the adjacent lanes (DPP wave shifts), a row is loaded once per strip and its
+// horizontal 3-cell OR is carried down the strip. Other widths: a cell per thread, nine byte loads.
+// No prefix scan: a cell's draw is keyed by its index (Philox (cell, global env id, rng_step, DSCE)), not by its rank.
+// `u < thr` is the integer test (bits >> 11) < ceil(thr * 2^53) (scaling by 2^53 is exact), the two integer
+// thresholds computed once per env.
+// Modify is folded into the CA's own store of that cell: the thread that computes the helicopter's cell writes EMPTY
+// instead of FIRE and reports the hit, so there is no second pass over the grid and no barrier between CA and Modify.
+// On a step without a CA pass one thread patches the byte in place.
+// The parts meet like bulldozer_step_fused_parts_kernel: one 64-bit atomic per env carries the part's E | T | F counts
+// (20 bits each), the hit bit and an arrival count in the top 3 bits; the last to arrive writes every per-env output
+// and leaves the slot zero. Nothing waits for anything: a part adds its word and leaves.
+#include "gca_common.h"
+
+namespace {
+
+constexpr int HELI_SH = 16;       // rows per strip of the dword path
+constexpr int HELI_THREADS = 256;
+
+__device__ __forceinline__ uint32_t heli_shr1(uint32_t v) {  // lane l <- lane l-1, lane 0 <- 0
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xF, 0xF, true);
+}
+__device__ __forceinline__ uint32_t heli_shl1(uint32_t v) {  // lane l <- lane l+1, lane 63 <- 0
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x130, 0xF, 0xF, true);
+}
+
+// ceil(thr * 2^53) clamped to [0, 2^53]: v < it  <=>  (double)v * 2^-53 < thr for every 53-bit v (NaN: never)
+__device__ __forceinline__ uint64_t heli_int_threshold(double thr) {
+    if (!(thr > 0.0)) return 0ull;
+    if (thr >= 1.0) return 1ull << 53;
+    return (uint64_t)ceil(thr * 0x1.0p53);
+}
+
+struct HeliRow {
+    uint32_t x;  // the row's 4 cells of this lane
+    uint32_t f;  // FIRE flags (0x01 per byte), 0 for a row outside the grid (padding = EMPTY)
+    uint32_t h;  // f of (c-1) | c | (c+1) per byte
+};
+
+// raw loads of row R (clamped into the grid; a row outside is discarded by heli_classify): the lane's dword and, when
+// the row continues beyond this 256-column chunk, the one byte to the left of lane 0 / right of lane 63
+struct HeliRaw {
+    uint32_t x, halo;
+};
+__device__ __forceinline__ HeliRaw heli_load(const uint8_t* __restrict__ S, int R, int H, int W, int col0, int lane,
+                                             bool has_left, bool has_right) {
+    const int Rc = min(max(R, 0), H - 1);
+    const uint8_t* p = S + (uint32_t)Rc * (uint32_t)W + (uint32_t)col0;
+    HeliRaw r;
+    r.x = *reinterpret_cast<const uint32_t*>(p);
+    r.halo = 0u;
+    if (has_left && lane == 0) r.halo = p[-1];
+    if (has_right && lane == 63) r.halo = p[4];
+    return r;
+}
+__device__ __forceinline__ HeliRow heli_classify(const HeliRaw& raw, bool valid, uint32_t Fp, int lane, bool has_left,
+                                                 bool has_right) {
+    HeliRow o;
+    o.x = raw.x;
+    o.f = valid ? bytes_eq01(raw.x, Fp) : 0u;
+    uint32_t prev = heli_shr1(o.f), next = heli_shl1(o.f);
+    const uint32_t hf = (valid && raw.halo == (Fp & 0xFFu)) ? 1u : 0u;
+    if (has_left && lane == 0) prev = hf << 24;
+    if (has_right && lane == 63) next = hf;
+    const uint32_t fl = __builtin_amdgcn_alignbyte(o.f, prev, 3);  // byte i = flag of column c-1
+    const uint32_t fr = __builtin_amdgcn_alignbyte(next, o.f, 1);  // byte i = flag of column c+1
+    o.h = o.f | fl | fr;
+    return o;
+}
+
+struct HeliCtx {
+    uint32_t Ep, Tp, Fp;       // replicated codes
+    uint32_t k0, k1, env_id, step;
+    uint64_t it_fire, it_tree;
+    int prow, pcol;            // the helicopter's (moved) position
+};
+
+// one draw: Philox((cell, env, step, DSCE)) -> 53 bits < threshold (gca_ds_step's u01_f64(x.x, x.y) < thr)
+__device__ __forceinline__ bool heli_draw(const HeliCtx& c, uint32_t cell, bool is_tree) {
+    const u32x4 rx = philox4x32_10(u32x4{cell, c.env_id, c.step, GCA_TAG_DS_CELL}, c.k0, c.k1);
+    const uint64_t v = (((uint64_t)rx.x << 32) | rx.y) >> 11;
+    return v < (is_tree ? c.it_fire : c.it_tree);
+}
+
+// rows [r0, min(r0 + HELI_SH, H)) x columns [256 ch, 256 ch + 256) of one env, by one wave
+__device__ __forceinline__ void heli_strip(const uint8_t* __restrict__ S, uint8_t* __restrict__ D, int r0, int ch,
+                                           int nch, int H, int W, int lane, const HeliCtx& c, int32_t& cE, int32_t& cT,
+                                           int32_t& cF, int32_t& hit) {
+    const int col0 = 256 * ch + 4 * lane;
+    const bool hl = ch > 0, hr = ch < nch - 1;
+    HeliRow A = heli_classify(heli_load(S, r0 - 1, H, W, col0, lane, hl, hr), r0 >= 1, c.Fp, lane, hl, hr);
+    HeliRow B = heli_classify(heli_load(S, r0, H, W, col0, lane, hl, hr), true, c.Fp, lane, hl, hr);
+    HeliRaw ahead = heli_load(S, r0 + 1, H, W, col0, lane, hl, hr);
+    const int rows = min(HELI_SH, H - r0);
+    for (int t = 0; t < rows; ++t) {
+        const int R = r0 + t;
+        const HeliRow C = heli_classify(ahead, R + 1 < H, c.Fp, lane, hl, hr);
+        if (t + 1 < rows) ahead = heli_load(S, R + 2, H, W, col0, lane, hl, hr);
+        const uint32_t nb = A.h | B.h | C.h;  // a burning Moore neighbour (the centre itself only matters for TREE)
+        const uint32_t tr = bytes_eq01(B.x, c.Tp), em = bytes_eq01(B.x, c.Ep);
+        const uint32_t ign = tr & nb;         // TREE -> FIRE, no draw
+        const uint32_t dT = tr ^ ign;         // TREE that draws
+        const uint32_t dr = dT | em;          // cells that draw
+        uint32_t win = 0u;
+        const uint32_t cell0 = (uint32_t)R * (uint32_t)W + (uint32_t)col0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const bool d = (dr >> (8 * j)) & 1u;
+            if (__ballot(d) != 0ull) {  // wave-uniform: no Philox call for a wave whose cells draw nothing
+                const bool w = heli_draw(c, cell0 + j, (dT >> (8 * j)) & 1u);
+                win |= (d && w) ? (1u << (8 * j)) : 0u;
+            }
+        }
+        uint32_t nF = ign | (dT & win);
+        const uint32_t nT = (dT & ~win) | (em & win);
+        uint32_t nE = (em & ~win) | B.f;
+        // Modify folded into the store: the helicopter's cell, if it would be FIRE, is written EMPTY
+        const uint32_t dc = (uint32_t)(c.pcol - col0);
+        const uint32_t mk = (R == c.prow && dc < 4u) ? (1u << (8 * dc)) : 0u;
+        const uint32_t hw = nF & mk;
+        nF ^= hw;
+        nE |= hw;
+        hit += hw != 0u;
+        const uint32_t known = nE | nT | nF;  // 0x01 where the cell holds one of the three codes
+        const uint32_t out = nE * (c.Ep & 0xFFu) + nT * (c.Tp & 0xFFu) + nF * (c.Fp & 0xFFu) +
+                             (B.x & ~(known * 0xFFu));
+        *reinterpret_cast<uint32_t*>(D + cell0) = out;
+        cE += __popc(nE);
+        cT += __popc(nT);
+        cF += __popc(nF);
+        A = B;
+        B = C;
+    }
+}
+
+// cells [begin, end) of one env, a cell per thread (any W)
+__device__ __forceinline__ void heli_cells(const uint8_t* __restrict__ S, uint8_t* __restrict__ D, int begin, int end,
+                                           int H, int W, int tid, const HeliCtx& c, int32_t& cE, int32_t& cT,
+                                           int32_t& cF, int32_t& hit) {
+    const int empty = (int)(c.Ep & 0xFFu), tree = (int)(c.Tp & 0xFFu), fire = (int)(c.Fp & 0xFFu);
+    for (int cell = begin + tid; cell < end; cell += HELI_THREADS) {
+        const int r = cell / W, col = cell - r * W;
+        const int x = S[cell];
+        int nx = x;
+        if (x == fire) {
+            nx = empty;
+        } else if (x == tree || x == empty) {
+            bool nbf = false;
+            if (x == tree) {
+#pragma unroll
+                for (int dr = -1; dr <= 1; ++dr) {
+#pragma unroll
+                    for (int dc = -1; dc <= 1; ++dc) {
+                        const int rr = r + dr, cc = col + dc;
+                        if ((dr | dc) != 0 && rr >= 0 && rr < H && cc >= 0 && cc < W && S[rr * W + cc] == fire)
+                            nbf = true;
+                    }
+                }
+            }
+            if (nbf) nx = fire;
+            else if (heli_draw(c, (uint32_t)cell, x == tree)) nx = x == tree ? fire : tree;
+        }
+        if (r == c.prow && col == c.pcol && nx == fire) {  // Modify folded into the store
+            nx = empty;
+            hit += 1;
+        }
+        D[cell] = (uint8_t)nx;
+        cE += nx == empty;
+        cT += nx == tree;
+        cF += nx == fire;
+    }
+}
+
+struct HeliArgs {
+    int empty, tree, fire, max_freeze;
+    uint64_t seed, action_seed;
+    int env_offset;
+    const int32_t* action;
+    int32_t* action_out;
+    const double* thr;
+    int32_t* freeze;
+    uint32_t* rng_step;
+    uint8_t* parity;
+    uint8_t* buf0;
+    uint8_t* buf1;
+    int H, W;
+    int32_t* pos;
+    int32_t* counts;
+    uint8_t* hit;
+    double* reward;
+    int64_t* steps_elapsed;
+    unsigned long long* meet;
+    int P;
+};
+
+// FAST: W % 256 == 0 and 4-byte aligned grids. Block = (env, part), 4 waves. Every wave of every block reaches the one
+// barrier (it stands outside every condition), whatever its share of the rows.
+template <bool FAST>
+__global__ __launch_bounds__(HELI_THREADS) void helicopter_step_kernel(HeliArgs a) {
+    __shared__ int32_t wave_cnt[HELI_THREADS / 64][4];
+    const int P = a.P;
+    const int e = blockIdx.x / P, part = blockIdx.x - e * P;
+    const int tid = threadIdx.x;
+    const int H = a.H, W = a.W;
+    // ---- every per-env input, read before anything of this env is written by anyone (the last part to arrive at
+    //      `meet` writes, and it arrives after every part's reads: each part's word depends on them)
+    const uint32_t rs = a.rng_step[e];
+    const uint32_t env_id = (uint32_t)(a.env_offset + e);
+    int32_t act;
+    if (a.action) {
+        act = a.action[e];
+    } else {  // column 0 of gca_random_actions
+        const u32x4 x = philox4x32_10(u32x4{0u, env_id, rs, GCA_TAG_ACTION}, (uint32_t)a.action_seed,
+                                      (uint32_t)(a.action_seed >> 32));
+        act = randint_ms(x.x, 0, 9);
+    }
+    const int32_t fz = a.freeze[e];
+    const bool odd = a.parity[e] != 0;
+    const int32_t prow0 = a.pos[2 * e], pcol0 = a.pos[2 * e + 1];
+    const int32_t c0 = a.counts[3 * e + 0], c1 = a.counts[3 * e + 1], c2 = a.counts[3 * e + 2];
+    const int64_t se = a.steps_elapsed[e];
+    const double thr_fire = a.thr[2 * e], thr_tree = a.thr[2 * e + 1];
+    // ---- Move (helicopter.py:56-62 action sets): up {0,1,2}, down {6,7,8}, left {0,3,6}, right {2,5,8}
+    const int a0 = clampi_dev(act, 0, 8);
+    int row = prow0, col = pcol0;
+    move_pos(a0, row, col, H, W, 0x007, 0x1C0, 0x049, 0x124);
+    const bool do_ca = fz == 0;
+    const int64_t HW = (int64_t)H * W;
+    uint8_t* cur = (odd ? a.buf1 : a.buf0) + e * HW;
+    uint8_t* nxt = (odd ? a.buf0 : a.buf1) + e * HW;
+    int32_t cE = 0, cT = 0, cF = 0, hitc = 0;
+    if (do_ca) {
+        HeliCtx c;
+        c.Ep = rep4((uint32_t)a.empty);
+        c.Tp = rep4((uint32_t)a.tree);
+        c.Fp = rep4((uint32_t)a.fire);
+        c.k0 = (uint32_t)a.seed;
+        c.k1 = (uint32_t)(a.seed >> 32);
+        c.env_id = env_id;
+        c.step = rs;
+        c.it_fire = heli_int_threshold(thr_fire);
+        c.it_tree = heli_int_threshold(thr_tree);
+        c.prow = row;
+        c.pcol = col;
+        if constexpr (FAST) {
+            const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+            const int nch = W >> 8;
+            const int strips = (H + HELI_SH - 1) / HELI_SH, spp = (strips + P - 1) / P;
+            const int s_begin = part * spp, s_end = min(strips, s_begin + spp);
+            const int items = max(s_end - s_begin, 0) * nch;
+            for (int i = wave; i < items; i += HELI_THREADS / 64) {
+                const int s = s_begin + i / nch, ch = i - (i / nch) * nch;
+                heli_strip(cur, nxt, s * HELI_SH, ch, nch, H, W, lane, c, cE, cT, cF, hitc);
+            }
+        } else {
+            const int rpp = (H + P - 1) / P;
+            const int r_begin = min(part * rpp, H), r_end = min(H, r_begin + rpp);
+            heli_cells(cur, nxt, r_begin * W, r_end * W, H, W, tid, c, cE, cT, cF, hitc);
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            cE += __shfl_xor(cE, off);
+            cT += __shfl_xor(cT, off);
+            cF += __shfl_xor(cF, off);
+            hitc += __shfl_xor(hitc, off);
+        }
+    }
+    if ((tid & 63) == 0) {
+        wave_cnt[tid >> 6][0] = cE;
+        wave_cnt[tid >> 6][1] = cT;
+        wave_cnt[tid >> 6][2] = cF;
+        wave_cnt[tid >> 6][3] = hitc;
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    int32_t pE = 0, pT = 0, pF = 0;
+    uint32_t h = 0;
+#pragma unroll
+    for (int w = 0; w < HELI_THREADS / 64; ++w) {
+        pE += wave_cnt[w][0];
+        pT += wave_cnt[w][1];
+        pF += wave_cnt[w][2];
+        h |= wave_cnt[w][3] != 0;
+    }
+    if (!do_ca && part == 0 && row >= 0 && row < H && col >= 0 && col < W) {
+        // no CA pass: Modify patches the one byte in place (a caller's own position outside the grid writes nothing)
+        uint8_t* g = cur + (int64_t)row * W + col;
+        if (*g == (uint8_t)a.fire) {
+            *g = (uint8_t)a.empty;
+            h = 1;
+        }
+    }
+    unsigned long long tot = (unsigned long long)(uint32_t)pE | ((unsigned long long)(uint32_t)pT << 20) |
+                             ((unsigned long long)(uint32_t)pF << 40) | ((unsigned long long)h << 60);
+    if (a.meet) {
+        const unsigned long long pk = tot | (1ull << 61);
+        const unsigned long long old = atomicAdd(&a.meet[e], pk);
+        if ((int)(old >> 61) != P - 1) return;  // not the last part to arrive
+        tot = old + pk;
+        a.meet[e] = 0ull;
+    }
+    int32_t nE, nT, nF;
+    const uint8_t hh = (uint8_t)((tot >> 60) & 1u);
+    if (do_ca) {
+        nE = (int32_t)(tot & 0xFFFFFu);
+        nT = (int32_t)((tot >> 20) & 0xFFFFFu);
+        nF = (int32_t)((tot >> 40) & 0xFFFFFu);
+        a.parity[e] = odd ? 0 : 1;
+    } else {
+        nE = c0 + hh;
+        nT = c1;
+        nF = c2 - hh;
+    }
+    if (a.action_out) a.action_out[e] = act;
+    a.pos[2 * e] = row;
+    a.pos[2 * e + 1] = col;
+    a.freeze[e] = do_ca ? a.max_freeze : fz - 1;
+    a.counts[3 * e + 0] = nE;
+    a.counts[3 * e + 1] = nT;
+    a.counts[3 * e + 2] = nF;
+    a.hit[e] = hh;
+    // helicopter.py:120-135: dot([0, 1, -1], counts / ncells) = cT / n - cF / n (0 * x and the first add are exact)
+    const double n = (double)HW;
+    a.reward[e] = __dsub_rn(__ddiv_rn((double)nT, n), __ddiv_rn((double)nF, n));
+    a.rng_step[e] = rs + 1u;
+    a.steps_elapsed[e] = se + 1;
+}
+
+}  // namespace
+
+extern "C" int gca_helicopter_step(int empty, int tree, int fire, int max_freeze, uint64_t seed, int env_offset,
+                                   const int32_t* action, uint64_t action_seed, int32_t* action_out,
+                                   const double* thresholds, int32_t* freeze, uint32_t* rng_step, uint8_t* parity,
+                                   uint8_t* buf0, uint8_t* buf1, int H, int W, int32_t* pos, int32_t* counts,
+                                   uint8_t* hit, double* reward, int64_t* steps_elapsed, uint64_t* meet, int E,
+                                   void* stream) {
+    GCA_CHECK_ARG(thresholds && freeze && rng_step && parity && buf0 && buf1 && pos && counts && hit && reward &&
+                      steps_elapsed,
+                  "helicopter_step: null argument");
+    GCA_CHECK_ARG(E > 0 && H > 0 && W > 0 && max_freeze >= 0, "helicopter_step: E, H, W > 0 and max_freeze >= 0");
+    GCA_CHECK_ARG(buf0 != buf1, "helicopter_step: buf0 and buf1 must differ");
+    GCA_CHECK_ARG((int64_t)H * W < (1 << 30), "helicopter_step: grid too large");
+    GCA_CHECK_ARG(((empty | tree | fire) & ~0xFF) == 0 && empty != tree && tree != fire && empty != fire,
+                  "helicopter_step: three distinct u8 codes");
+    const int64_t HW = (int64_t)H * W;
+    const bool fast = W % 256 == 0 && (((uintptr_t)buf0 | (uintptr_t)buf1) & 3u) == 0;
+    // the parts' word packs 20-bit counts: larger grids (and every grid without `meet`) run one workgroup per env;
+    // parts only while the launch is small (E * P < 1024 workgroups) and every part keeps at least two strips / rows
+    const int units = fast ? (H + HELI_SH - 1) / HELI_SH : H;
+    int P = 1;
+    if (meet && HW + 1 < (1 << 20))
+        while (P < 8 && (int64_t)E * P < 1024 && 2 * P <= units) P *= 2;
+    GCA_CHECK_ARG((int64_t)E * P < (1ll << 31), "helicopter_step: too many workgroups");
+    HeliArgs a;
+    a.empty = empty; a.tree = tree; a.fire = fire; a.max_freeze = max_freeze;
+    a.seed = seed; a.action_seed = action_seed; a.env_offset = env_offset;
+    a.action = action; a.action_out = action_out; a.thr = thresholds; a.freeze = freeze; a.rng_step = rng_step;
+    a.parity = parity; a.buf0 = buf0; a.buf1 = buf1; a.H = H; a.W = W; a.pos = pos; a.counts = counts; a.hit = hit;
+    a.reward = reward; a.steps_elapsed = steps_elapsed;
+    a.meet = P > 1 ? (unsigned long long*)meet : nullptr;
+    a.P = P;
+    const dim3 grid((unsigned)((int64_t)E * P)), block(HELI_THREADS);
+    if (fast) hipLaunchKernelGGL(helicopter_step_kernel<true>, grid, block, 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(helicopter_step_kernel<false>, grid, block, 0, (hipStream_t)stream, a);
+    GCA_CHECK_LAUNCH("helicopter_step");
+    return GCA_OK;
+}

@@ -1,3 +1,4 @@
+from .batched import BatchedForestFireHelicopterEnv
 from .helicopter import ForestFireHelicopterEnv
 
-__all__ = ["ForestFireHelicopterEnv"]
+__all__ = ["ForestFireHelicopterEnv", "BatchedForestFireHelicopterEnv"]

@@ -1,0 +1,241 @@
+"""BatchedForestFireHelicopterEnv — E ForestFireHelicopter envs resident in HBM, one launch per env step.
+
+The batched form of helicopter.py's MDP (reference helicopter.py:220-236 + ca_env.py:27-48). gca_helicopter_step
+does the whole step of every env: the action (the caller's, or drawn inside the step), Move, the Drossel–Schwabl CA
+when the env's freeze countdown is 0, Modify {FIRE: EMPTY} at the moved position, freeze, cell counts and reward.
+
+Grids live in two buffers; env e's current grid is buf[parity[e]][e], so an env whose countdown is still running
+moves no bytes beyond the one cell Modify may patch. The CA's draws are Philox keyed by (cell, global env id,
+rng_step) -- the Philox mode of gca_ds_step, bit for bit -- so a sharded env (env_offset) reproduces the unsharded one
+env for env. Replaying numpy's stream cell for cell stays the single-env ForestFireHelicopterEnv's role.
+"""
+import numpy as np
+
+from ... import _device as dev
+from ..._lib import SLOT, BoundCall, call
+from ..operators.ca_DrosselSchwabl import choice_threshold
+
+# state the pre-bound calls hold by address (step, step_random, sample_actions): assigning one of these attributes
+# validates the replacement and drops the bound calls (rebind), so the next step binds the new tensor
+_BOUND_STATE = frozenset({"buf", "parity", "freeze", "pos", "counts", "rng_step", "hit", "reward", "steps_elapsed",
+                          "thresholds", "_meet", "_act_buf", "_act2"})
+
+
+class BatchedForestFireHelicopterEnv:
+    def __setattr__(self, name, value):
+        d = self.__dict__
+        if name in _BOUND_STATE and "_step_call" in d and d.get(name) is not value:
+            old = d.get(name)
+            if not (dev.is_device_tensor(value) and value.dtype == old.dtype and value.shape == old.shape
+                    and value.device == old.device and value.is_contiguous()):
+                raise ValueError(f"env.{name}: the replacement must be a contiguous {old.dtype} tensor of shape "
+                                 f"{tuple(old.shape)} on {old.device} (or update the tensor in place)")
+            object.__setattr__(self, name, value)
+            self.rebind()
+            return
+        object.__setattr__(self, name, value)
+
+    def __init__(self, num_envs, nrows, ncols, device=None, seed=0, env_offset=0, speed=0.5, freeze=None,
+                 p_fire=0.033, p_tree=0.333, materialize_obs=True):
+        import torch
+
+        self.device = dev.require_device(device)
+        self.num_envs, self.nrows, self.ncols = E, H, W = int(num_envs), int(nrows), int(ncols)
+        if E < 1 or H < 1 or W < 1 or H * W >= 2**30:
+            raise ValueError("num_envs, nrows, ncols >= 1 and nrows * ncols < 2**30")
+        self.seed_value = int(seed)
+        self.env_offset = int(env_offset)
+        self.materialize_obs = materialize_obs
+        self._empty, self._tree, self._fire = 0, 1, 2
+        self._p_fire, self._p_tree = float(p_fire), float(p_tree)
+        self.max_freeze = int(speed * ((H + W) // 2)) if freeze is None else int(freeze)
+        if self.max_freeze < 0:
+            raise ValueError("freeze >= 0")
+        kw = dict(device=self.device)
+        self.buf = torch.zeros((2, E, H, W), dtype=torch.uint8, **kw)
+        self.parity = torch.zeros(E, dtype=torch.uint8, **kw)
+        self.freeze = torch.full((E,), self.max_freeze, dtype=torch.int32, **kw)
+        self.pos = torch.zeros((E, 2), dtype=torch.int32, **kw)
+        self.counts = torch.zeros((E, 3), dtype=torch.int32, **kw)
+        self.rng_step = torch.zeros(E, dtype=torch.int32, **kw)  # uint32 bits
+        self.hit = torch.zeros(E, dtype=torch.uint8, **kw)
+        self.reward = torch.zeros(E, dtype=torch.float64, **kw)
+        self.steps_elapsed = torch.zeros(E, dtype=torch.int64, **kw)
+        # cdf[0] of numpy's choice([True, False], p=[p, 1 - p]) per env: what gca_ds_step takes
+        thr = np.array([choice_threshold(self._p_fire), choice_threshold(self._p_tree)], dtype=np.float64)
+        self.thresholds = dev.to_device(np.broadcast_to(thr, (E, 2)), torch.float64, self.device)
+        self.ca_params = dev.to_device(np.broadcast_to(np.array([self._p_fire, self._p_tree]), (E, 2)), torch.float64,
+                                       self.device)
+        # the step's per-env meeting slots (gca_helicopter_step: several workgroups per env at small E), kept zero
+        self._meet = torch.zeros(E, dtype=torch.int64, **kw)
+        self._terminated = torch.zeros(E, dtype=torch.bool, **kw)
+        self._truncated = torch.zeros(E, dtype=torch.bool, **kw)
+        self._dev_index = dev.device_index(self.device)
+        self._act_buf = torch.zeros(E, dtype=torch.int32, **kw)
+        self._act2 = torch.zeros((E, 2), dtype=torch.int32, **kw)  # gca_random_actions draws (move, shoot) pairs
+        self._act_shape = self._act_buf.shape
+        self._step_call = None
+        self.rebind()
+
+    # ------------------------------------------------------------------ state
+    def grids(self):
+        """(E, H, W) uint8: every env's current grid (one gather pass)."""
+        import torch
+
+        return torch.where(self.parity.bool()[:, None, None], self.buf[1], self.buf[0])
+
+    def _recount(self):
+        E, H, W = self.num_envs, self.nrows, self.ncols
+        self.buf[0].copy_(self.grids())
+        self.parity.zero_()
+        call("gca_count_cells", dev.ptr(self.buf[0]), E, H, W, self._empty, self._tree, self._fire,
+             dev.ptr(self.counts), dev.stream_ptr(self.device))
+
+    def _check_positions(self, positions):
+        E, H, W = self.num_envs, self.nrows, self.ncols
+        pos = np.asarray(positions).reshape(E, 2)
+        if not ((pos[:, 0] >= 0) & (pos[:, 0] < H) & (pos[:, 1] >= 0) & (pos[:, 1] < W)).all():
+            raise ValueError(f"every position must lie inside the {H}x{W} grid")
+        return pos.astype(np.int32)
+
+    def reset(self, seed=None, grids=None, positions=None):
+        """Reset all envs: the grid uniform over {EMPTY, TREE, FIRE} (grid_space.sample(), helicopter.py:33-42) from
+        Philox keyed by the global env id, the helicopter at the centre, freeze = max_freeze."""
+        import torch
+
+        E, H, W = self.num_envs, self.nrows, self.ncols
+        if grids is not None:
+            self.buf[0].copy_(dev.to_device(np.asarray(grids).reshape(E, H, W).astype(np.uint8), torch.uint8,
+                                            self.device))
+        else:
+            cdf = torch.tensor([1.0 / 3.0, 2.0 / 3.0, 1.0], dtype=torch.float32, device=self.device)
+            vals = torch.tensor([self._empty, self._tree, self._fire], dtype=torch.uint8, device=self.device)
+            call("gca_fill_categorical", dev.ptr(self.buf[0]), H * W, E, self.env_offset,
+                 (self.seed_value if seed is None else int(seed)) & (2**64 - 1), dev.ptr(cdf), dev.ptr(vals), 3,
+                 dev.stream_ptr(self.device))
+        if positions is not None:
+            self.pos.copy_(torch.as_tensor(self._check_positions(positions), device=self.device))
+        else:
+            self.pos[:, 0] = H // 2
+            self.pos[:, 1] = W // 2
+        self.parity.zero_()
+        self.freeze.fill_(self.max_freeze)
+        self.hit.zero_()
+        self.reward.zero_()
+        self.rng_step.zero_()
+        self.steps_elapsed.zero_()
+        self._recount()
+        return self._obs(), {"hit": self.hit}
+
+    def set_state(self, grid=None, pos=None, freeze=None, rng_step=None):
+        """Overwrite parts of the state in place (host arrays or device tensors, leading axis E); the cell counts
+        are taken again from the grids."""
+        import torch
+
+        E, H, W = self.num_envs, self.nrows, self.ncols
+        if grid is not None:
+            g = grid if dev.is_device_tensor(grid) else np.asarray(grid).astype(np.uint8)
+            self.buf[0].copy_(dev.to_device(g, torch.uint8, self.device).reshape(E, H, W))
+            self.parity.zero_()
+        if pos is not None:
+            p = pos.cpu().numpy() if dev.is_device_tensor(pos) else pos
+            self.pos.copy_(torch.as_tensor(self._check_positions(p), device=self.device))
+        if freeze is not None:
+            f = freeze if dev.is_device_tensor(freeze) else np.broadcast_to(np.asarray(freeze, dtype=np.int64), (E,))
+            self.freeze.copy_(dev.to_device(f, torch.int32, self.device).reshape(E))
+        if rng_step is not None:
+            r = rng_step if dev.is_device_tensor(rng_step) else \
+                np.broadcast_to(np.asarray(rng_step, dtype=np.int64), (E,)).astype(np.uint32).view(np.int32)
+            self.rng_step.copy_(dev.to_device(r, torch.int32, self.device).reshape(E))
+        self._recount()
+
+    def _obs(self):
+        return (self.grids() if self.materialize_obs else None), self._ctx
+
+    def _action(self, action):
+        """action as a contiguous int32 (E,) device tensor: the caller's own tensor when it is one (checked on every
+        call), else converted into the env's action buffer."""
+        import torch
+
+        if (type(action) is torch.Tensor and action.dtype is torch.int32 and action.get_device() == self._dev_index
+                and action.shape == self._act_shape and action.is_contiguous()):
+            return action
+        src = action if dev.is_device_tensor(action) else torch.as_tensor(np.asarray(action))
+        self._act_buf.copy_(src.reshape(self.num_envs))
+        return self._act_buf
+
+    def rebind(self):
+        """Drop the pre-bound calls. The state tensors are bound by address on the first step and every method here
+        updates them in place; assigning a new tensor to one of them calls this by itself (__setattr__, which also
+        checks the replacement's dtype / shape / device). The bound calls hold references to what they bound, so
+        nothing they address is freed under them."""
+        self._step_call = None
+        self._random_call = None
+        self._sample_call = None
+        self._info = {"hit": self.hit}
+        self._ctx = {"ca_params": self.ca_params, "position": self.pos, "freeze": self.freeze}
+
+    def _bound_tensors(self):
+        return (self.thresholds, self.freeze, self.rng_step, self.parity, self.buf, self.pos, self.counts, self.hit,
+                self.reward, self.steps_elapsed, self._meet)
+
+    def _bind(self, action, action_seed, action_out, keep=()):
+        E, H, W = self.num_envs, self.nrows, self.ncols
+        return BoundCall(
+            "gca_helicopter_step", self._empty, self._tree, self._fire, self.max_freeze,
+            self.seed_value & (2**64 - 1), self.env_offset, action, action_seed, action_out,
+            dev.ptr(self.thresholds), dev.ptr(self.freeze), dev.ptr(self.rng_step), dev.ptr(self.parity),
+            dev.ptr(self.buf[0]), dev.ptr(self.buf[1]), H, W, dev.ptr(self.pos), dev.ptr(self.counts),
+            dev.ptr(self.hit), dev.ptr(self.reward), dev.ptr(self.steps_elapsed), dev.ptr(self._meet), E, SLOT,
+            keep=self._bound_tensors() + tuple(keep))
+
+    def _result(self):
+        return self._obs(), self.reward, self._terminated, self._truncated, self._info
+
+    # ------------------------------------------------------------------ step
+    def step(self, action):
+        """action: (E,) int in [0, 9) (clamped), device tensor or numpy. Returns ((grids | None, context), reward,
+        terminated, truncated, info) as device tensors that the next step overwrites in place (terminated and
+        truncated are persistent all-False tensors: the env never ends, helicopter.py:137-138); clone to keep them. A
+        contiguous int32 (E,) device action is used as it is. One launch, no allocation (with materialize_obs=False)
+        and no sync."""
+        a = self._action(action)
+        sc = self._step_call
+        if sc is None:
+            sc = self._step_call = self._bind(SLOT, 0, None)
+        sc(a.data_ptr(), dev.raw_stream(self._dev_index))
+        return self._result()
+
+    def _check_out(self, out, who):
+        import torch
+
+        if not (type(out) is torch.Tensor and out.dtype is torch.int32 and out.get_device() == self._dev_index
+                and out.shape == self._act_shape and out.is_contiguous()):
+            raise ValueError(f"{who}: the output must be a contiguous int32 (E,) tensor on the env's device")
+        return out
+
+    def step_random(self, seed=9, action_out=None):
+        """One env step of every env under a uniform random policy, the action drawn INSIDE the step exactly as
+        sample_actions(out, tag=seed) draws it before step(out): the two in one launch, bit for bit. The drawn actions
+        go to `action_out` (a contiguous int32 (E,) device tensor, default the env's action buffer)."""
+        out = self._check_out(self._act_buf if action_out is None else action_out, "step_random")
+        key = (seed, out.data_ptr())
+        rc = self._random_call
+        if rc is None or rc[0] != key or rc[1] is not out:
+            rc = self._random_call = (key, out, self._bind(None, int(seed) & (2**64 - 1), dev.ptr(out), keep=(out,)))
+        rc[2](dev.raw_stream(self._dev_index))
+        return self._result()
+
+    def sample_actions(self, out=None, tag=9):
+        """Uniform random actions in [0, 9) for every env on the device -- the batched `action_space.sample()`: column
+        0 of gca_random_actions (Philox keyed by (tag, global env id, the env's rng_step)) -- into `out` (a contiguous
+        int32 (E,) device tensor) or the env's action buffer. Returns the tensor."""
+        out = self._check_out(self._act_buf if out is None else out, "sample_actions")
+        sc = self._sample_call
+        if sc is None or sc[0] != tag:
+            sc = self._sample_call = (tag, BoundCall("gca_random_actions", dev.ptr(self._act2), self.num_envs,
+                                                     self.env_offset, int(tag) & (2**64 - 1), dev.ptr(self.rng_step),
+                                                     SLOT, keep=(self._act2, self.rng_step)))
+        sc[1](dev.raw_stream(self._dev_index))
+        out.copy_(self._act2[:, 0])
+        return out

@@ -484,6 +484,32 @@ int gca_ds_step(const uint8_t* grid_in, uint8_t* grid_out, int E, int H, int W, 
                 const double* uniforms, const int64_t* uniform_offset, uint64_t seed, const uint32_t* rng_step,
                 int env_offset, int32_t* counts, void* stream);
 
+/* The whole ForestFireHelicopter env step for E envs in one launch (helicopter.py:220-236 MDP.update + ca_env.py:27-48
+ * step / reward; operators: move_modify.py:37-67 Move, :128-134 MoveModify, ca_DrosselSchwabl.py:32-66 ForestFire):
+ *   action   action[e] clamped to [0, 8]; action == NULL: randint_ms(x.x, 0, 9) of Philox((0, env_offset+e,
+ *            rng_step[e], GCA_TAG_ACTION), action_seed), column 0 of gca_random_actions, written to action_out[e]
+ *            (nullable; with a caller's action it receives that action unclamped)
+ *   Move     pos[e] under the helicopter's action sets up {0,1,2}, down {6,7,8}, left {0,3,6}, right {2,5,8}
+ *   CA       iff freeze[e] == 0: one Drossel-Schwabl step from buf[parity[e]][e] into buf[parity[e]^1][e], parity
+ *            flipped; bit-identical to gca_ds_step(..., uniforms = NULL, seed, rng_step, env_offset) on that grid
+ *   Modify   always on, at the moved position on the post-CA grid: FIRE -> EMPTY and hit[e] = 1, else hit[e] = 0
+ *   freeze   max_freeze after a CA step, else freeze - 1
+ *   counts   [E][3] EMPTY / TREE / FIRE of the env's grid after the step (in: of its grid before the step)
+ *   reward   (double)T / n - (double)F / n, n = H*W: two IEEE divisions and one subtraction, which is
+ *            np.dot([0, 1, -1], counts / ncells) (helicopter.py:120-135) bit for bit
+ *   rng_step[e] += 1, steps_elapsed[e] += 1; the env never terminates (helicopter.py:137-138).
+ * thresholds [E][2] as gca_ds_step's. Any H, W >= 1 with H*W < 2^30; W % 256 == 0 with 4-byte aligned grids takes the
+ * dword path. Three distinct u8 codes; cells holding another value are copied and not counted.
+ * meet (nullable): E 64-bit slots, zero-initialised once by the caller (every launch leaves them zero); with them a
+ * small launch (E * P < 1024) splits each env's rows over P <= 8 workgroups that meet in one atomic per env, the last
+ * to arrive writing the env's outputs -- the same results; NULL, or H*W + 1 >= 2^20: one workgroup per env. Not
+ * shared between concurrent launches. The host build runs plain loops and ignores meet. */
+int gca_helicopter_step(int empty, int tree, int fire, int max_freeze, uint64_t seed, int env_offset,
+                        const int32_t* action, uint64_t action_seed, int32_t* action_out, const double* thresholds,
+                        int32_t* freeze, uint32_t* rng_step, uint8_t* parity, uint8_t* buf0, uint8_t* buf1, int H,
+                        int W, int32_t* pos, int32_t* counts, uint8_t* hit, double* reward, int64_t* steps_elapsed,
+                        uint64_t* meet, int E, void* stream);
+
 /* ------------------------------------------ measurement yardsticks (bench.py; no reference counterpart)
  * gca_bench_copy: a 16-B device copy of nbytes (one element per thread, one pass) (a multiple of 16, 16-B aligned), nt != 0 non-temporal
  * loads and stores: the practical HBM ceiling the bench reports beside the 8 TB/s spec.
