@@ -13,6 +13,7 @@
 //   gca_move_modify   move_modify.py:37-134                (gca_env.hip move_modify_kernel)
 //   gca_ds_count_draws / gca_ds_step  ca_DrosselSchwabl.py:32-66 (gca_ds.hip), exact-stream and Philox modes
 //   gca_helicopter_step  helicopter.py:220-236 + ca_env.py:27-48 (gca_heli.hip), the batched env step's twin
+//   gca_bulldozer_reset_where  bulldozer.py:221-275 + ca_env.py:64-81 (gca_reset.hip), the per-env reset's twin
 //   gca_philox        Random123 Philox4x32-10 (KAT hook)
 #include <stdarg.h>
 #include <stdint.h>
@@ -299,6 +300,82 @@ extern "C" int gca_helicopter_step(int empty, int tree, int fire, int max_freeze
         reward[e] = qt - qf;  // helicopter.py:120-135 (built with -ffp-contract=off)
         rng_step[e] = rs + 1u;
         steps_elapsed[e] += 1;
+    }
+    return GCA_OK;
+}
+
+// _seeding._splitmix64 / env_integers restated: an integer in [0, span) per (seed, global env id, tag).
+static inline uint64_t splitmix64(uint64_t x) {
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+static inline int32_t env_integer(uint64_t seed, uint64_t env_id, uint32_t tag, uint32_t span) {
+    const uint64_t r = splitmix64(splitmix64(seed ^ (uint64_t)tag) ^ splitmix64(env_id));
+    return (int32_t)(((r >> 32) * (uint64_t)span) >> 32);
+}
+
+// The per-env reset of the batched ForestFireBulldozer env (gca_reset.hip) in plain loops: bulldozer.py:221-275 +
+// ca_env.py:64-81. buf1 is checked and left as it is.
+extern "C" int gca_bulldozer_reset_where(const gca_bulldozer_params* p, uint64_t reset_seed, const uint8_t* mask,
+                                         int64_t max_steps, int64_t set_episode, const float* cdf,
+                                         const uint8_t* values, uint8_t* done, uint8_t* terminated_out,
+                                         uint8_t* truncated_out, uint32_t* episode, int64_t* last_length_out,
+                                         double* accu, uint8_t* parity, uint8_t* buf0, uint8_t* buf1, int H, int W,
+                                         int32_t* pos, int32_t* counts, uint8_t* hit, int64_t* steps_elapsed, int E,
+                                         void*) {
+    CPU_CHECK_ARG(p && cdf && values && done && episode && accu && parity && buf0 && buf1 && pos && counts && hit &&
+                      steps_elapsed,
+                  "bulldozer_reset_where: null argument");
+    CPU_CHECK_ARG(E > 0 && H > 0 && W > 0, "bulldozer_reset_where: E, H, W must be positive");
+    CPU_CHECK_ARG(H < 32768 && W < 32768, "bulldozer_reset_where: H, W < 32768");
+    CPU_CHECK_ARG(buf0 != buf1, "bulldozer_reset_where: buf0 and buf1 must differ");
+    CPU_CHECK_ARG(max_steps >= 0 && set_episode >= -1 && set_episode <= 0xFFFFFFFFll,
+                  "bulldozer_reset_where: max_steps >= 0 and set_episode in [-1, 2^32)");
+    CPU_CHECK_ARG(p->env_offset >= 0, "bulldozer_reset_where: env_offset >= 0");
+    const int64_t HW = (int64_t)H * W;
+    const uint32_t k0 = (uint32_t)reset_seed, k1 = (uint32_t)(reset_seed >> 32);
+    const uint32_t span_h = (uint32_t)(H / 12 > 1 ? H / 12 : 1), span_w = (uint32_t)(W / 12 > 1 ? W / 12 : 1);
+    for (int e = 0; e < E; ++e) {
+        const bool was_done = done[e] != 0;
+        const int64_t se = steps_elapsed[e];
+        const bool by_limit = max_steps > 0 && se >= max_steps;
+        const bool selected = (mask ? mask[e] != 0 : was_done) || by_limit;
+        if (terminated_out) terminated_out[e] = was_done ? 1 : 0;
+        if (truncated_out) truncated_out[e] = (by_limit && !was_done) ? 1 : 0;
+        if (!selected) continue;
+        const uint32_t k = set_episode >= 0 ? (uint32_t)set_episode : episode[e] + 1u;
+        const uint64_t env_id = (uint64_t)(p->env_offset + e);
+        const uint32_t ktag = (k & 0xFFFFFFu) << 8;
+        uint8_t* g = buf0 + e * HW;
+        for (int64_t i = 0; i < HW; ++i) {
+            const u32x4 x = philox4x32_10(u32x4{(uint32_t)(i >> 2), (uint32_t)env_id, k, GCA_TAG_INIT}, k0, k1);
+            const uint32_t xs[4] = {x.x, x.y, x.z, x.w};
+            const float u = (float)(xs[i & 3] >> 8) * 0x1.0p-24f;
+            g[i] = u < cdf[0] ? values[0] : (u < cdf[1] ? values[1] : values[2]);
+        }
+        const int fr = 3 * H / 4 + env_integer(reset_seed, env_id, 1u | ktag, span_h);
+        const int fc = W / 4 + env_integer(reset_seed, env_id, 2u | ktag, span_w);
+        g[(int64_t)fr * W + fc] = (uint8_t)p->fire;
+        int32_t cE = 0, cT = 0, cF = 0;
+        for (int64_t i = 0; i < HW; ++i) {
+            cE += g[i] == (uint8_t)p->empty;
+            cT += g[i] == (uint8_t)p->tree;
+            cF += g[i] == (uint8_t)p->fire;
+        }
+        counts[3 * e] = cE;
+        counts[3 * e + 1] = cT;
+        counts[3 * e + 2] = cF;
+        pos[2 * e] = H / 4 + env_integer(reset_seed, env_id, 3u | ktag, span_h);
+        pos[2 * e + 1] = 3 * W / 4 + env_integer(reset_seed, env_id, 4u | ktag, span_w);
+        if (last_length_out) last_length_out[e] = se;
+        episode[e] = k;
+        parity[e] = 0;
+        accu[e] = 0.0;
+        done[e] = 0;
+        hit[e] = 0;
+        steps_elapsed[e] = 0;
     }
     return GCA_OK;
 }

@@ -188,6 +188,8 @@ _SIGNATURES = {
                                          c_int, P, P, P, P, P, P, c_int, P], c_int),
     "gca_bulldozer_rollout_random": ([POINTER(BulldozerParams), c_uint64, c_int, P, P, P, P, P, P, P, c_int64, P, P, P,
                                       P, c_int, c_int, P, P, P, P, P, c_int, P], c_int),
+    "gca_bulldozer_reset_where": ([POINTER(BulldozerParams), c_uint64, P, c_int64, c_int64, P, P, P, P, P, P, P, P, P,
+                                   P, P, c_int, c_int, P, P, P, P, c_int, P], c_int),
     "gca_move_modify": ([POINTER(BulldozerParams), P, P, P, c_int, c_int, P, c_int, P], c_int),
     "gca_alex_prepare_slope": ([P, P, c_int, c_int, c_int, P], c_int),
     "gca_alex_step": ([POINTER(AlexParams), c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P],
@@ -233,7 +235,7 @@ _SIGNATURES = {
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 # the subset libgca_cpu.so exports (tiny grids and the O(1)-per-env operators on host arrays)
 CPU_SYMBOLS = ("gca_last_error", "gca_version", "gca_philox", "gca_count_cells", "gca_move_modify",
-               "gca_ds_count_draws", "gca_ds_step", "gca_helicopter_step")
+               "gca_ds_count_draws", "gca_ds_step", "gca_helicopter_step", "gca_bulldozer_reset_where")
 
 _lib = None
 _lib_cpu = None

@@ -30,3 +30,11 @@ def env_integers(seed, env_offset, count, tag, low, high):
         return np.full(int(count), int(low), dtype=np.int64)
     top = env_draws(seed, ids, tag) >> np.uint64(32)
     return int(low) + ((top * np.uint64(span)) >> np.uint64(32)).astype(np.int64)
+
+
+def env_integers_episode(seed, env_offset, count, tag, low, high, episode):
+    """env_integers for episode `episode` of each env: the draw's tag is tag | ((episode & 0xFFFFFF) << 8) (tag < 256),
+    so episode 0 is env_integers itself. The rule gca_bulldozer_reset_where restates on the device."""
+    if not 0 <= int(tag) < 256:
+        raise ValueError("env_integers_episode: tag in [0, 256)")
+    return env_integers(seed, env_offset, count, int(tag) | ((int(episode) & 0xFFFFFF) << 8), low, high)

@@ -14,6 +14,11 @@ bench configs 2 and 5), the same step in ONE launch (gca_bulldozer_step_fused: a
 step this env step leave after their O(1) work). `fused=None` picks it whenever it applies; the two paths are
 checked to give identical envs (tests/test_gpu_windy.py).
 
+Episodes: `reset()` starts episode 0 of every env; `reset_where()` (gca_bulldozer_reset_where, one launch, no host work)
+starts a new episode of the selected envs only, and `autoreset=True` launches it right after every step for the envs
+that finished (or reached `max_episode_steps`): Gymnasium's same-step autoreset, the reference's stateless_step ->
+conditional_reset pair. With both options off nothing of this runs.
+
 Grids live in two buffers; env e's current grid is buf[parity[e]][e], so envs whose
 RepeatCA yields 0 repeats this step (most of them: ~1 CA step per 13 env steps at
 256^2 with random actions) move no bytes at all. Cell counts are
@@ -32,7 +37,8 @@ from .bulldozer import ACTION_SETS, DEFAULT_WIND, bulldozer_timings, parse_wind
 # state the pre-bound calls hold by address (step, step_random, sample_actions): assigning one of these attributes
 # validates the replacement and drops the bound calls (rebind), so the next step binds the new tensor
 _BOUND_STATE = frozenset({"buf", "parity", "accu", "steps", "dir_mask", "counts", "pos", "rng_step", "done", "hit",
-                          "reward", "wind", "steps_elapsed", "params", "_meet", "_act_buf"})
+                          "reward", "wind", "steps_elapsed", "params", "_meet", "_act_buf", "episode",
+                          "last_episode_length", "_terminated", "_truncated_u8"})
 
 
 class BatchedForestFireBulldozerEnv:
@@ -56,8 +62,13 @@ class BatchedForestFireBulldozerEnv:
 
     def __init__(self, num_envs, nrows, ncols, device=None, seed=0, env_offset=0, speed_move=0.12, speed_act=0.03,
                  t_move=None, t_shoot=None, t_any=0.001, p_tree=0.90, p_empty=0.10, wind=DEFAULT_WIND,
-                 materialize_obs=True, fused=None):
+                 materialize_obs=True, fused=None, autoreset=False, max_episode_steps=None):
         import torch
+
+        if max_episode_steps is not None and int(max_episode_steps) <= 0:
+            raise ValueError("max_episode_steps must be positive (or None: no time limit)")
+        self.autoreset = bool(autoreset)
+        self.max_episode_steps = None if max_episode_steps is None else int(max_episode_steps)
 
         self.device = dev.require_device(device)
         self.num_envs, self.nrows, self.ncols = E, H, W = int(num_envs), int(nrows), int(ncols)
@@ -105,17 +116,25 @@ class BatchedForestFireBulldozerEnv:
         # the fused step's per-env meeting slots (gca_bulldozer_step_fused: several workgroups per env), kept zero
         self._meet = torch.zeros(E, dtype=torch.int64, **kw)
         self._truncated = torch.zeros(E, dtype=torch.bool, **kw)
+        # per-env episodes (reset_where / autoreset): the episode index keys the reset's draws; the two flag tensors are
+        # what the reset launch saw on entry (done, and the time limit reached without done)
+        self.episode = torch.zeros(E, dtype=torch.int32, **kw)  # uint32 bits
+        self.last_episode_length = torch.zeros(E, dtype=torch.int64, **kw)
+        self._terminated = torch.zeros(E, dtype=torch.uint8, **kw)
+        self._truncated_u8 = torch.zeros(E, dtype=torch.uint8, **kw)
+        self._reset_seed = self.seed_value
+        self._reset_cdf = torch.tensor([p_empty, p_empty + p_tree, 1.0], dtype=torch.float32, device=self.device)
+        self._reset_vals = torch.tensor([self._empty, self._tree, self._fire], dtype=torch.uint8, device=self.device)
         # the eager step's host path: persistent outputs and pre-bound C-ABI calls, so a step is
         # one action check, one raw-stream read and one prepared ctypes call
         self._dev_index = dev.device_index(self.device)
         self._act_buf = torch.zeros((E, 2), dtype=torch.int32, **kw)
         self._act_shape = self._act_buf.shape
-        self._done_bool = self.done.view(torch.bool)
-        self._info = {"hit": self.hit, "ca_steps": self.steps}
-        self._ctx = {"wind": self.wind, "position": self.pos, "time": self.accu}
+        self._views()
         self._fused_call = self._bound_meet = None
         self._sample_call = None
         self._random_call = self._bound_meet_r = None
+        self._reset_call = None
 
     # ------------------------------------------------------------------ state
     def grids(self):
@@ -164,6 +183,8 @@ class BatchedForestFireBulldozerEnv:
         self.hit.zero_()
         self.rng_step.zero_()
         self.steps_elapsed.zero_()
+        self.episode.zero_()
+        self._reset_seed = s  # reset_where draws the later episodes from the same seed
         call("gca_count_cells", dev.ptr(self.buf[0]), E, H, W, self._empty, self._tree, self._fire,
              dev.ptr(self.counts), st)
         return self._obs(), {"hit": self.hit}
@@ -190,14 +211,83 @@ class BatchedForestFireBulldozerEnv:
         updates them in place. Assigning a new tensor to one of them (env.wind = w) calls this by itself
         (__setattr__, which also checks the replacement's dtype / shape / device); the bound calls hold references to
         what they bound, so nothing they address is ever freed under them."""
-        import torch
-
         self._fused_call = self._bound_meet = None
         self._sample_call = None
         self._random_call = self._bound_meet_r = None
+        self._reset_call = None
+        self._views()
+
+    def _views(self):
+        """The persistent objects a step returns: bool views of the flag tensors and the info / context dicts."""
+        import torch
+
         self._done_bool = self.done.view(torch.bool)
         self._info = {"hit": self.hit, "ca_steps": self.steps}
         self._ctx = {"wind": self.wind, "position": self.pos, "time": self.accu}
+        if self.autoreset:
+            self._info.update(episode=self.episode, last_episode_length=self.last_episode_length)
+        self._term_bool = self._terminated.view(torch.bool)
+        self._trunc_bool = self._truncated_u8.view(torch.bool)
+
+    # ------------------------------------------------------------------ per-env reset
+    def _launch_reset(self, mask_ptr, max_steps, set_episode):
+        rc = self._reset_call
+        if rc is None:
+            E, H, W = self.num_envs, self.nrows, self.ncols
+            rc = self._reset_call = BoundCall(
+                "gca_bulldozer_reset_where", self.params, SLOT, SLOT, SLOT, SLOT, dev.ptr(self._reset_cdf),
+                dev.ptr(self._reset_vals), dev.ptr(self.done), dev.ptr(self._terminated), dev.ptr(self._truncated_u8),
+                dev.ptr(self.episode), dev.ptr(self.last_episode_length), dev.ptr(self.accu), dev.ptr(self.parity),
+                dev.ptr(self.buf[0]), dev.ptr(self.buf[1]), H, W, dev.ptr(self.pos), dev.ptr(self.counts),
+                dev.ptr(self.hit), dev.ptr(self.steps_elapsed), E, SLOT,
+                keep=self._bound_tensors() + (self._reset_cdf, self._reset_vals, self._terminated, self._truncated_u8,
+                                              self.episode, self.last_episode_length))
+        rc(self._reset_seed & (2**64 - 1), mask_ptr, max_steps, set_episode, dev.raw_stream(self._dev_index))
+
+    def _autoreset(self):
+        """The reset launch that follows a step under autoreset=True: the envs that are done, or at their time limit,
+        start their next episode; the step's return values are the terminal step's reward, the flags the launch saw
+        and the new episode's observation."""
+        self._launch_reset(None, self.max_episode_steps or 0, -1)
+        return self._obs(), self.reward, self._term_bool, self._trunc_bool, self._info
+
+    def reset_where(self, mask=None, episode=None):
+        """Start a new episode of the selected envs in one launch on the device (gca_bulldozer_reset_where); every
+        other env is left untouched, bit for bit. mask: a uint8 / bool (E,) device tensor or numpy array, non-zero =
+        reset; None selects the envs that are done and, with max_episode_steps, those at their time limit. episode:
+        None moves each selected env to its next episode index; an int replays that index (0 = the state reset() gave
+        with the same seed). The grid, the fire cell and the bulldozer's position are keyed by (the last reset()'s
+        seed, global env id, episode index), so a sharded env resets like the unsharded one; rng_step runs on, so the
+        new episode's Windy rolls and sampled actions do not replay the last episode's. Returns (obs, info)."""
+        import torch
+
+        E = self.num_envs
+        if mask is None:
+            mask_ptr, max_steps = None, self.max_episode_steps or 0
+        else:
+            if isinstance(mask, torch.Tensor):
+                if mask.device != self.done.device:
+                    raise ValueError(f"reset_where: mask must be on {self.done.device} (or a numpy array)")
+                m = mask
+            else:
+                m = np.asarray(mask)
+            if str(m.dtype).replace("torch.", "") not in ("uint8", "bool") or tuple(m.shape) != (E,):
+                raise ValueError(f"reset_where: mask must be a uint8 or bool array of shape ({E},)")
+            if not isinstance(m, torch.Tensor):
+                m = dev.to_device(m.astype(np.uint8), torch.uint8, self.device)
+            m = m.contiguous()
+            m = m.view(torch.uint8) if m.dtype is torch.bool else m
+            mask_ptr, max_steps = m.data_ptr(), 0
+        if episode is None:
+            set_episode = -1
+        else:
+            set_episode = int(episode)
+            if set_episode != episode or not 0 <= set_episode < 2**32:
+                raise ValueError("reset_where: episode must be an int in [0, 2**32) (or None: the next episode)")
+        # `m` stays alive until the launch is enqueued; its memory is reused in stream order only
+        self._launch_reset(mask_ptr, max_steps, set_episode)
+        return self._obs(), {"hit": self.hit, "episode": self.episode,
+                             "last_episode_length": self.last_episode_length}
 
     def _bound_tensors(self):
         return (self.params, self.accu, self.steps, self.done, self.wind, self.rng_step, self.parity, self.buf,
@@ -242,6 +332,8 @@ class BatchedForestFireBulldozerEnv:
                 keep=self._bound_tensors() + (out,)))
             self._bound_meet_r = meet
         self._random_call[2](dev.raw_stream(self._dev_index))
+        if self.autoreset:
+            return self._autoreset()
         return self._obs(), self.reward, self._done_bool, self._truncated, self._info
 
     def rollout_random(self, K, seed=9, action_out=None, reward_out=None, done_out=None):
@@ -253,6 +345,8 @@ class BatchedForestFireBulldozerEnv:
 
         if not self.fused:
             raise ValueError("rollout_random needs the fused step (W in (256, 512), at most one CA pass per env step)")
+        if self.autoreset or self.max_episode_steps is not None:
+            raise ValueError("rollout_random runs no per-env reset: not available with autoreset or max_episode_steps")
         K, E = int(K), self.num_envs
         if K < 0:
             raise ValueError("rollout_random: K >= 0")
@@ -293,13 +387,18 @@ class BatchedForestFireBulldozerEnv:
         """action: (E, 2) int (move in [0,9), shoot in {0,1}); device tensor or numpy. Returns (obs, reward,
         terminated, truncated, info) as device tensors that the next step overwrites in place (terminated is a bool
         view of `done`, truncated a persistent all-False tensor, info one persistent dict: no kernel launch and no
-        allocation per step); clone to keep them. A contiguous int32 (E, 2) device action is used as it is."""
+        allocation per step); clone to keep them. A contiguous int32 (E, 2) device action is used as it is.
+        autoreset=True: one more launch resets the envs this step finished (or that reached max_episode_steps): reward
+        is the terminal step's, terminated / truncated are bool views of what that launch saw, the observation is
+        already the new episode's, and info carries `episode` and `last_episode_length` (persistent tensors)."""
         a = self._action(action)
         if self.fused:
             fc = self._fused_call if self._bound_meet is self._meet else None
             if fc is None:
                 fc = self._bind_fused()
             fc(a.data_ptr(), dev.raw_stream(self._dev_index))
+            if self.autoreset:
+                return self._autoreset()
             # done is 0 / 1 bytes: a bool view, no kernel; truncated is a persistent all-False tensor
             return self._obs(), self.reward, self._done_bool, self._truncated, self._info
         import torch
@@ -322,6 +421,8 @@ class BatchedForestFireBulldozerEnv:
              dev.ptr(self.buf[0]), dev.ptr(self.buf[1]), H, W, dev.ptr(self.pos), dev.ptr(self.counts),
              dev.ptr(self.rng_step), dev.ptr(self.done), dev.ptr(self.hit), dev.ptr(self.reward), E, st)
         self.steps_elapsed += (self.steps >= 0).to(torch.int64)
+        if self.autoreset:
+            return self._autoreset()
         return self._obs(), self.reward, self._done_bool, self._truncated, self._info
 
     def ca_step_all(self, dir_mask=None):

@@ -152,6 +152,30 @@ int gca_bulldozer_rollout_random(const gca_bulldozer_params* p, uint64_t action_
                                  uint8_t* buf0, uint8_t* buf1, int H, int W, int32_t* pos, int32_t* counts, uint8_t* hit,
                                  double* reward, int64_t* steps_elapsed, int E, void* stream);
 
+/* Per-env reset of the batched ForestFireBulldozer env on the device, one launch, device pointers only (capturable):
+ * the initial distribution of bulldozer.py:221-275 and the fresh-episode state of ca_env.py:64-81 for the selected envs.
+ *   selected  (mask ? mask[e] != 0 : done[e] != 0) || (max_steps > 0 && steps_elapsed[e] >= max_steps)
+ *   flags     terminated_out[e] = done[e] on entry, truncated_out[e] = selected by the time limit and not done: both
+ *             nullable, written for EVERY env; last_length_out[e] (nullable) = steps_elapsed[e], selected envs only
+ *   episode   k = set_episode >= 0 ? (uint32)set_episode : episode[e] + 1, stored to episode[e]
+ *   grid      buf0[e]: flat cell i = values[first j with u < cdf[j]], u = u01_f32 of word i & 3 of Philox((i >> 2,
+ *             p->env_offset + e, k, GCA_TAG_INIT), reset_seed) -- gca_fill_categorical (n_values = 3) with counter
+ *             word 2 = k -- then p->fire at (3H/4 + n1, W/4 + n2); pos[e] = (H/4 + n3, 3W/4 + n4), where n_t is
+ *             _seeding.env_integers(reset_seed, global env id, tag = t | ((k & 0xFFFFFF) << 8), 0, max(1, N/12)):
+ *             episode 0 is BatchedForestFireBulldozerEnv.reset(seed = reset_seed)'s own state
+ *   counts    [e][3] p->empty / p->tree / p->fire cells of the new grid, summed in the same launch (no atomics)
+ *   state     parity, accu, done, hit, steps_elapsed = 0. rng_step is not a parameter: the Windy rolls and sampled
+ *             actions of the new episode continue the env's stream. buf1 and every byte of an unselected env are left
+ *             untouched.
+ * cdf [3] f32 and values [3] u8 are device arrays. H, W < 32768; any H*W (a partial last quad and unaligned env bases
+ * take byte stores). One workgroup per env; unselected envs leave after their per-env loads. */
+int gca_bulldozer_reset_where(const gca_bulldozer_params* p, uint64_t reset_seed, const uint8_t* mask,
+                              int64_t max_steps, int64_t set_episode, const float* cdf, const uint8_t* values,
+                              uint8_t* done, uint8_t* terminated_out, uint8_t* truncated_out, uint32_t* episode,
+                              int64_t* last_length_out, double* accu, uint8_t* parity, uint8_t* buf0, uint8_t* buf1,
+                              int H, int W, int32_t* pos, int32_t* counts, uint8_t* hit, int64_t* steps_elapsed, int E,
+                              void* stream);
+
 /* Move then Modify for E envs (move_modify.py:37-134): action[e] = (move, shoot);
  * uses p->up/down/left/right_mask and p->effect; grid may be NULL (Move only); hit nullable. */
 int gca_move_modify(const gca_bulldozer_params* p, const int32_t* action, int32_t* pos, uint8_t* grid, int H, int W,
