@@ -13,6 +13,7 @@
 //   gca_move_modify   move_modify.py:37-134                (gca_env.hip move_modify_kernel)
 //   gca_ds_count_draws / gca_ds_step  ca_DrosselSchwabl.py:32-66 (gca_ds.hip), exact-stream and Philox modes
 //   gca_helicopter_step  helicopter.py:220-236 + ca_env.py:27-48 (gca_heli.hip), the batched env step's twin
+//   gca_helicopter_rollout  K of those steps with per-step records (gca_heli.hip), the resident rollout's twin
 //   gca_bulldozer_reset_where  bulldozer.py:221-275 + ca_env.py:64-81 (gca_reset.hip), the per-env reset's twin
 //   gca_philox        Random123 Philox4x32-10 (KAT hook)
 #include <stdarg.h>
@@ -215,21 +216,25 @@ extern "C" int gca_ds_step(const uint8_t* grid_in, uint8_t* grid_out, int E, int
     return GCA_OK;
 }
 
-// The batched ForestFireHelicopter env step (gca_heli.hip) in plain loops: helicopter.py:220-236 + ca_env.py:27-48.
-// `meet` is not used (nothing runs in parts here) and is left as it is.
-extern "C" int gca_helicopter_step(int empty, int tree, int fire, int max_freeze, uint64_t seed, int env_offset,
-                                   const int32_t* action, uint64_t action_seed, int32_t* action_out,
-                                   const double* thresholds, int32_t* freeze, uint32_t* rng_step, uint8_t* parity,
-                                   uint8_t* buf0, uint8_t* buf1, int H, int W, int32_t* pos, int32_t* counts,
-                                   uint8_t* hit, double* reward, int64_t* steps_elapsed, uint64_t*, int E, void*) {
-    CPU_CHECK_ARG(thresholds && freeze && rng_step && parity && buf0 && buf1 && pos && counts && hit && reward &&
-                      steps_elapsed,
-                  "helicopter_step: null argument");
-    CPU_CHECK_ARG(E > 0 && H > 0 && W > 0 && max_freeze >= 0, "helicopter_step: E, H, W > 0 and max_freeze >= 0");
-    CPU_CHECK_ARG(buf0 != buf1, "helicopter_step: buf0 and buf1 must differ");
-    CPU_CHECK_ARG((int64_t)H * W < (1 << 30), "helicopter_step: grid too large");
-    CPU_CHECK_ARG(((empty | tree | fire) & ~0xFF) == 0 && empty != tree && tree != fire && empty != fire,
-                  "helicopter_step: three distinct u8 codes");
+// The argument checks shared by gca_helicopter_step and gca_helicopter_rollout (`who` names the entry point).
+#define CPU_CHECK_HELI_ARGS(who)                                                                                       \
+    CPU_CHECK_ARG(thresholds && freeze && rng_step && parity && buf0 && buf1 && pos && counts && hit && reward &&      \
+                      steps_elapsed,                                                                                   \
+                  who ": null argument");                                                                              \
+    CPU_CHECK_ARG(E > 0 && H > 0 && W > 0 && max_freeze >= 0, who ": E, H, W > 0 and max_freeze >= 0");                \
+    CPU_CHECK_ARG(buf0 != buf1, who ": buf0 and buf1 must differ");                                                    \
+    CPU_CHECK_ARG((int64_t)H * W < (1 << 30), who ": grid too large");                                                 \
+    CPU_CHECK_ARG(((empty | tree | fire) & ~0xFF) == 0 && empty != tree && tree != fire && empty != fire,              \
+                  who ": three distinct u8 codes")
+
+// One batched ForestFireHelicopter env step of every env (gca_heli.hip) in plain loops: helicopter.py:220-236 +
+// ca_env.py:27-48. rec_reward / rec_hit (nullable): gca_helicopter_rollout's record rows of this step.
+static void helicopter_step_host(int empty, int tree, int fire, int max_freeze, uint64_t seed, int env_offset,
+                                 const int32_t* action, uint64_t action_seed, int32_t* action_out,
+                                 const double* thresholds, int32_t* freeze, uint32_t* rng_step, uint8_t* parity,
+                                 uint8_t* buf0, uint8_t* buf1, int H, int W, int32_t* pos, int32_t* counts,
+                                 uint8_t* hit, double* reward, int64_t* steps_elapsed, int E, double* rec_reward,
+                                 uint8_t* rec_hit) {
     const int64_t HW = (int64_t)H * W;
     const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
     gca_bulldozer_params mv = {};  // the helicopter's action sets (helicopter.py:56-62); only the masks are read
@@ -298,8 +303,42 @@ extern "C" int gca_helicopter_step(int empty, int tree, int fire, int max_freeze
         const double n = (double)HW;
         const double qt = (double)counts[3 * e + 1] / n, qf = (double)counts[3 * e + 2] / n;
         reward[e] = qt - qf;  // helicopter.py:120-135 (built with -ffp-contract=off)
+        if (rec_reward) rec_reward[e] = reward[e];
+        if (rec_hit) rec_hit[e] = h;
         rng_step[e] = rs + 1u;
         steps_elapsed[e] += 1;
+    }
+}
+
+// The batched ForestFireHelicopter env step (gca_heli.hip): `meet` is not used (nothing runs in parts here) and is
+// left as it is.
+extern "C" int gca_helicopter_step(int empty, int tree, int fire, int max_freeze, uint64_t seed, int env_offset,
+                                   const int32_t* action, uint64_t action_seed, int32_t* action_out,
+                                   const double* thresholds, int32_t* freeze, uint32_t* rng_step, uint8_t* parity,
+                                   uint8_t* buf0, uint8_t* buf1, int H, int W, int32_t* pos, int32_t* counts,
+                                   uint8_t* hit, double* reward, int64_t* steps_elapsed, uint64_t*, int E, void*) {
+    CPU_CHECK_HELI_ARGS("helicopter_step");
+    helicopter_step_host(empty, tree, fire, max_freeze, seed, env_offset, action, action_seed, action_out, thresholds,
+                         freeze, rng_step, parity, buf0, buf1, H, W, pos, counts, hit, reward, steps_elapsed, E,
+                         nullptr, nullptr);
+    return GCA_OK;
+}
+
+// K env steps (gca_heli.hip's resident rollout) in plain loops: K times the step above, plus the records.
+extern "C" int gca_helicopter_rollout(int empty, int tree, int fire, int max_freeze, uint64_t seed, int env_offset,
+                                      const int32_t* actions, uint64_t action_seed, int K, int32_t* action_out,
+                                      double* reward_out, uint8_t* hit_out, const double* thresholds, int32_t* freeze,
+                                      uint32_t* rng_step, uint8_t* parity, uint8_t* buf0, uint8_t* buf1, int H, int W,
+                                      int32_t* pos, int32_t* counts, uint8_t* hit, double* reward,
+                                      int64_t* steps_elapsed, int E, void*) {
+    CPU_CHECK_HELI_ARGS("helicopter_rollout");
+    CPU_CHECK_ARG(K >= 0, "helicopter_rollout: K >= 0");
+    for (int k = 0; k < K; ++k) {
+        const size_t o = (size_t)k * (size_t)E;
+        helicopter_step_host(empty, tree, fire, max_freeze, seed, env_offset, actions ? actions + o : nullptr,
+                             action_seed, action_out ? action_out + o : nullptr, thresholds, freeze, rng_step, parity,
+                             buf0, buf1, H, W, pos, counts, hit, reward, steps_elapsed, E,
+                             reward_out ? reward_out + o : nullptr, hit_out ? hit_out + o : nullptr);
     }
     return GCA_OK;
 }

@@ -17,6 +17,11 @@
 // The parts meet like bulldozer_step_fused_parts_kernel: one 64-bit atomic per env carries the part's E | T | F counts
 // (20 bits each), the hit bit and an arrival count in the top 3 bits; the last to arrive writes every per-env output
 // and leaves the slot zero. Nothing waits for anything: a part adds its word and leaves.
+//
+// gca_helicopter_rollout: K of those steps with the caller's (K, E) actions (or the random policy) in ONE launch,
+// helicopter_rollout_kernel: a workgroup per env keeps both grid planes in LDS (4-byte pitch, EMPTY padding) and the
+// env's scalars in registers for the K steps, the CA pass in the strip's SWAR form on LDS dwords for any W; one barrier
+// per step, no atomics, no `meet`. Grids whose planes do not fit in 64 KiB run K launches of the step kernel instead.
 #include "gca_common.h"
 
 namespace {
@@ -198,6 +203,8 @@ struct HeliArgs {
     int64_t* steps_elapsed;
     unsigned long long* meet;
     int P;
+    double* rec_reward;  // gca_helicopter_rollout's records of this step (nullable; action_out is the third)
+    uint8_t* rec_hit;
 };
 
 // FAST: W % 256 == 0 and 4-byte aligned grids. Block = (env, part), 4 waves. Every wave of every block reaches the one
@@ -328,9 +335,300 @@ __global__ __launch_bounds__(HELI_THREADS) void helicopter_step_kernel(HeliArgs 
     a.hit[e] = hh;
     // helicopter.py:120-135: dot([0, 1, -1], counts / ncells) = cT / n - cF / n (0 * x and the first add are exact)
     const double n = (double)HW;
-    a.reward[e] = __dsub_rn(__ddiv_rn((double)nT, n), __ddiv_rn((double)nF, n));
+    const double rw = __dsub_rn(__ddiv_rn((double)nT, n), __ddiv_rn((double)nF, n));
+    a.reward[e] = rw;
+    if (a.rec_reward) a.rec_reward[e] = rw;
+    if (a.rec_hit) a.rec_hit[e] = hh;
     a.rng_step[e] = rs + 1u;
     a.steps_elapsed[e] = se + 1;
+}
+
+// ---------------------------------------------------------------- K env steps in one launch, the grid resident in LDS
+struct HeliRollArgs {
+    int empty, tree, fire, max_freeze;
+    uint64_t seed, action_seed;
+    int env_offset, K, E;
+    const int32_t* actions;  // (K, E) or null
+    int32_t* action_out;     // (K, E) records, each nullable
+    double* reward_out;
+    uint8_t* hit_out;
+    const double* thr;
+    int32_t* freeze;
+    uint32_t* rng_step;
+    uint8_t* parity;
+    uint8_t* buf0;
+    uint8_t* buf1;
+    int H, W;
+    int D;            // dwords per row, ceil(W / 4)
+    int plane_words;  // dwords per LDS plane, a multiple of 4
+    int dwords;       // W % 4 == 0 and 4-byte aligned grids: dword loads / stores of the planes, else bytes
+    int32_t* pos;
+    int32_t* counts;
+    uint8_t* hit;
+    double* reward;
+    int64_t* steps_elapsed;
+};
+
+// the cells of row r, dword d (columns 4d .. 4d+3) of an env's grid in global memory; columns >= W read as EMPTY
+__device__ __forceinline__ uint32_t heli_g2r(const uint8_t* __restrict__ g, int r, int d, int W, bool dwords,
+                                             uint32_t Ep) {
+    const uint32_t cell0 = (uint32_t)r * (uint32_t)W + 4u * (uint32_t)d;
+    if (dwords) return *reinterpret_cast<const uint32_t*>(g + cell0);
+    uint32_t v = 0u;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v |= (4 * d + j < W ? (uint32_t)g[cell0 + j] : (Ep & 0xFFu)) << (8 * j);
+    return v;
+}
+__device__ __forceinline__ void heli_r2g(uint8_t* __restrict__ g, int r, int d, int W, bool dwords, uint32_t v) {
+    const uint32_t cell0 = (uint32_t)r * (uint32_t)W + 4u * (uint32_t)d;
+    if (dwords) {
+        *reinterpret_cast<uint32_t*>(g + cell0) = v;
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (4 * d + j < W) g[cell0 + j] = (uint8_t)(v >> (8 * j));
+}
+
+// One workgroup (4 waves) per env, K steps. LDS: two planes of PD = D + 1 dwords per row, rows -1 .. H, one leading
+// dword; cell (r, c) is byte c of dword 1 + (r + 1) * PD of its plane, and the dword after a row's D, rows -1 and H
+// and the columns >= W of a row's last dword hold EMPTY for the whole launch (never FIRE, never stored to), so every
+// neighbour outside the grid reads as not-FIRE with no bounds test. LDS plane p mirrors buf[p] of the env.
+// Every thread carries the env's scalars. freeze, position, rng_step and the plane index follow from uniform loads and
+// the actions alone, so they are the same in all 256 threads in every step; that makes `do_ca` uniform. The counts and
+// the hit are exact in wave 0, which writes the records and the exit state: after a CA pass every thread reads the
+// waves' words back, on a countdown step only thread 0 knows the hit and wave 0 takes it by readfirstlane.
+// The K loop, the item loop inside a CA pass and the one barrier per step have the same trip count in every thread
+// (K, `iters`, K): the barrier stands outside every condition, no thread leaves early, nothing waits for another
+// workgroup.
+__global__ __launch_bounds__(HELI_THREADS) void helicopter_rollout_kernel(HeliRollArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t heli_lds[];
+    const int e = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int H = a.H, W = a.W, D = a.D, PD = D + 1, NP = a.plane_words, K = a.K;
+    const int64_t HW = (int64_t)H * W;
+    const bool dwords = a.dwords != 0;
+    uint32_t* const wave_cnt = heli_lds + 2 * NP;  // [step & 1][wave][2]
+    uint32_t rs = a.rng_step[e];
+    const uint32_t env_id = (uint32_t)(a.env_offset + e);
+    int32_t fz = a.freeze[e];
+    int p = a.parity[e] != 0;
+    int row = a.pos[2 * e], col = a.pos[2 * e + 1];
+    int32_t c0 = a.counts[3 * e + 0], c1 = a.counts[3 * e + 1], c2 = a.counts[3 * e + 2];
+    HeliCtx c;
+    c.Ep = rep4((uint32_t)a.empty);
+    c.Tp = rep4((uint32_t)a.tree);
+    c.Fp = rep4((uint32_t)a.fire);
+    c.k0 = (uint32_t)a.seed;
+    c.k1 = (uint32_t)(a.seed >> 32);
+    c.env_id = env_id;
+    c.it_fire = heli_int_threshold(a.thr[2 * e]);
+    c.it_tree = heli_int_threshold(a.thr[2 * e + 1]);
+    const uint32_t fire = (uint32_t)a.fire;
+    // ---- entry: the current plane from buf[p][e], everything else of both planes EMPTY
+    {
+        const uint8_t* g = (p ? a.buf1 : a.buf0) + e * HW;
+        uint32_t* cur = heli_lds + p * NP;
+        uint32_t* oth = heli_lds + (p ^ 1) * NP;
+        for (int idx = tid; idx < NP; idx += HELI_THREADS) {
+            const int t = idx - 1, rr = t / PD, d = t - rr * PD, r = rr - 1;
+            uint32_t v = c.Ep;
+            if (idx >= 1 && r >= 0 && r < H && d < D) v = heli_g2r(g, r, d, W, dwords, c.Ep);
+            cur[idx] = v;
+            oth[idx] = c.Ep;
+        }
+    }
+    __syncthreads();
+    // a thread's items of a CA pass: (row, dword) number tid + 256 * it, it < iters, walked without a division
+    const int iters = (H * D + HELI_THREADS - 1) / HELI_THREADS;
+    const int r_first = tid / D, d_first = tid - r_first * D;
+    const int r_step = HELI_THREADS / D, d_step = HELI_THREADS - r_step * D;
+    const uint32_t tail = 0x01010101u >> (8 * (4 * D - W));  // the last dword's columns < W
+    int nca = 0;
+    uint32_t hh = 0u;
+    int32_t chunk = 0, rec_t = 0, rec_f = 0;
+    uint32_t rec_h = 0u;
+    for (int k = 0; k < K; ++k) {
+        int32_t act;
+        if (a.actions) {  // 64 steps' actions per load: lane l holds step (k & ~63) + l
+            if ((k & 63) == 0) chunk = k + lane < K ? a.actions[(size_t)(k + lane) * a.E + e] : 0;
+            act = __builtin_amdgcn_readlane(chunk, k & 63);
+        } else {  // column 0 of gca_random_actions
+            const u32x4 x = philox4x32_10(u32x4{0u, env_id, rs, GCA_TAG_ACTION}, (uint32_t)a.action_seed,
+                                          (uint32_t)(a.action_seed >> 32));
+            act = randint_ms(x.x, 0, 9);
+        }
+        move_pos(clampi_dev(act, 0, 8), row, col, H, W, 0x007, 0x1C0, 0x049, 0x124);
+        const bool do_ca = fz == 0;
+        uint32_t* S = heli_lds + p * NP;
+        uint32_t w0 = 0u, w1 = 0u;  // cE | cT << 16, cF | hit << 16 (the plane fits LDS: H * W < 2^15)
+        uint32_t patched = 0u;
+        if (do_ca) {
+            uint32_t* Dst = heli_lds + (p ^ 1) * NP;
+            const uint8_t* Sb = reinterpret_cast<const uint8_t*>(S);
+            c.step = rs;
+            c.prow = row;
+            c.pcol = col;
+            int r = r_first, d = d_first;
+            for (int it = 0; it < iters; ++it) {
+                const bool active = r < H;
+                const int idx = 1 + (r + 1) * PD + d;
+                uint32_t x = 0u, fB = 0u, em = 0u, ign = 0u, dT = 0u;
+                if (active) {
+                    x = S[idx];
+                    const int bl = 4 * idx - 1, br = 4 * idx + 4, pb = 4 * PD;
+                    const uint32_t lf = (Sb[bl - pb] == fire) | (Sb[bl] == fire) | (Sb[bl + pb] == fire);
+                    const uint32_t rf = (Sb[br - pb] == fire) | (Sb[br] == fire) | (Sb[br + pb] == fire);
+                    const uint32_t fx = bytes_eq01(x, c.Fp);
+                    const uint32_t V = bytes_eq01(S[idx - PD], c.Fp) | fx | bytes_eq01(S[idx + PD], c.Fp);
+                    const uint32_t nb = V | (V << 8) | lf | (V >> 8) | (rf << 24);  // a burning Moore neighbour
+                    const uint32_t vm = d == D - 1 ? tail : 0x01010101u;
+                    const uint32_t tr = bytes_eq01(x, c.Tp) & vm;
+                    em = bytes_eq01(x, c.Ep) & vm;
+                    fB = fx & vm;
+                    ign = tr & nb;   // TREE -> FIRE, no draw
+                    dT = tr ^ ign;   // TREE that draws
+                }
+                const uint32_t dr = dT | em;
+                const uint32_t cell0 = (uint32_t)r * (uint32_t)W + 4u * (uint32_t)d;
+                uint32_t win = 0u;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const bool dj = (dr >> (8 * j)) & 1u;
+                    if (__ballot(dj) != 0ull) {  // wave-uniform: no Philox call for a wave whose cells draw nothing
+                        const bool w = heli_draw(c, cell0 + j, (dT >> (8 * j)) & 1u);
+                        win |= (dj && w) ? (1u << (8 * j)) : 0u;
+                    }
+                }
+                if (active) {
+                    uint32_t nF = ign | (dT & win);
+                    const uint32_t nT = (dT & ~win) | (em & win);
+                    uint32_t nE = (em & ~win) | fB;
+                    // Modify folded into the store: the helicopter's cell, if it would be FIRE, is written EMPTY
+                    const uint32_t dc = (uint32_t)(col - 4 * d);
+                    const uint32_t mk = (r == row && dc < 4u) ? (1u << (8 * dc)) : 0u;
+                    const uint32_t hw = nF & mk;
+                    nF ^= hw;
+                    nE |= hw;
+                    const uint32_t known = nE | nT | nF;
+                    Dst[idx] = nE * (c.Ep & 0xFFu) + nT * (c.Tp & 0xFFu) + nF * (c.Fp & 0xFFu) +
+                               (x & ~(known * 0xFFu));
+                    w0 += (uint32_t)__popc(nE) + ((uint32_t)__popc(nT) << 16);
+                    w1 += (uint32_t)__popc(nF) + ((hw != 0u ? 1u : 0u) << 16);
+                }
+                d += d_step;
+                r += r_step;
+                if (d >= D) {
+                    d -= D;
+                    r += 1;
+                }
+            }
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                w0 += __shfl_xor(w0, off);
+                w1 += __shfl_xor(w1, off);
+            }
+            if (lane == 0) {  // double-buffered by step parity (below)
+                uint32_t* wc = wave_cnt + (k & 1) * 8;
+                wc[2 * wave] = w0;
+                wc[2 * wave + 1] = w1;
+            }
+            p ^= 1;
+            nca += 1;
+        } else if (tid == 0 && row >= 0 && row < H && col >= 0 && col < W) {
+            // no CA pass: Modify patches the one LDS byte in place
+            uint8_t* b = reinterpret_cast<uint8_t*>(S) + 4 * (1 + (row + 1) * PD) + col;
+            if (*b == (uint8_t)a.fire) {
+                *b = (uint8_t)a.empty;
+                patched = 1u;
+            }
+        }
+        // The step's only barrier, outside every condition. It orders (1) the pass's stores / the byte patch before the
+        // next step's reads of that plane, (2) this step's reads of plane p before the next pass's stores into it,
+        // (3) after a pass, the waves' words before everyone's read of them. The words are double-buffered by step
+        // parity: slot k & 1 is written again in step k + 2 at the earliest, which a wave reaches only through step
+        // k + 1's barrier, i.e. after every wave's read here.
+        __syncthreads();
+        if (do_ca) {
+            const uint32_t* wc = wave_cnt + (k & 1) * 8;
+            const uint32_t t0 = wc[0] + wc[2] + wc[4] + wc[6], t1 = wc[1] + wc[3] + wc[5] + wc[7];
+            hh = (t1 >> 16) != 0u ? 1u : 0u;
+            c0 = (int32_t)(t0 & 0xFFFFu);
+            c1 = (int32_t)(t0 >> 16);
+            c2 = (int32_t)(t1 & 0xFFFFu);
+            fz = a.max_freeze;
+        } else {
+            // a countdown step's hit is thread 0's alone and only wave 0 uses it (records, exit): nothing is published.
+            // Waves 1-3 read 0 here, so their c0 / c2 / hh are right only from a CA step until the next hit; they are
+            // never used.
+            hh = (uint32_t)__builtin_amdgcn_readfirstlane((int)patched);
+            c0 += (int32_t)hh;
+            c2 -= (int32_t)hh;
+            fz -= 1;
+        }
+        rs += 1u;
+        // records: lane k & 63 keeps step k's action, TREE and FIRE counts and hit; wave 0 writes the 64 rows of a
+        // chunk at its end, a lane per row, so the two f64 divisions of a reward are done 64 at a time instead of by
+        // one lane in every step (no barrier inside: the other waves just pass)
+        if (lane == (k & 63)) {
+            chunk = act;
+            rec_t = c1;
+            rec_f = c2;
+            rec_h = hh;
+        }
+        if (((k & 63) == 63 || k == K - 1) && wave == 0 && lane <= (k & 63)) {
+            const size_t o = (size_t)((k & ~63) + lane) * a.E + e;
+            if (a.action_out) a.action_out[o] = chunk;
+            if (a.hit_out) a.hit_out[o] = (uint8_t)rec_h;
+            if (a.reward_out) {
+                const double n = (double)HW;
+                a.reward_out[o] = __dsub_rn(__ddiv_rn((double)rec_t, n), __ddiv_rn((double)rec_f, n));
+            }
+        }
+    }
+    // ---- exit (the last step's barrier stands between every LDS store and these reads): the current plane, and after
+    //      at least one CA pass the other one too -- the grid before the last pass with the patches made on it, which
+    //      is what K step calls leave in buf[parity ^ 1]
+    for (int q = 0; q < 2; ++q) {
+        if (q == 1 && nca == 0) break;
+        const int pl = p ^ q;
+        uint8_t* g = (pl ? a.buf1 : a.buf0) + e * HW;
+        const uint32_t* L = heli_lds + pl * NP;
+        int r = r_first, d = d_first;
+        for (int it = 0; it < iters; ++it) {
+            if (r < H) heli_r2g(g, r, d, W, dwords, L[1 + (r + 1) * PD + d]);
+            d += d_step;
+            r += r_step;
+            if (d >= D) {
+                d -= D;
+                r += 1;
+            }
+        }
+    }
+    if (tid != 0) return;
+    a.parity[e] = (uint8_t)p;
+    a.freeze[e] = fz;
+    a.pos[2 * e] = row;
+    a.pos[2 * e + 1] = col;
+    a.counts[3 * e + 0] = c0;
+    a.counts[3 * e + 1] = c1;
+    a.counts[3 * e + 2] = c2;
+    a.hit[e] = (uint8_t)hh;
+    const double n = (double)HW;
+    a.reward[e] = __dsub_rn(__ddiv_rn((double)c1, n), __ddiv_rn((double)c2, n));
+    a.rng_step[e] = rs;
+    a.steps_elapsed[e] += K;
+}
+
+// LDS of the resident rollout: two planes and the waves' words, within the 64 KiB a launch gets by default
+bool heli_rollout_fits(int H, int W, int* D, int* plane_words, size_t* lds_bytes) {
+    const int64_t d = ((int64_t)W + 3) / 4;
+    const int64_t words = (1 + ((int64_t)H + 2) * (d + 1) + 3) & ~(int64_t)3;
+    const int64_t bytes = 2 * words * 4 + 16 * 4;
+    if (bytes > 65536) return false;
+    *D = (int)d;
+    *plane_words = (int)words;
+    *lds_bytes = (size_t)bytes;
+    return true;
 }
 
 }  // namespace
@@ -366,9 +664,66 @@ extern "C" int gca_helicopter_step(int empty, int tree, int fire, int max_freeze
     a.reward = reward; a.steps_elapsed = steps_elapsed;
     a.meet = P > 1 ? (unsigned long long*)meet : nullptr;
     a.P = P;
+    a.rec_reward = nullptr;
+    a.rec_hit = nullptr;
     const dim3 grid((unsigned)((int64_t)E * P)), block(HELI_THREADS);
     if (fast) hipLaunchKernelGGL(helicopter_step_kernel<true>, grid, block, 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(helicopter_step_kernel<false>, grid, block, 0, (hipStream_t)stream, a);
     GCA_CHECK_LAUNCH("helicopter_step");
+    return GCA_OK;
+}
+
+extern "C" int gca_helicopter_rollout(int empty, int tree, int fire, int max_freeze, uint64_t seed, int env_offset,
+                                      const int32_t* actions, uint64_t action_seed, int K, int32_t* action_out,
+                                      double* reward_out, uint8_t* hit_out, const double* thresholds, int32_t* freeze,
+                                      uint32_t* rng_step, uint8_t* parity, uint8_t* buf0, uint8_t* buf1, int H, int W,
+                                      int32_t* pos, int32_t* counts, uint8_t* hit, double* reward,
+                                      int64_t* steps_elapsed, int E, void* stream) {
+    GCA_CHECK_ARG(thresholds && freeze && rng_step && parity && buf0 && buf1 && pos && counts && hit && reward &&
+                      steps_elapsed,
+                  "helicopter_rollout: null argument");
+    GCA_CHECK_ARG(E > 0 && H > 0 && W > 0 && max_freeze >= 0, "helicopter_rollout: E, H, W > 0 and max_freeze >= 0");
+    GCA_CHECK_ARG(K >= 0, "helicopter_rollout: K >= 0");
+    GCA_CHECK_ARG(buf0 != buf1, "helicopter_rollout: buf0 and buf1 must differ");
+    GCA_CHECK_ARG((int64_t)H * W < (1 << 30), "helicopter_rollout: grid too large");
+    GCA_CHECK_ARG(((empty | tree | fire) & ~0xFF) == 0 && empty != tree && tree != fire && empty != fire,
+                  "helicopter_rollout: three distinct u8 codes");
+    if (K == 0) return GCA_OK;
+    const bool aligned = (((uintptr_t)buf0 | (uintptr_t)buf1) & 3u) == 0;
+    const dim3 grid((unsigned)E), block(HELI_THREADS);
+    int D = 0, plane_words = 0;
+    size_t lds_bytes = 0;
+    if (heli_rollout_fits(H, W, &D, &plane_words, &lds_bytes)) {
+        HeliRollArgs a;
+        a.empty = empty; a.tree = tree; a.fire = fire; a.max_freeze = max_freeze;
+        a.seed = seed; a.action_seed = action_seed; a.env_offset = env_offset; a.K = K; a.E = E;
+        a.actions = actions; a.action_out = action_out; a.reward_out = reward_out; a.hit_out = hit_out;
+        a.thr = thresholds; a.freeze = freeze; a.rng_step = rng_step; a.parity = parity; a.buf0 = buf0; a.buf1 = buf1;
+        a.H = H; a.W = W; a.D = D; a.plane_words = plane_words; a.dwords = (W % 4 == 0 && aligned) ? 1 : 0;
+        a.pos = pos; a.counts = counts; a.hit = hit; a.reward = reward; a.steps_elapsed = steps_elapsed;
+        hipLaunchKernelGGL(helicopter_rollout_kernel, grid, block, lds_bytes, (hipStream_t)stream, a);
+        GCA_CHECK_LAUNCH("helicopter_rollout");
+        return GCA_OK;
+    }
+    // the planes do not fit in LDS: K launches of the step kernel, one workgroup per env, each writing its record row
+    const bool fast = W % 256 == 0 && aligned;
+    HeliArgs a;
+    a.empty = empty; a.tree = tree; a.fire = fire; a.max_freeze = max_freeze;
+    a.seed = seed; a.action_seed = action_seed; a.env_offset = env_offset;
+    a.thr = thresholds; a.freeze = freeze; a.rng_step = rng_step;
+    a.parity = parity; a.buf0 = buf0; a.buf1 = buf1; a.H = H; a.W = W; a.pos = pos; a.counts = counts; a.hit = hit;
+    a.reward = reward; a.steps_elapsed = steps_elapsed;
+    a.meet = nullptr;
+    a.P = 1;
+    for (int k = 0; k < K; ++k) {
+        const size_t o = (size_t)k * (size_t)E;
+        a.action = actions ? actions + o : nullptr;
+        a.action_out = action_out ? action_out + o : nullptr;
+        a.rec_reward = reward_out ? reward_out + o : nullptr;
+        a.rec_hit = hit_out ? hit_out + o : nullptr;
+        if (fast) hipLaunchKernelGGL(helicopter_step_kernel<true>, grid, block, 0, (hipStream_t)stream, a);
+        else hipLaunchKernelGGL(helicopter_step_kernel<false>, grid, block, 0, (hipStream_t)stream, a);
+        GCA_CHECK_LAUNCH("helicopter_rollout");
+    }
     return GCA_OK;
 }

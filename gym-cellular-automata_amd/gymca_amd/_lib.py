@@ -228,6 +228,8 @@ _SIGNATURES = {
     "gca_ds_step": ([P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, c_uint64, P, c_int, P, P], c_int),
     "gca_helicopter_step": ([c_int, c_int, c_int, c_int, c_uint64, c_int, P, c_uint64, P, P, P, P, P, P, P, c_int, c_int,
                              P, P, P, P, P, P, c_int, P], c_int),
+    "gca_helicopter_rollout": ([c_int, c_int, c_int, c_int, c_uint64, c_int, P, c_uint64, c_int, P, P, P, P, P, P, P, P,
+                                P, c_int, c_int, P, P, P, P, P, c_int, P], c_int),
     "gca_bench_copy": ([P, P, c_int64, c_int, P], c_int),
     "gca_bench_march_pattern": ([c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P], c_int),
 }
@@ -235,7 +237,8 @@ _SIGNATURES = {
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 # the subset libgca_cpu.so exports (tiny grids and the O(1)-per-env operators on host arrays)
 CPU_SYMBOLS = ("gca_last_error", "gca_version", "gca_philox", "gca_count_cells", "gca_move_modify",
-               "gca_ds_count_draws", "gca_ds_step", "gca_helicopter_step", "gca_bulldozer_reset_where")
+               "gca_ds_count_draws", "gca_ds_step", "gca_helicopter_step", "gca_helicopter_rollout",
+               "gca_bulldozer_reset_where")
 
 _lib = None
 _lib_cpu = None

@@ -3,6 +3,7 @@
 The batched form of helicopter.py's MDP (reference helicopter.py:220-236 + ca_env.py:27-48). gca_helicopter_step
 does the whole step of every env: the action (the caller's, or drawn inside the step), Move, the Drossel–Schwabl CA
 when the env's freeze countdown is 0, Modify {FIRE: EMPTY} at the moved position, freeze, cell counts and reward.
+rollout(actions) runs K such steps in one launch (gca_helicopter_rollout: the env's grid stays in LDS between steps).
 
 Grids live in two buffers; env e's current grid is buf[parity[e]][e], so an env whose countdown is still running
 moves no bytes beyond the one cell Modify may patch. The CA's draws are Philox keyed by (cell, global env id,
@@ -172,6 +173,7 @@ class BatchedForestFireHelicopterEnv:
         self._step_call = None
         self._random_call = None
         self._sample_call = None
+        self._rollout_call = None
         self._info = {"hit": self.hit}
         self._ctx = {"ca_params": self.ca_params, "position": self.pos, "freeze": self.freeze}
 
@@ -225,6 +227,78 @@ class BatchedForestFireHelicopterEnv:
             rc = self._random_call = (key, out, self._bind(None, int(seed) & (2**64 - 1), dev.ptr(out), keep=(out,)))
         rc[2](dev.raw_stream(self._dev_index))
         return self._result()
+
+    def _check_record(self, out, dtype, K, who, what):
+        import torch
+
+        if not (type(out) is torch.Tensor and out.dtype is dtype and out.get_device() == self._dev_index
+                and tuple(out.shape) == (K, self.num_envs) and out.is_contiguous()):
+            raise ValueError(f"{who}: {what} must be a contiguous {str(dtype).replace('torch.', '')} (K, E) tensor on "
+                             "the env's device")
+        return out
+
+    def rollout(self, actions=None, K=None, seed=9, action_out=None, reward_out=None, hit_out=None):
+        """K env steps of every env in one call: exactly K step(actions[k]) calls (frame-skip / action-repeat, open-loop
+        planners scoring candidate action sequences from one state, recorded trajectories), or with actions=None K
+        step_random(seed) calls. actions: (K, E) ints decided before the call; a contiguous int32 device tensor on the
+        env's device is used as it is, anything else is converted. Returns (reward_out, hit_out): float64 and uint8
+        (K, E) device tensors, row k what step k leaves in env.reward / env.hit (allocated here unless given);
+        `action_out` (int32 (K, E), only when given) receives the actions taken, unclamped. Afterwards the env is in the
+        state the K calls leave (env.reward, env.hit, grids(), the context tensors), so step / step_random / rollout
+        interleave freely. A grid whose two padded planes fit in 64 KiB of LDS runs the K steps in ONE launch
+        (gca_helicopter_rollout), other shapes in K launches; no sync either way."""
+        import torch
+
+        E = self.num_envs
+        if actions is None:
+            if K is None:
+                raise ValueError("rollout: K is needed with actions=None")
+            K, a = int(K), None
+        else:
+            a = actions
+            if not (type(a) is torch.Tensor and a.dtype is torch.int32 and a.get_device() == self._dev_index
+                    and a.is_contiguous()):
+                if dev.is_device_tensor(a):
+                    if a.is_floating_point() or a.dtype is torch.bool:
+                        raise ValueError("rollout: actions must be integers")
+                    if a.device != self.device:
+                        raise ValueError(f"rollout: actions live on {a.device}, the env on {self.device}")
+                    a = a.to(torch.int32).contiguous()
+                else:
+                    h = np.asarray(a)
+                    if h.dtype.kind not in "iu":
+                        raise ValueError("rollout: actions must be integers")
+                    a = dev.to_device(h.astype(np.int32), torch.int32, self.device)
+            if a.dim() != 2 or a.shape[1] != E:
+                raise ValueError(f"rollout: actions must have shape (K, {E}), got {tuple(a.shape)}")
+            if K is not None and int(K) != a.shape[0]:
+                raise ValueError(f"rollout: K = {K} disagrees with actions of shape {tuple(a.shape)}")
+            K = int(a.shape[0])
+        if K < 0:
+            raise ValueError("rollout: K >= 0")
+        kw = dict(device=self.device)
+        reward_out = torch.empty((K, E), dtype=torch.float64, **kw) if reward_out is None else \
+            self._check_record(reward_out, torch.float64, K, "rollout", "reward_out")
+        hit_out = torch.empty((K, E), dtype=torch.uint8, **kw) if hit_out is None else \
+            self._check_record(hit_out, torch.uint8, K, "rollout", "hit_out")
+        if action_out is not None:
+            self._check_record(action_out, torch.int32, K, "rollout", "action_out")
+        if K == 0:
+            return reward_out, hit_out
+        rc = self._rollout_call
+        if rc is None:
+            H, W = self.nrows, self.ncols
+            rc = self._rollout_call = BoundCall(
+                "gca_helicopter_rollout", self._empty, self._tree, self._fire, self.max_freeze,
+                self.seed_value & (2**64 - 1), self.env_offset, SLOT, SLOT, SLOT, SLOT, SLOT, SLOT,
+                dev.ptr(self.thresholds), dev.ptr(self.freeze), dev.ptr(self.rng_step), dev.ptr(self.parity),
+                dev.ptr(self.buf[0]), dev.ptr(self.buf[1]), H, W, dev.ptr(self.pos), dev.ptr(self.counts),
+                dev.ptr(self.hit), dev.ptr(self.reward), dev.ptr(self.steps_elapsed), E, SLOT,
+                keep=self._bound_tensors())
+        rc(None if a is None else a.data_ptr(), int(seed) & (2**64 - 1), K,
+           None if action_out is None else action_out.data_ptr(), reward_out.data_ptr(), hit_out.data_ptr(),
+           dev.raw_stream(self._dev_index))
+        return reward_out, hit_out
 
     def sample_actions(self, out=None, tag=9):
         """Uniform random actions in [0, 9) for every env on the device -- the batched `action_space.sample()`: column

@@ -534,6 +534,27 @@ int gca_helicopter_step(int empty, int tree, int fire, int max_freeze, uint64_t 
                         int W, int32_t* pos, int32_t* counts, uint8_t* hit, double* reward, int64_t* steps_elapsed,
                         uint64_t* meet, int E, void* stream);
 
+/* K consecutive ForestFireHelicopter env steps of E envs (K x helicopter.py:220-236 MDP.update + ca_env.py:27-48 step /
+ * reward): exactly K calls of gca_helicopter_step on the same state tensors, step k taking actions + k*E. actions
+ * (K, E) int32, decided before the launch (frame-skip, open-loop planners, recorded trajectories); actions == NULL:
+ * step k draws its actions inside the step from action_seed, keyed by the env's rng_step at that step, as
+ * gca_helicopter_step's action == NULL does. Afterwards every state tensor (both planes of buf, parity, freeze, pos,
+ * counts, rng_step (mod 2^32), hit and reward of the last step, steps_elapsed) holds bit for bit what the K calls
+ * leave. Records, each (K, E) and nullable: row k of action_out / reward_out / hit_out = what step k writes to
+ * action_out (the raw action, unclamped) / reward / hit.
+ * A grid whose two 4-byte-pitched, EMPTY-padded planes fit in 64 KiB of LDS (4 * (1 + (H + 2) * (ceil(W / 4) + 1))
+ * bytes each) runs all K steps in ONE launch, one workgroup per env, the grid resident in LDS and the env's scalars
+ * in registers; global memory is touched at entry, at exit and for the records. Other shapes run K launches of the
+ * step kernel (one workgroup per env, no meet) on the same stream: the same results, the caller need not know which.
+ * Launches only (no sync, no allocation, no memset): capturable. K == 0 is a no-op, K < 0 an argument error; the other
+ * arguments and limits are gca_helicopter_step's. The host build runs plain loops. */
+int gca_helicopter_rollout(int empty, int tree, int fire, int max_freeze, uint64_t seed, int env_offset,
+                           const int32_t* actions, uint64_t action_seed, int K, int32_t* action_out,
+                           double* reward_out, uint8_t* hit_out, const double* thresholds, int32_t* freeze,
+                           uint32_t* rng_step, uint8_t* parity, uint8_t* buf0, uint8_t* buf1, int H, int W,
+                           int32_t* pos, int32_t* counts, uint8_t* hit, double* reward, int64_t* steps_elapsed, int E,
+                           void* stream);
+
 /* ------------------------------------------ measurement yardsticks (bench.py; no reference counterpart)
  * gca_bench_copy: a 16-B device copy of nbytes (one element per thread, one pass) (a multiple of 16, 16-B aligned), nt != 0 non-temporal
  * loads and stores: the practical HBM ceiling the bench reports beside the 8 TB/s spec.
