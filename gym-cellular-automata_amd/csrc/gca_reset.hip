@@ -5,23 +5,9 @@
 // the bulldozer's position from the per-env draws of _seeding.env_integers restated here, the cell counts of the grid
 // just written, and the per-env state of a fresh episode (ca_env.py:64-81). Device pointers only, no memset, no atomics,
 // no host synchronisation: the call can be captured in a graph right after an env step.
-#include "gca_common.h"
+#include "gca_reset_dev.h"  // the draws, shared with the rollout kernel's in-launch reset (gca_windy.hip)
 
 #define RESET_MAX_THREADS 1024
-
-// _seeding._splitmix64 / env_draws / env_integers, bit for bit
-__device__ __forceinline__ uint64_t splitmix64_dev(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-// integer in [0, span) for (seed, global env id, tag): multiply-shift of the draw's top 32 bits
-__device__ __forceinline__ int32_t env_integer_dev(uint64_t seed, uint64_t env_id, uint32_t tag, uint32_t span) {
-    const uint64_t h = splitmix64_dev(seed ^ (uint64_t)tag);
-    const uint64_t r = splitmix64_dev(h ^ splitmix64_dev(env_id));
-    return (int32_t)(((r >> 32) * (uint64_t)span) >> 32);
-}
 
 // One workgroup per env. Every thread reads the env's selection inputs (wave-uniform addresses) before any write of the
 // launch to them: the only writer of done / steps_elapsed / episode is thread 0 after the barrier below.
@@ -35,14 +21,12 @@ __global__ __launch_bounds__(RESET_MAX_THREADS) void bulldozer_reset_where_kerne
     __shared__ int32_t wave_cnt[RESET_MAX_THREADS / GCA_WAVE][3];
     const int e = blockIdx.x;
     const int tid = threadIdx.x;
-    const uint32_t k0 = (uint32_t)reset_seed, k1 = (uint32_t)(reset_seed >> 32);
     // ---- per-env inputs, issued together
     const bool was_done = done[e] != 0;
     const int64_t se = steps_elapsed[e];
     const uint32_t ep = episode[e];
     const bool by_mask = mask ? mask[e] != 0 : was_done;
-    const float cdf0 = cdf[0], cdf1 = cdf[1];
-    const uint32_t v0 = values[0], v1 = values[1], v2 = values[2];
+    const ResetDist dist = reset_dist(cdf, values);
     const bool by_limit = max_steps > 0 && se >= max_steps;
     const bool selected = by_mask || by_limit;
     if (tid == 0) {
@@ -53,51 +37,11 @@ __global__ __launch_bounds__(RESET_MAX_THREADS) void bulldozer_reset_where_kerne
 
     const uint32_t k = set_episode >= 0 ? (uint32_t)set_episode : ep + 1u;
     const uint64_t env_id = (uint64_t)(int64_t)(env_offset + e);
-    const uint32_t ktag = (k & 0xFFFFFFu) << 8;
-    const uint32_t span_h = (uint32_t)max(1, H / 12), span_w = (uint32_t)max(1, W / 12);
-    // one FIRE around the lower-left quadrant (bulldozer.py:221-253); the bulldozer around the upper-right (:255-275)
-    const int fr = 3 * H / 4 + env_integer_dev(reset_seed, env_id, 1u | ktag, span_h);
-    const int fc = W / 4 + env_integer_dev(reset_seed, env_id, 2u | ktag, span_w);
     const int64_t HW = (int64_t)H * W;
-    const int64_t fire_cell = (int64_t)fr * W + fc;
-    const int64_t fire_quad = fire_cell >> 2;
-    const uint32_t fire_shift = 8u * (uint32_t)(fire_cell & 3);
-
-    uint8_t* __restrict__ g = buf0 + e * HW;
-    const bool aligned = (((uintptr_t)g) & 3u) == 0;  // wave-uniform
-    const int64_t quads = (HW + 3) >> 2;
-    const uint32_t pe = rep4(empty), pt = rep4(tree), pf = rep4(fire);
     int32_t cE = 0, cT = 0, cF = 0;
-    for (int64_t q = tid; q < quads; q += blockDim.x) {
-        const u32x4 x = philox4x32_10(u32x4{(uint32_t)q, (uint32_t)env_id, k, GCA_TAG_INIT}, k0, k1);
-        const uint32_t xs[4] = {x.x, x.y, x.z, x.w};
-        uint32_t word = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float u = u01_f32(xs[j]);
-            const uint32_t v = u < cdf0 ? v0 : (u < cdf1 ? v1 : v2);
-            word |= v << (8 * j);
-        }
-        // the owner of the fire cell's quad plants it before the store: one store per byte, no ordering to reason about
-        if (q == fire_quad) word = (word & ~(0xFFu << fire_shift)) | ((fire & 0xFFu) << fire_shift);
-        const int64_t i = q << 2;
-        const int nvalid = (int)min((int64_t)4, HW - i);
-        const uint32_t valid = nvalid == 4 ? 0x01010101u : ((1u << (8 * nvalid)) - 1u) & 0x01010101u;
-        cE += __popc(bytes_eq01(word, pe) & valid);
-        cT += __popc(bytes_eq01(word, pt) & valid);
-        cF += __popc(bytes_eq01(word, pf) & valid);
-        if (aligned && nvalid == 4) {
-            *reinterpret_cast<uint32_t*>(g + i) = word;
-        } else {
-            for (int j = 0; j < nvalid; ++j) g[i + j] = (uint8_t)(word >> (8 * j));
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        cE += __shfl_xor(cE, off);
-        cT += __shfl_xor(cT, off);
-        cF += __shfl_xor(cF, off);
-    }
+    reset_fill_grid<false>(buf0 + e * HW, HW, tid, (int)blockDim.x, reset_seed, env_id, k, dist,
+                           reset_fire_cell(reset_seed, env_id, k, H, W), empty, tree, fire, cE, cT, cF);
+    wave_sum3(cE, cT, cF);
     const int wave = tid >> 6;
     if ((tid & 63) == 0) {
         wave_cnt[wave][0] = cE;
@@ -116,8 +60,10 @@ __global__ __launch_bounds__(RESET_MAX_THREADS) void bulldozer_reset_where_kerne
     counts[3 * e + 0] = sE;
     counts[3 * e + 1] = sT;
     counts[3 * e + 2] = sF;
-    pos[2 * e] = H / 4 + env_integer_dev(reset_seed, env_id, 3u | ktag, span_h);
-    pos[2 * e + 1] = 3 * W / 4 + env_integer_dev(reset_seed, env_id, 4u | ktag, span_w);
+    int32_t row, col;
+    reset_position(reset_seed, env_id, k, H, W, row, col);
+    pos[2 * e] = row;
+    pos[2 * e + 1] = col;
     if (last_length_out) last_length_out[e] = se;
     episode[e] = k;
     parity[e] = 0;

@@ -19,6 +19,7 @@
 //    horizontal ones from byte funnel shifts plus the neighbour lane's edge dword.
 //    Reward/done counts of the new grid are fused (wave reduction + 3 atomics).
 #include "gca_common.h"
+#include "gca_reset_dev.h"  // the in-launch reset of the rollout kernel
 
 // windy_fast_kernel: row chunks in flight ahead of the one being computed (r01o: 2 / 4 / 8 measured slower than 1)
 constexpr int WINDY_AHEAD = 1;
@@ -758,13 +759,39 @@ __global__ __launch_bounds__(256) void bulldozer_step_fused_parts_kernel(
 // before the other waves' CA reads) and closes with one (the new grid and the counts). Otherwise thread 0 applies
 // Modify and broadcasts its counts through LDS behind a barrier per step. (Every thread applying Modify itself was
 // tried first: a slow wave then reads the cell a fast wave already rewrote and miscounts, r06f.)
-template <int NW, bool STD, bool SOLO>
+//
+// EXT (gca_bulldozer_rollout): the caller's actions (K, E, 2) from ext.actions (ACT) -- step k + 1's pair is loaded
+// before step k's work, so the load is off the step's chain -- and a truncated record next to done_out (zeros here).
+// RESET (EXT with autoreset): after each step an env that is done, or whose steps_elapsed reached ext.max_steps, starts
+// its next episode inside the launch exactly as gca_bulldozer_reset_where(mask = NULL, set_episode = -1) would after
+// that step (the draws of gca_reset_dev.h): done_out / ext.truncated_out record what that reset saw, every wave refills
+// buf0 and the workgroup takes the new counts through wave_cnt. Whether an env resets is uniform over its workgroup
+// (every thread holds the FIRE count and steps_elapsed), so the refill's barriers sit in a uniform branch: one before
+// it under SOLO (thread 0's Modify since the last barrier may have written a byte of buf0, and a step without a CA
+// pass has no barrier of its own; !SOLO has its per-step barrier after Modify) and one after it (the next CA step and
+// thread 0's next Modify read cells other waves wrote). Only the resetting env's workgroup pays for it.
+struct RolloutExt {
+    const int32_t* actions;  // (K, E, 2) or NULL: the random policy under `seed`
+    uint8_t* truncated_out;  // (K, E) or NULL
+    // RESET only
+    uint64_t reset_seed;
+    int64_t max_steps;
+    const float* cdf;
+    const uint8_t* values;
+    uint32_t* episode;
+    int64_t* last_length;
+    uint8_t* terminated;
+    uint8_t* truncated;
+};
+template <int NW, bool STD, bool SOLO, bool EXT = false, bool RESET = false, bool ACT = false>
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) void bulldozer_rollout_random_kernel(
     gca_bulldozer_params p, int K, uint64_t seed, int32_t* __restrict__ action_out, double* __restrict__ reward_out,
     uint8_t* __restrict__ done_out, double* __restrict__ accu, int32_t* __restrict__ steps, uint8_t* __restrict__ done,
     const double* __restrict__ wind, int64_t wind_stride, uint32_t* __restrict__ rng_step, uint8_t* __restrict__ parity,
     uint8_t* buf0, uint8_t* buf1, int H, int32_t* __restrict__ pos, int32_t* __restrict__ counts,
-    uint8_t* __restrict__ hit, double* __restrict__ reward, int64_t* __restrict__ steps_elapsed, int E) {
+    uint8_t* __restrict__ hit, double* __restrict__ reward, int64_t* __restrict__ steps_elapsed, int E, RolloutExt ext) {
+    static_assert(EXT || (!RESET && !ACT), "the caller's actions and the reset are EXT instantiations");
+    static_assert(!(RESET && ACT), "the reset instantiation reads ext.actions at run time");
     constexpr int W = 256 * NW;
     __shared__ int32_t wave_cnt[2][16][3];  // per CA step, double-buffered (no barrier after the counts are read)
     __shared__ int32_t bc[2][4];  // !SOLO: thread 0 -> the workgroup, per step (double-buffered): E, T, F counts, hit
@@ -787,9 +814,35 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
     for (int k = 0; k < 9; ++k) wl[k] = wind[(int64_t)e * wind_stride + k];
     const int64_t HW = (int64_t)H * W;
     const uint32_t lofs = 4 * NW * (uint32_t)lane;
+    // EXT: the caller's action of the step ahead (wave-uniform addresses), RESET: the env's episode index
+    int32_t nact0 = 0, nact1 = 0;
+    uint32_t ep = 0;
+    bool term = false, trunc_f = false;  // RESET: what the last step's reset saw
+    // whose actions: known at compile time without the reset (a run-time test per step cost 5 % of the 1024 x 256^2
+    // random-policy rollout), read from ext.actions in the reset instantiation
+    const bool use_act = RESET ? ext.actions != nullptr : ACT;
+    if (use_act && K > 0) {
+        nact0 = ext.actions[2 * (size_t)e];
+        nact1 = ext.actions[2 * (size_t)e + 1];
+    }
+    if constexpr (RESET) ep = ext.episode[e];
+    // without the reset no step is truncated: the record's column of this env is zeroed here by the whole workgroup, off
+    // the steps' chain (a store per step by thread 0 cost 3 % of the same rollout)
+    if constexpr (EXT && !RESET) {
+        if (ext.truncated_out)
+            for (int k = tid; k < K; k += (int)blockDim.x) ext.truncated_out[(size_t)k * E + e] = 0;
+    }
     for (int k = 0; k < K; ++k) {
         int32_t act0, act1;
-        fused_action(nullptr, FusedPolicy{seed, nullptr}, e, env_id, rs, act0, act1);
+        if (use_act) {
+            act0 = nact0;
+            act1 = nact1;
+            const size_t kn = (size_t)min(k + 1, K - 1) * E + e;  // the last step loads its own pair again: in bounds
+            nact0 = ext.actions[2 * kn];
+            nact1 = ext.actions[2 * kn + 1];
+        } else {
+            fused_action(nullptr, FusedPolicy{seed, nullptr}, e, env_id, rs, act0, act1);
+        }
         const size_t ke = (size_t)k * E + e;
         if (action_out && tid == 0) {
             action_out[2 * ke] = act0;
@@ -804,92 +857,144 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
             rew = 0.0;
             if (tid == 0) {
                 if (reward_out) reward_out[ke] = 0.0;
-                if (done_out) done_out[ke] = 1;
+                if (!RESET && done_out) done_out[ke] = 1;
             }
-            continue;
+            if constexpr (!RESET) continue;
         }
-        int nrow = row, ncol = col;
-        move_pos(a0, nrow, ncol, H, W, p.up_mask, p.down_mask, p.left_mask, p.right_mask);
-        uint8_t* grid = (odd ? buf1 : buf0) + e * HW;
-        if (n > 0) {
-            if constexpr (SOLO) __syncthreads();  // thread 0's Modify writes since the last barrier, before the CA reads
-            auto get_mask = [&]() -> uint32_t { return wave_windy_mask(p, wl, e, rs, lane); };
-            const uint8_t* S = grid;
-            uint8_t* Dst = (odd ? buf0 : buf1) + e * HW;
-            int32_t cntT = 0, cntF = 0, cntV = 0;
-            for (int s0 = wave * FUSED_SH<NW>; s0 < H; s0 += nw * FUSED_SH<NW>)
-                windy_rows_strip_f<NW, FUSED_SH<NW>, FUSED_RD<NW>, STD>(S, Dst, s0, H, get_mask, lofs, rep4(p.empty),
-                                                                       rep4(p.tree), rep4(p.fire), cntT, cntF, cntV);
+        if (!RESET || n >= 0) {  // (the reset instantiation goes on to reset the finished env below)
+            int nrow = row, ncol = col;
+            move_pos(a0, nrow, ncol, H, W, p.up_mask, p.down_mask, p.left_mask, p.right_mask);
+            uint8_t* grid = (odd ? buf1 : buf0) + e * HW;
+            if (n > 0) {
+                if constexpr (SOLO) __syncthreads();  // thread 0's Modify writes since the last barrier, before the CA reads
+                auto get_mask = [&]() -> uint32_t { return wave_windy_mask(p, wl, e, rs, lane); };
+                const uint8_t* S = grid;
+                uint8_t* Dst = (odd ? buf0 : buf1) + e * HW;
+                int32_t cntT = 0, cntF = 0, cntV = 0;
+                for (int s0 = wave * FUSED_SH<NW>; s0 < H; s0 += nw * FUSED_SH<NW>)
+                    windy_rows_strip_f<NW, FUSED_SH<NW>, FUSED_RD<NW>, STD>(S, Dst, s0, H, get_mask, lofs, rep4(p.empty),
+                                                                           rep4(p.tree), rep4(p.fire), cntT, cntF, cntV);
 #pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                cntT += __shfl_xor(cntT, off);
-                cntF += __shfl_xor(cntF, off);
-                cntV += __shfl_xor(cntV, off);
-            }
-            int32_t (*WC)[3] = wave_cnt[ca & 1];  // a wave that runs ahead writes the other buffer at the next CA step
-            ++ca;
-            if (lane == 0) {
-                WC[wave][0] = cntV - cntT - cntF;
-                WC[wave][1] = cntT;
-                WC[wave][2] = cntF;
-            }
-            __syncthreads();  // the new grid (every wave's stores) and the counts are complete
-            grid = Dst;
-            odd = !odd;
-            cE = cT = cF = 0;
-            for (int w = 0; w < nw; ++w) {
-                cE += WC[w][0];
-                cT += WC[w][1];
-                cF += WC[w][2];
-            }
-        }
-        acc = x - reps;
-        row = nrow;
-        col = ncol;
-        // MoveModify (move_modify.py:128-134): Modify at the new position, on the post-CA grid
-        auto modify = [&](int32_t& mE, int32_t& mT, int32_t& mF) -> uint8_t {
-            uint8_t hh = 0;
-            if (act1 && row >= 0 && row < H && col >= 0 && col < W) {
-                const int v = grid[(int64_t)row * W + col];
-                const int nv = p.effect[v];
-                if (nv >= 0) {
-                    grid[(int64_t)row * W + col] = (uint8_t)nv;
-                    hh = 1;
-                    const int c_old = cell_category(v, p.empty, p.tree, p.fire);
-                    const int c_new = cell_category(nv, p.empty, p.tree, p.fire);
-                    if (c_old == 0) mE -= 1; else if (c_old == 1) mT -= 1; else if (c_old == 2) mF -= 1;
-                    if (c_new == 0) mE += 1; else if (c_new == 1) mT += 1; else if (c_new == 2) mF += 1;
+                for (int off = 32; off > 0; off >>= 1) {
+                    cntT += __shfl_xor(cntT, off);
+                    cntF += __shfl_xor(cntF, off);
+                    cntV += __shfl_xor(cntV, off);
+                }
+                int32_t (*WC)[3] = wave_cnt[ca & 1];  // a wave that runs ahead writes the other buffer at the next CA step
+                ++ca;
+                if (lane == 0) {
+                    WC[wave][0] = cntV - cntT - cntF;
+                    WC[wave][1] = cntT;
+                    WC[wave][2] = cntF;
+                }
+                __syncthreads();  // the new grid (every wave's stores) and the counts are complete
+                grid = Dst;
+                odd = !odd;
+                cE = cT = cF = 0;
+                for (int w = 0; w < nw; ++w) {
+                    cE += WC[w][0];
+                    cT += WC[w][1];
+                    cF += WC[w][2];
                 }
             }
-            return hh;
-        };
-        if constexpr (SOLO) {
-            if (tid == 0) h = modify(cE, cT, cF);  // FIRE count unchanged (host-checked): the other threads' cF holds
-        } else {
-            int32_t* B = bc[k & 1];
-            if (tid == 0) {
-                const uint8_t hh = modify(cE, cT, cF);
-                B[0] = cE;
-                B[1] = cT;
-                B[2] = cF;
-                B[3] = hh;
+            acc = x - reps;
+            row = nrow;
+            col = ncol;
+            // MoveModify (move_modify.py:128-134): Modify at the new position, on the post-CA grid
+            auto modify = [&](int32_t& mE, int32_t& mT, int32_t& mF) -> uint8_t {
+                uint8_t hh = 0;
+                if (act1 && row >= 0 && row < H && col >= 0 && col < W) {
+                    const int v = grid[(int64_t)row * W + col];
+                    const int nv = p.effect[v];
+                    if (nv >= 0) {
+                        grid[(int64_t)row * W + col] = (uint8_t)nv;
+                        hh = 1;
+                        const int c_old = cell_category(v, p.empty, p.tree, p.fire);
+                        const int c_new = cell_category(nv, p.empty, p.tree, p.fire);
+                        if (c_old == 0) mE -= 1; else if (c_old == 1) mT -= 1; else if (c_old == 2) mF -= 1;
+                        if (c_new == 0) mE += 1; else if (c_new == 1) mT += 1; else if (c_new == 2) mF += 1;
+                    }
+                }
+                return hh;
+            };
+            if constexpr (SOLO) {
+                if (tid == 0) h = modify(cE, cT, cF);  // FIRE count unchanged (host-checked): the other threads' cF holds
+            } else {
+                int32_t* B = bc[k & 1];
+                if (tid == 0) {
+                    const uint8_t hh = modify(cE, cT, cF);
+                    B[0] = cE;
+                    B[1] = cT;
+                    B[2] = cF;
+                    B[3] = hh;
+                }
+                __syncthreads();  // the Modify write and its counts, for every wave's next step
+                cE = B[0];
+                cT = B[1];
+                cF = B[2];
+                h = (uint8_t)B[3];
             }
-            __syncthreads();  // the Modify write and its counts, for every wave's next step
-            cE = B[0];
-            cT = B[1];
-            cF = B[2];
-            h = (uint8_t)B[3];
+            rew = (cT + cF) > 0 ? -((double)cF / (double)(cT + cF)) : (double)NAN;
+            was_done = cF == 0;
+            rs += (uint32_t)n;
+            se += 1;
+            if (tid == 0) {
+                if (reward_out) reward_out[ke] = rew;
+                if (!RESET && done_out) done_out[ke] = was_done ? 1 : 0;
+            }
         }
-        rew = (cT + cF) > 0 ? -((double)cF / (double)(cT + cF)) : (double)NAN;
-        was_done = cF == 0;
-        rs += (uint32_t)n;
-        se += 1;
-        if (tid == 0) {
-            if (reward_out) reward_out[ke] = rew;
-            if (done_out) done_out[ke] = was_done ? 1 : 0;
+        if constexpr (RESET) {
+            // gca_bulldozer_reset_where(mask = NULL, set_episode = -1) after this step: the flags it saw, for every env
+            const bool by_limit = ext.max_steps > 0 && se >= ext.max_steps;
+            term = was_done;
+            trunc_f = by_limit && !was_done;
+            if (tid == 0) {
+                if (done_out) done_out[ke] = term ? 1 : 0;
+                if (ext.truncated_out) ext.truncated_out[ke] = trunc_f ? 1 : 0;
+            }
+            if (was_done || by_limit) {  // workgroup-uniform
+                const ResetDist dist = reset_dist(ext.cdf, ext.values);
+                ep += 1u;
+                const int64_t fire_cell = reset_fire_cell(ext.reset_seed, (uint64_t)env_id, ep, H, W);
+                // thread 0's Modify write since the last barrier (SOLO: a step without a CA pass has none) must land
+                // before another wave's refill of the same byte
+                if constexpr (SOLO) __syncthreads();
+                int32_t rE = 0, rT = 0, rF = 0;
+                reset_fill_grid<true>(buf0 + e * HW, HW, tid, (int)blockDim.x, ext.reset_seed, (uint64_t)env_id, ep,
+                                      dist, fire_cell, (uint32_t)p.empty, (uint32_t)p.tree, (uint32_t)p.fire, rE, rT, rF);
+                wave_sum3(rE, rT, rF);
+                int32_t (*WC)[3] = wave_cnt[ca & 1];  // the CA steps' buffers and their alternation
+                ++ca;
+                if (lane == 0) {
+                    WC[wave][0] = rE;
+                    WC[wave][1] = rT;
+                    WC[wave][2] = rF;
+                }
+                __syncthreads();  // the new grid (every wave's stores) and the counts are complete
+                cE = cT = cF = 0;
+                for (int w = 0; w < nw; ++w) {
+                    cE += WC[w][0];
+                    cT += WC[w][1];
+                    cF += WC[w][2];
+                }
+                reset_position(ext.reset_seed, (uint64_t)env_id, ep, H, W, row, col);
+                if (tid == 0) {
+                    if (ext.last_length) ext.last_length[e] = se;
+                    ext.episode[e] = ep;
+                }
+                odd = false;
+                acc = 0.0;
+                was_done = false;
+                h = 0;
+                se = 0;
+            }
         }
     }
     if (tid != 0 || K == 0) return;
+    if constexpr (RESET) {
+        if (ext.terminated) ext.terminated[e] = term ? 1 : 0;
+        if (ext.truncated) ext.truncated[e] = trunc_f ? 1 : 0;
+    }
     steps[e] = last_n;
     reward[e] = rew;
     accu[e] = acc;
@@ -1100,7 +1205,7 @@ extern "C" int gca_bulldozer_rollout_random(const gca_bulldozer_params* p, uint6
 #define GCA_ROLLOUT_LAUNCH(NWV, STDV, SOLOV)                                                                             \
     hipLaunchKernelGGL((bulldozer_rollout_random_kernel<NWV, STDV, SOLOV>), dim3((unsigned)E), dim3(threads), 0, st, *p, \
                        K, action_seed, action_out, reward_out, done_out, accu, steps, done, wind, wind_stride, rng_step,  \
-                       parity, buf0, buf1, H, pos, counts, hit, reward, steps_elapsed, E)
+                       parity, buf0, buf1, H, pos, counts, hit, reward, steps_elapsed, E, RolloutExt{})
     if (W == 256) {
         if (std_codes && solo) GCA_ROLLOUT_LAUNCH(1, true, true);
         else if (solo) GCA_ROLLOUT_LAUNCH(1, false, true);
@@ -1112,5 +1217,77 @@ extern "C" int gca_bulldozer_rollout_random(const gca_bulldozer_params* p, uint6
     }
 #undef GCA_ROLLOUT_LAUNCH
     GCA_CHECK_LAUNCH("bulldozer_rollout_random");
+    return GCA_OK;
+}
+
+// The rollout with the caller's actions (or the random policy) and, with `autoreset`, the per-env reset after every step
+extern "C" int gca_bulldozer_rollout(const gca_bulldozer_params* p, const int32_t* actions, uint64_t action_seed, int K,
+                                     int32_t* action_out, double* reward_out, uint8_t* terminated_out,
+                                     uint8_t* truncated_out, int autoreset, uint64_t reset_seed, int64_t max_steps,
+                                     const float* cdf, const uint8_t* values, uint32_t* episode, int64_t* last_length,
+                                     uint8_t* terminated, uint8_t* truncated, double* accu, int32_t* steps,
+                                     uint8_t* done, const double* wind, int64_t wind_stride, uint32_t* rng_step,
+                                     uint8_t* parity, uint8_t* buf0, uint8_t* buf1, int H, int W, int32_t* pos,
+                                     int32_t* counts, uint8_t* hit, double* reward, int64_t* steps_elapsed, int E,
+                                     void* stream) {
+    // gca_bulldozer_rollout_random's checks
+    GCA_CHECK_ARG(p && accu && steps && done && wind && rng_step && parity && buf0 && buf1 && pos && counts && hit &&
+                      reward && E > 0 && H > 0 && K >= 0,
+                  "bulldozer_rollout: null argument, empty batch or K < 0");
+    GCA_CHECK_ARG(W == 256 || W == 512, "bulldozer_rollout: W must be 256 or 512 (the row-stream CA)");
+    GCA_CHECK_ARG(p->empty == 0 && p->empty < p->tree && p->tree < p->fire && p->fire < 256,
+                  "bulldozer_rollout: cell codes must be empty = 0 < tree < fire < 256 (the closed-form rule)");
+    GCA_CHECK_ARG(((((uintptr_t)buf0) | ((uintptr_t)buf1)) & 15u) == 0, "bulldozer_rollout: buffers 16-B aligned");
+    GCA_CHECK_ARG(wind_stride >= 0, "bulldozer_rollout: wind_stride >= 0");
+    GCA_CHECK_ARG((int64_t)K * E < ((int64_t)1 << 40), "bulldozer_rollout: K x E too large");
+    double tmax = 0.0;
+    for (int a = 0; a < 9; ++a)
+        for (int b = 0; b < 2; ++b) tmax = fmax(tmax, (p->t_move[a] + p->t_shoot[b]) + p->t_any);
+    GCA_CHECK_ARG(tmax < 1.0, "bulldozer_rollout: an action can take >= 1 time unit (several CA passes per step)");
+    // gca_bulldozer_reset_where's checks (the reset's inputs and state are read only under autoreset)
+    GCA_CHECK_ARG(buf0 != buf1, "bulldozer_rollout: buf0 and buf1 must differ");
+    GCA_CHECK_ARG(H < 32768, "bulldozer_rollout: H < 32768");
+    GCA_CHECK_ARG(max_steps >= 0, "bulldozer_rollout: max_steps >= 0");
+    if (autoreset) {
+        GCA_CHECK_ARG(cdf && values && episode && steps_elapsed,
+                      "bulldozer_rollout: null argument (autoreset needs cdf, values, episode and steps_elapsed)");
+        GCA_CHECK_ARG(p->env_offset >= 0, "bulldozer_rollout: env_offset >= 0");
+    }
+    if (K == 0) return GCA_OK;
+    const int fsh = W == 256 ? FUSED_SH<1> : FUSED_SH<2>;
+    const int strips = (H + fsh - 1) / fsh;
+    const int threads = 64 * (strips < 16 ? strips : 16);
+    hipStream_t st = (hipStream_t)stream;
+    const bool std_codes = p->empty == 0 && p->tree == 3 && p->fire == 25;
+    // SOLO: Modify never changes the FIRE count (the kernel's comment)
+    bool solo = true;
+    for (int v = 0; v < 256; ++v) {
+        const int nv = p->effect[v];
+        if (nv >= 0 && (v == p->fire) != (nv == p->fire)) solo = false;
+    }
+    const RolloutExt ext{actions, truncated_out, reset_seed, max_steps, cdf, values, episode, last_length, terminated,
+                         truncated};
+#define GCA_ROLLOUT_LAUNCH(NWV, STDV, SOLOV, RESETV, ACTV)                                                             \
+    hipLaunchKernelGGL((bulldozer_rollout_random_kernel<NWV, STDV, SOLOV, true, RESETV, ACTV>), dim3((unsigned)E),     \
+                       dim3(threads), 0, st, *p, K, action_seed, action_out, reward_out, terminated_out, accu, steps,  \
+                       done, wind, wind_stride, rng_step, parity, buf0, buf1, H, pos, counts, hit, reward,             \
+                       steps_elapsed, E, ext)
+#define GCA_ROLLOUT_PICK(NWV, RESETV, ACTV)                                       \
+    do {                                                                          \
+        if (std_codes && solo) GCA_ROLLOUT_LAUNCH(NWV, true, true, RESETV, ACTV); \
+        else if (solo) GCA_ROLLOUT_LAUNCH(NWV, false, true, RESETV, ACTV);        \
+        else GCA_ROLLOUT_LAUNCH(NWV, false, false, RESETV, ACTV);                 \
+    } while (0)
+#define GCA_ROLLOUT_MODE(NWV)                                 \
+    do {                                                      \
+        if (autoreset) GCA_ROLLOUT_PICK(NWV, true, false);    \
+        else if (actions) GCA_ROLLOUT_PICK(NWV, false, true); \
+        else GCA_ROLLOUT_PICK(NWV, false, false);             \
+    } while (0)
+    if (W == 256) GCA_ROLLOUT_MODE(1); else GCA_ROLLOUT_MODE(2);
+#undef GCA_ROLLOUT_MODE
+#undef GCA_ROLLOUT_PICK
+#undef GCA_ROLLOUT_LAUNCH
+    GCA_CHECK_LAUNCH("bulldozer_rollout");
     return GCA_OK;
 }

@@ -188,6 +188,9 @@ _SIGNATURES = {
                                          c_int, P, P, P, P, P, P, c_int, P], c_int),
     "gca_bulldozer_rollout_random": ([POINTER(BulldozerParams), c_uint64, c_int, P, P, P, P, P, P, P, c_int64, P, P, P,
                                       P, c_int, c_int, P, P, P, P, P, c_int, P], c_int),
+    "gca_bulldozer_rollout": ([POINTER(BulldozerParams), P, c_uint64, c_int, P, P, P, P, c_int, c_uint64, c_int64, P, P,
+                               P, P, P, P, P, P, P, P, c_int64, P, P, P, P, c_int, c_int, P, P, P, P, P, c_int, P],
+                              c_int),
     "gca_bulldozer_reset_where": ([POINTER(BulldozerParams), c_uint64, P, c_int64, c_int64, P, P, P, P, P, P, P, P, P,
                                    P, P, c_int, c_int, P, P, P, P, c_int, P], c_int),
     "gca_move_modify": ([POINTER(BulldozerParams), P, P, P, c_int, c_int, P, c_int, P], c_int),

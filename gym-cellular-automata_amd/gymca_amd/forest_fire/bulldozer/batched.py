@@ -17,7 +17,8 @@ checked to give identical envs (tests/test_gpu_windy.py).
 Episodes: `reset()` starts episode 0 of every env; `reset_where()` (gca_bulldozer_reset_where, one launch, no host work)
 starts a new episode of the selected envs only, and `autoreset=True` launches it right after every step for the envs
 that finished (or reached `max_episode_steps`): Gymnasium's same-step autoreset, the reference's stateless_step ->
-conditional_reset pair. With both options off nothing of this runs.
+conditional_reset pair. With both options off nothing of this runs. `rollout(actions)` runs K steps of every env, and
+under autoreset the resets between them, in ONE launch (gca_bulldozer_rollout): bit for bit the K step calls.
 
 Grids live in two buffers; env e's current grid is buf[parity[e]][e], so envs whose
 RepeatCA yields 0 repeats this step (most of them: ~1 CA step per 13 env steps at
@@ -135,6 +136,7 @@ class BatchedForestFireBulldozerEnv:
         self._sample_call = None
         self._random_call = self._bound_meet_r = None
         self._reset_call = None
+        self._rollout_call = None
 
     # ------------------------------------------------------------------ state
     def grids(self):
@@ -215,6 +217,7 @@ class BatchedForestFireBulldozerEnv:
         self._sample_call = None
         self._random_call = self._bound_meet_r = None
         self._reset_call = None
+        self._rollout_call = None
         self._views()
 
     def _views(self):
@@ -363,6 +366,108 @@ class BatchedForestFireBulldozerEnv:
              dev.ptr(self.buf[1]), H, W, dev.ptr(self.pos), dev.ptr(self.counts), dev.ptr(self.hit), dev.ptr(self.reward),
              dev.ptr(self.steps_elapsed), E, dev.stream_ptr(self.device))
         return reward_out, done_out
+
+    def _check_record(self, out, dtype, shape, what):
+        import torch
+
+        if not (type(out) is torch.Tensor and out.dtype is dtype and out.get_device() == self._dev_index
+                and tuple(out.shape) == shape and out.is_contiguous()):
+            raise ValueError(f"rollout: {what} must be a contiguous {str(dtype).replace('torch.', '')} "
+                             f"{'(K, E, 2)' if len(shape) == 3 else '(K, E)'} tensor on the env's device")
+        return out
+
+    def rollout(self, actions=None, K=None, seed=9, action_out=None, reward_out=None, terminated_out=None,
+                truncated_out=None):
+        """K env steps of every env in one call: exactly K step(actions[k]) calls (frame-skip / action-repeat, open-loop
+        planners, recorded trajectories), or with actions=None K step_random(seed) calls, under the env's own
+        `autoreset` and `max_episode_steps`: with autoreset=True an env that finishes (or reaches its time limit) at step
+        k starts its next episode before step k + 1, as the reset launch after an eager step does; with autoreset=False
+        finished envs take the no-op step and max_episode_steps is ignored, as step ignores it. actions: (K, E, 2) ints
+        decided before the call (clamped as step clamps them); a contiguous int32 tensor on the env's device is used as
+        it is, anything else is converted. Returns (reward_out, terminated_out, truncated_out): float64 / uint8 / uint8
+        (K, E) device tensors, allocated here unless given; row k holds what step k leaves in env.reward (the terminal
+        step's reward where an episode ended) and the flags of step k (under autoreset what the reset saw, otherwise
+        `done` and zeros). `action_out` (int32 (K, E, 2), only when given) receives the actions taken, unclamped.
+        Afterwards every state tensor, both grid planes and env.reward are what the K calls leave, so step / step_random /
+        reset_where / rollout interleave freely. With the fused step (W = 256 / 512, one CA pass at most per env step)
+        the K steps and the resets between them are ONE launch (gca_bulldozer_rollout), a resetting env overlapping the
+        other envs' steps; otherwise K x (the launches of a step). No sync either way, and with every record given and
+        device int32 actions no allocation: the call can be captured in a graph."""
+        import torch
+
+        E = self.num_envs
+        if actions is None:
+            if K is None:
+                raise ValueError("rollout: K is needed with actions=None")
+            K, a = int(K), None
+        else:
+            a = actions
+            if not (type(a) is torch.Tensor and a.dtype is torch.int32 and a.get_device() == self._dev_index
+                    and a.is_contiguous()):
+                if dev.is_device_tensor(a):
+                    if a.is_floating_point() or a.dtype is torch.bool:
+                        raise ValueError("rollout: actions must be integers")
+                    if a.device != self.device:
+                        raise ValueError(f"rollout: actions live on {a.device}, the env on {self.device}")
+                    a = a.to(torch.int32).contiguous()
+                elif isinstance(a, torch.Tensor):
+                    raise ValueError(f"rollout: actions live on {a.device}, the env on {self.device}")
+                else:
+                    h = np.asarray(a)
+                    if h.dtype.kind not in "iu":
+                        raise ValueError("rollout: actions must be integers")
+                    a = dev.to_device(h.astype(np.int32), torch.int32, self.device)
+            if a.dim() != 3 or a.shape[1] != E or a.shape[2] != 2:
+                raise ValueError(f"rollout: actions must have shape (K, {E}, 2), got {tuple(a.shape)}")
+            if K is not None and int(K) != a.shape[0]:
+                raise ValueError(f"rollout: K = {K} disagrees with actions of shape {tuple(a.shape)}")
+            K = int(a.shape[0])
+        if K < 0:
+            raise ValueError("rollout: K >= 0")
+        kw = dict(device=self.device)
+        reward_out = torch.empty((K, E), dtype=torch.float64, **kw) if reward_out is None else \
+            self._check_record(reward_out, torch.float64, (K, E), "reward_out")
+        terminated_out = torch.empty((K, E), dtype=torch.uint8, **kw) if terminated_out is None else \
+            self._check_record(terminated_out, torch.uint8, (K, E), "terminated_out")
+        truncated_out = torch.empty((K, E), dtype=torch.uint8, **kw) if truncated_out is None else \
+            self._check_record(truncated_out, torch.uint8, (K, E), "truncated_out")
+        if action_out is not None:
+            self._check_record(action_out, torch.int32, (K, E, 2), "action_out")
+        if K == 0:
+            return reward_out, terminated_out, truncated_out
+        if not self.fused:
+            # K x (the launches of a step): each step's results copied into the records on the device
+            for k in range(K):
+                ak = self.sample_actions(tag=seed) if a is None else a[k]
+                self.step(ak)
+                if action_out is not None:
+                    action_out[k].copy_(ak)
+                reward_out[k].copy_(self.reward)
+                if self.autoreset:
+                    terminated_out[k].copy_(self._terminated)
+                    truncated_out[k].copy_(self._truncated_u8)
+                else:
+                    terminated_out[k].copy_(self.done)
+                    truncated_out[k].zero_()
+            return reward_out, terminated_out, truncated_out
+        rc = self._rollout_call
+        if rc is None:
+            H, W = self.nrows, self.ncols
+            rc = self._rollout_call = BoundCall(
+                "gca_bulldozer_rollout", self.params, SLOT, SLOT, SLOT, SLOT, SLOT, SLOT, SLOT, SLOT, SLOT, SLOT,
+                dev.ptr(self._reset_cdf), dev.ptr(self._reset_vals), dev.ptr(self.episode),
+                dev.ptr(self.last_episode_length), dev.ptr(self._terminated), dev.ptr(self._truncated_u8),
+                dev.ptr(self.accu), dev.ptr(self.steps), dev.ptr(self.done), dev.ptr(self.wind), 9,
+                dev.ptr(self.rng_step), dev.ptr(self.parity), dev.ptr(self.buf[0]), dev.ptr(self.buf[1]), H, W,
+                dev.ptr(self.pos), dev.ptr(self.counts), dev.ptr(self.hit), dev.ptr(self.reward),
+                dev.ptr(self.steps_elapsed), E, SLOT,
+                keep=self._bound_tensors() + (self._reset_cdf, self._reset_vals, self._terminated, self._truncated_u8,
+                                              self.episode, self.last_episode_length))
+        rc(None if a is None else a.data_ptr(), int(seed) & (2**64 - 1), K,
+           None if action_out is None else action_out.data_ptr(), reward_out.data_ptr(), terminated_out.data_ptr(),
+           truncated_out.data_ptr(), 1 if self.autoreset else 0, self._reset_seed & (2**64 - 1),
+           (self.max_episode_steps or 0) if self.autoreset else 0, dev.raw_stream(self._dev_index))
+        return reward_out, terminated_out, truncated_out
 
     def sample_actions(self, out=None, tag=9):
         """Uniform random actions for every env on the device -- the batched `action_space.sample()` (move in [0, 9),

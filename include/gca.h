@@ -151,6 +151,32 @@ int gca_bulldozer_rollout_random(const gca_bulldozer_params* p, uint64_t action_
                                  const double* wind, int64_t wind_stride, uint32_t* rng_step, uint8_t* parity,
                                  uint8_t* buf0, uint8_t* buf1, int H, int W, int32_t* pos, int32_t* counts, uint8_t* hit,
                                  double* reward, int64_t* steps_elapsed, int E, void* stream);
+/* K env steps of every env in ONE launch with the caller's actions and, optionally, same-step autoreset: the batched
+ * form of K iterations of `env.step(action)` (bulldozer.py:393-400, ca_env.py:27-62) followed, under autoreset, by the
+ * reference's conditional reset of the envs that finished (ca_env.py:64-81). Bit for bit K consecutive
+ * gca_bulldozer_step_fused calls on actions[k] (actions (K, E, 2) int32, decided before the call; NULL: K
+ * gca_bulldozer_step_fused_random calls under action_seed), each followed when autoreset != 0 by
+ * gca_bulldozer_reset_where(mask = NULL, max_steps, set_episode = -1): one workgroup per env keeps the env's state in
+ * registers across the K steps, and an env's reset (grid into buf0 keyed by (reset_seed, global env id, episode + 1),
+ * fire cell, position, counts; parity, accu, done, hit, steps_elapsed = 0; rng_step runs on, reward and steps stay)
+ * overlaps every other env's steps. An env that is done on entry takes the no-op step (reward 0) and is then reset.
+ * Per-step records, all nullable: action_out (K, E, 2) int32 the actions taken, unclamped; reward_out (K, E) f64 what
+ * step k leaves in `reward`; terminated_out / truncated_out (K, E) u8: under autoreset the flags the reset after step k
+ * saw (done, and the time limit reached without done), otherwise `done` after step k and zeros.
+ * autoreset == 0: reset_seed, max_steps, cdf, values, episode, last_length, terminated, truncated are not used (max_steps
+ * is ignored as gca_bulldozer_step_fused ignores it). autoreset != 0: cdf [3] f32, values [3] u8 (device arrays),
+ * episode and steps_elapsed are required; last_length (written for the envs that reset), terminated and truncated (the
+ * last step's flags, every env) are nullable. Same contract as gca_bulldozer_step_fused (W = 256 / 512, one CA pass at
+ * most per env step, empty = 0 < tree < fire, 16-B aligned buffers) and gca_bulldozer_reset_where (buf0 != buf1,
+ * H < 32768, max_steps >= 0, env_offset >= 0). K = 0 launches nothing. */
+int gca_bulldozer_rollout(const gca_bulldozer_params* p, const int32_t* actions, uint64_t action_seed, int K,
+                          int32_t* action_out, double* reward_out, uint8_t* terminated_out, uint8_t* truncated_out,
+                          int autoreset, uint64_t reset_seed, int64_t max_steps, const float* cdf,
+                          const uint8_t* values, uint32_t* episode, int64_t* last_length, uint8_t* terminated,
+                          uint8_t* truncated, double* accu, int32_t* steps, uint8_t* done, const double* wind,
+                          int64_t wind_stride, uint32_t* rng_step, uint8_t* parity, uint8_t* buf0, uint8_t* buf1, int H,
+                          int W, int32_t* pos, int32_t* counts, uint8_t* hit, double* reward, int64_t* steps_elapsed,
+                          int E, void* stream);
 
 /* Per-env reset of the batched ForestFireBulldozer env on the device, one launch, device pointers only (capturable):
  * the initial distribution of bulldozer.py:221-275 and the fresh-episode state of ca_env.py:64-81 for the selected envs.
