@@ -7,8 +7,9 @@
 // every row and the wave walks its tile top to bottom, one row per iteration, with every input of row r+1 in
 // flight while row r is computed. No LDS staging and no workgroup barrier (the tiled kernel spent 31 % of a wave's
 // life staging its halo and building the column prefix, profiles/r03i):
-//   fire ring   FIRE flags (0x01 bytes, one dword per row) of rows r-R-1 .. r+R;
-//   V_k         per column, the FIRE count of the 2k+1 rows around r: V_k += row r+k - row r-1-k per row;
+//   fire ring   FIRE flags (0x01 bytes, one dword per row) of rows r-R .. r+R;
+//   V_k         per column, the FIRE count of the 2k+1 rows around r, rebuilt in every row from the ring rows it has
+//               just read: V_k = V_{k-1} + row r+k + row r-k (one three-input add per radius, nothing carried);
 //   B_k         the (2k+1) x (2k+1) box sum = the (2k+1)-column window of V_k: v_dot4_u32_u8 of the lane's dword
 //               and its DPP neighbours (lanes l-2 .. l+2, wave_shr / wave_shl) against constant 0/1 byte masks;
 //   D_1, D_2    the same on the dousing flags (3 x 3 and 5 x 5 boxes, a ring of 6 rows);
@@ -80,6 +81,25 @@ __device__ __forceinline__ uint32_t from_prev_or(uint32_t old, uint32_t v) {
 }
 __device__ __forceinline__ uint32_t from_next_or(uint32_t old, uint32_t v) {
     return (uint32_t)__builtin_amdgcn_update_dpp((int)old, (int)v, 0x130, 0xF, 0xF, false);
+}
+
+// Lane masks (NSEG = 1): bit l of the 64-bit mask = byte J of lane l's flag dword is nonzero (one SDWA compare, the
+// mask in an SGPR pair), and the select that consumes one: c where the lane's bit is set, +0 elsewhere. Every lane is
+// active wherever the row loop runs (its branches are wave-uniform), so the masks are whole
+template <int J> __device__ __forceinline__ uint64_t byte_lanes(uint32_t x) {
+    static_assert(J >= 0 && J < 4, "byte 0..3");
+    uint64_t m;
+    const uint32_t zero = 0u;
+    if constexpr (J == 0) asm("v_cmp_ne_u32_sdwa %0, %1, %2 src0_sel:BYTE_0 src1_sel:DWORD" : "=s"(m) : "v"(x), "s"(zero));
+    if constexpr (J == 1) asm("v_cmp_ne_u32_sdwa %0, %1, %2 src0_sel:BYTE_1 src1_sel:DWORD" : "=s"(m) : "v"(x), "s"(zero));
+    if constexpr (J == 2) asm("v_cmp_ne_u32_sdwa %0, %1, %2 src0_sel:BYTE_2 src1_sel:DWORD" : "=s"(m) : "v"(x), "s"(zero));
+    if constexpr (J == 3) asm("v_cmp_ne_u32_sdwa %0, %1, %2 src0_sel:BYTE_3 src1_sel:DWORD" : "=s"(m) : "v"(x), "s"(zero));
+    return m;
+}
+__device__ __forceinline__ uint32_t lanes_select(uint32_t c, uint64_t m) {
+    uint32_t o;
+    asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(o) : "v"(c), "s"(m));
+    return o;
 }
 
 // byte mask of dword o (lane l+o, o in -2..2) inside the window of radius k around the lane's column j
@@ -236,8 +256,15 @@ __global__ __launch_bounds__(NSEG == 1 ? 256 : 64 * NSEG) __attribute__((amdgpu_
     const uint8_t* __restrict__ vd, const uint16_t* __restrict__ dbits, const float* __restrict__ es,
     const int32_t* __restrict__ wind_index, const uint32_t* __restrict__ rng_step, int32_t* __restrict__ counts,
     const uint8_t* __restrict__ act_in, uint8_t* __restrict__ act_out, MarchObs obs) {
-    constexpr int NF = 2 * R + 2;  // fire ring rows r-R-1 .. r+R
+    constexpr int NF = 2 * R + 1;  // fire ring rows r-R .. r+R
+    constexpr int RB = R;          // the ring's first row is r - RB; rw[RB] is row r
     constexpr bool HALO = NSEG > 1;
+    // the burning-neighbour masks as lane masks in SGPRs (dir_lanes below): the flat-terrain step without the frame,
+    // which has the 16 SGPRs to carry them. The general step and the fused-frame instances are at the SGPR limit
+    // already; with the masks they moved SGPRs through VGPR lanes inside the row loop (3 and 8 v_writelane /
+    // v_readlane per pass) and gained nothing (profiles/march_lanes/): they keep the byte masks, as the segments of
+    // a wider grid do
+    constexpr bool SMASK = !HALO && !OBS && FLATM >= 1;
     constexpr int WPB = HALO ? NSEG : 4;  // waves per workgroup: 4 independent tiles, or the NSEG segments of a strip
     constexpr int W = MW * NSEG;
     __shared__ float lut[WPB][16];
@@ -403,11 +430,11 @@ __global__ __launch_bounds__(NSEG == 1 ? 256 : 64 * NSEG) __attribute__((amdgpu_
     //      p_tree == 0, host-checked), otherwise from the rows themselves: two rows first (in a dense state they
     //      already hold a FIRE, so the check costs a few VALU), then the other 16 at once
     //      (r03ac: the episode's first steps, where most tiles are quiet, no longer run the full step on them)
-    // the fire ring's first rows (s0 - R - 1 .. s0 + R - 1) are loaded before the check, which reads two of them: a
+    // the fire ring's first rows (s0 - R .. s0 + R - 1) are loaded before the check, which reads two of them: a
     // dense tile pays no extra round trip
     uint32_t g_init[NF - 1];
 #pragma unroll
-    for (int t = 0; t < NF - 1; ++t) g_init[t] = graw(s0 - R - 1 + t);
+    for (int t = 0; t < NF - 1; ++t) g_init[t] = graw(s0 - RB + t);
     // a quiet tile: the input rows copied (grid, ages when not in place, the frame) and counted; row(i) gives row s0+i
     auto quiet_copy = [&](auto row) {
         int cE = 0, cT = 0;
@@ -450,9 +477,9 @@ __global__ __launch_bounds__(NSEG == 1 ? 256 : 64 * NSEG) __attribute__((amdgpu_
             const uint32_t v = x ^ Fp;
             return (v - 0x01010101u) & ~v & 0x80808080u;
         };
-        if (__ballot((has_fire(g_init[R]) | has_fire(g_init[R + 1])) != 0u) == 0ull) {  // rows s0 - 1, s0
+        if (__ballot((has_fire(g_init[RB - 1]) | has_fire(g_init[RB])) != 0u) == 0ull) {  // rows s0 - 1, s0
             uint32_t gq[SH];  // rows s0 .. s0+SH-1, kept for the copy (no second load round trip, r04)
-            gq[0] = g_init[R + 1];
+            gq[0] = g_init[RB];
             uint32_t f = has_fire(graw(s0 + SH));
 #pragma unroll
             for (int i = 1; i < SH; ++i) {
@@ -496,23 +523,25 @@ __global__ __launch_bounds__(NSEG == 1 ? 256 : 64 * NSEG) __attribute__((amdgpu_
         return;
     }
 
-    // ---- fire ring in LDS: the FIRE flags (0x01 bytes) of rows r-R-1 .. r+R, one dword per lane and row, each row
+    // ---- fire ring in LDS: the FIRE flags (0x01 bytes) of rows r-R .. r+R, one dword per lane and row, each row
     //      stored twice (slots t and t + NF), so that the rows around r sit at fixed offsets from one base that moves
     //      by one slot per row: immediate-offset ds_read_b32, no register rotation. Rows are stored in DESCENDING
     //      order (the base moves down one slot per row): the entering row sits at the base and its copy at base + NF,
     //      both immediate offsets off the address the reads use (ascending order put the copy at base - 1, which took
     //      a second per-lane address register and, in the fused-frame variant, a spill, r03p)
     uint32_t* FR = fring[wl];
-    auto ring_put = [&](int t, uint32_t v) {  // relative row t = row - (s0 - R - 1): slot NF - 1 - t (row 0's base)
+    auto ring_put = [&](int t, uint32_t v) {  // relative row t = row - (s0 - RB): slot NF - 1 - t (row 0's base)
         const int sl = (2 * NF - 2 - t) % NF;
         FR[sl * 64 + lane] = v;
         FR[(sl + NF) * 64 + lane] = v;
     };
 #pragma unroll
     for (int t = 0; t < NF - 1; ++t) ring_put(t, bytes_eq01(g_init[t], Fp));
-    uint32_t dring[6];
+    // dousing flags of rows r-DB .. r+2 (the 5-row sum's rows)
+    constexpr int DB = 2, ND = DB + 3;
+    uint32_t dring[ND];
 #pragma unroll
-    for (int t = 0; t < 5; ++t) dring[t] = dflags(draw_bits(s0 - 3 + t));
+    for (int t = 0; t < ND - 1; ++t) dring[t] = dflags(draw_bits(s0 - DB + t));
     // loads of row s0 (and the slopes of rows s0, s0+1)
     // row r's own codes are re-read one row ahead (nOwn) although the ring saw them R rows earlier: a per-wave LDS ring
     // of the codes instead cuts the traffic by 1.0 B / cell (26.2 -> 25.2) but measured 0.6-2 % slower (r03q/r03r)
@@ -535,16 +564,12 @@ __global__ __launch_bounds__(NSEG == 1 ? 256 : 64 * NSEG) __attribute__((amdgpu_
     xrow_publish(true, sc);  // (raw planes: prep_own below rewrites sc)
     // the tile below is the next wave of this workgroup, in the same env, and published its first row
     const bool xuse = XROW && wl < 3 && s0 + SH < H && xok[XROW ? wl + 1 : 0] != 0u;
-    uint32_t V[R + 1];
-#pragma unroll
-    for (int k = 1; k <= R; ++k) {
-        uint32_t v = 0u;
-#pragma unroll
-        for (int t = R - k; t <= R + k; ++t) v += FR[((2 * NF - 2 - t) % NF) * 64 + lane];
-        V[k] = v;
-    }
-    uint32_t Dv1 = dring[1] + dring[2] + dring[3];
-    uint32_t Dv2 = dring[0] + Dv1 + dring[4];
+    // the vertical sums V_k (FIRE flags of rows r-k .. r+k, per column) and Dv1 / Dv2 (dousing flags, 3 / 5 rows):
+    // rebuilt in every row from the ring rows it reads anyway, V_k = V_{k-1} + row r+k + row r-k (one three-input
+    // add per radius); nothing is carried from row to row (running sums V_k += row r+k - row r-1-k cost two adds per
+    // radius, one more ring row and an initialisation of 48 LDS reads per tile)
+    uint32_t V[R + 1] = {};
+    uint32_t Dv1 = 0u, Dv2 = 0u;
 
     // border columns 0 and W-1 (lanes 0 / 63 of the first / last segment, elements 0 / 3): slope factor 1 (the rows
     // 0 / H-1: kill_row below)
@@ -630,6 +655,13 @@ __global__ __launch_bounds__(NSEG == 1 ? 256 : 64 * NSEG) __attribute__((amdgpu_
     const float w_in_minus_bd = __fsub_rn(p.dous_inner, p.dous_border);
     const uint32_t codes = (p.empty & 0xFFu) | ((p.tree & 0xFFu) << 8) | ((p.fire & 0xFFu) << 16);
     int cntE = 0, cntT = 0, cntF = 0;
+    // SMASK: the lane masks of the FIRE flags of rows r-1 and r (see dir_lanes below), from the ring's first rows
+    uint64_t mP[4] = {}, mC[4] = {};
+    if constexpr (SMASK) {
+        const uint32_t fa = bytes_eq01(g_init[RB - 1], Fp), fb = bytes_eq01(g_init[RB], Fp);
+        mP[0] = byte_lanes<0>(fa); mP[1] = byte_lanes<1>(fa); mP[2] = byte_lanes<2>(fa); mP[3] = byte_lanes<3>(fa);
+        mC[0] = byte_lanes<0>(fb); mC[1] = byte_lanes<1>(fb); mC[2] = byte_lanes<2>(fb); mC[3] = byte_lanes<3>(fb);
+    }
     uint32_t out_row0 = 0u;  // OBS refit check: the new codes of row 0 (tile 0)
 
     // one row of the tile. SC: row r's planes (0..2 as prepared own factors, 3 raw); SN: row r+1's raw planes.
@@ -698,18 +730,30 @@ __global__ __launch_bounds__(NSEG == 1 ? 256 : 64 * NSEG) __attribute__((amdgpu_
         {
             uint32_t rw[NF];
 #pragma unroll
-            for (int t = 0; t < NF; ++t) rw[t] = Fb[(NF - 1 - t) * 64 + lane];  // rw[t] = row r-R-1+t
+            for (int t = 0; t < NF; ++t) rw[t] = Fb[(NF - 1 - t) * 64 + lane];  // rw[t] = row r-R+t
+            V[1] = rw[RB - 1] + rw[RB] + rw[RB + 1];
 #pragma unroll
-            for (int k = 1; k <= R; ++k) V[k] += rw[R + 1 + k] - rw[R - k];
-            fm1 = rw[R];
-            f0 = rw[R + 1];
-            fp1 = rw[R + 2];
+            for (int k = 2; k <= R; ++k) V[k] = V[k - 1] + rw[RB + k] + rw[RB - k];
+            fm1 = rw[RB - 1];
+            f0 = rw[RB];
+            fp1 = rw[RB + 1];
             if constexpr (R >= 3)
-                need_next = need_next && __ballot((rw[R + 1] | rw[R + 2] | rw[R + 3] | rw[R + 4]) != 0u) != 0ull;
+                need_next = need_next && __ballot((rw[RB] | rw[RB + 1] | rw[RB + 2] | rw[RB + 3]) != 0u) != 0ull;
         }
-        dring[5] = dflags(dnew);
-        Dv1 += dring[4] - dring[1];
-        Dv2 += dring[5] - dring[0];
+        dring[ND - 1] = dflags(dnew);  // row r+2
+        Dv1 = dring[1] + dring[2] + dring[3];
+        Dv2 = Dv1 + dring[0] + dring[4];
+        // lane masks of row r+1's FIRE flags, one per cell of the lane; rows r-1 and r are carried from the rows before.
+        // Taken where directions 5..7 first need them, when row r-1's masks are dead: 16 SGPRs of masks live, not 24
+        uint64_t mN[4] = {};
+        auto next_lanes = [&]() {
+            if constexpr (SMASK) {
+                mN[0] = byte_lanes<0>(fp1);
+                mN[1] = byte_lanes<1>(fp1);
+                mN[2] = byte_lanes<2>(fp1);
+                mN[3] = byte_lanes<3>(fp1);
+            }
+        };
 
         // ---- HALO: post this row's edge values for the neighbour segments, one barrier, and read theirs. xr / xr2:
         //      the neighbours' items (lane 0: left segment's lanes 63 / 62; lane 63: right segment's lanes 0 / 1).
@@ -763,6 +807,17 @@ __global__ __launch_bounds__(NSEG == 1 ? 256 : 64 * NSEG) __attribute__((amdgpu_
             asm volatile("" : "+v"(m));  // opaque: hipcc would fold the byte extractions into per-byte multiplies
             return m;
         };
+        // NSEG = 1: the same as lane masks, no VALU work. Cell j's neighbour in column offset dc is the row's cell
+        // j + dc of the same lane, or across the lane boundary cell 3 of lane l-1 (the mask shifted left one lane;
+        // lane 0 gets 0, the grid's border) / cell 0 of lane l+1 (shifted right; lane 63 gets 0). The segments of a
+        // wider grid keep the byte masks: their edge lanes take the flags of the neighbour segment (hfm1 / hf0 / hfp1)
+        auto dir_lanes = [&](int d, int j) -> uint64_t {
+            const uint64_t* m = d < 3 ? mP : (d < 5 ? mC : mN);
+            const int dc = d < 3 ? d - 1 : (d == 3 ? -1 : (d == 4 ? 1 : d - 6));
+            if (dc < 0) return j > 0 ? m[j - 1] : m[3] << 1;
+            if (dc > 0) return j < 3 ? m[j + 1] : m[0] >> 1;
+            return m[j];
+        };
         const uint32_t fireB = (f0 * 0x01020408u) >> 24;
         // a FIRE anywhere in the 3 x 3 block (the centre too: it only matters for TREE cells, which are not FIRE)
         const uint32_t vor = fm1 | f0 | fp1, hvor = hfm1 | hf0 | hfp1;
@@ -783,6 +838,7 @@ __global__ __launch_bounds__(NSEG == 1 ? 256 : 64 * NSEG) __attribute__((amdgpu_
             SN[k] = make_float4(col_lo ? 1.0f : oa.x, oa.y, ob.x, col_hi ? 1.0f : ob.y);
         };
         if (!row_need) {
+            next_lanes();
             if constexpr (!FLAT) {
                 load_next_slopes();
                 float unused[4];
@@ -871,7 +927,6 @@ __global__ __launch_bounds__(NSEG == 1 ? 256 : 64 * NSEG) __attribute__((amdgpu_
                     // hoisted (as in gca_alex.hip)
                     asm volatile("" : "+v"(ph[0]), "+v"(ph[1]), "+v"(qn[0]), "+v"(qn[1]));
                     const gca_f2 wd2 = bcast(windp[d >> 1], d & 1);
-                    const uint32_t Md = dir_mask(d);
                     // the two cell pairs' chains interleaved step by step (a packed f32 result read by the next
                     // instruction costs a wait state; two independent chains hide it)
                     // (KILL: every factor 1, so clamp01(base * wind) is the product's own clamp modifier -- one packed
@@ -890,10 +945,19 @@ __global__ __launch_bounds__(NSEG == 1 ? 256 : 64 * NSEG) __attribute__((amdgpu_
                     // qn <- fma(-qn, c, qn) = qn * (1 - c), one rounding (the oracle's order); no burning
                     // neighbour d: c -> +0 and qn is unchanged exactly (the oracle skips the factor)
                     uint32_t cm[2][2];
+                    if constexpr (SMASK) {
 #pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        cm[h][0] = __float_as_uint(c[h].x) & (uint32_t)(int32_t)(int8_t)(Md >> (16 * h));
-                        cm[h][1] = __float_as_uint(c[h].y) & (uint32_t)(int32_t)(int8_t)(Md >> (16 * h + 8));
+                        for (int h = 0; h < 2; ++h) {
+                            cm[h][0] = lanes_select(__float_as_uint(c[h].x), dir_lanes(d, 2 * h));
+                            cm[h][1] = lanes_select(__float_as_uint(c[h].y), dir_lanes(d, 2 * h + 1));
+                        }
+                    } else {
+                        const uint32_t Md = dir_mask(d);
+#pragma unroll
+                        for (int h = 0; h < 2; ++h) {
+                            cm[h][0] = __float_as_uint(c[h].x) & (uint32_t)(int32_t)(int8_t)(Md >> (16 * h));
+                            cm[h][1] = __float_as_uint(c[h].y) & (uint32_t)(int32_t)(int8_t)(Md >> (16 * h + 8));
+                        }
                     }
 #pragma unroll
                     for (int h = 0; h < 2; ++h)
@@ -932,6 +996,7 @@ __global__ __launch_bounds__(NSEG == 1 ? 256 : 64 * NSEG) __attribute__((amdgpu_
                     apply(4, a4);
                 }
                 if constexpr (!FLAT) load_next_slopes();
+                next_lanes();
                 float nb[4];
                 // plane 2 of (r+1, c-1): lane 0's first cell is column 0 (DPP old = 1.0)
                 if constexpr (!FLAT) prep_next(2, !KILL, nb);
@@ -1063,7 +1128,7 @@ __global__ __launch_bounds__(NSEG == 1 ? 256 : 64 * NSEG) __attribute__((amdgpu_
         __builtin_nontemporal_store(outw, reinterpret_cast<uint32_t*>(gO + o));
         { typedef uint32_t u2v __attribute__((ext_vector_type(2)));
           __builtin_nontemporal_store((u2v){nag[0], nag[1]}, reinterpret_cast<u2v*>(aO + o)); }
-        write_rgb_row(r, newT, newF, dring[3]);
+        write_rgb_row(r, newT, newF, dring[DB]);
         if constexpr (OBS && !HALO) {
             if (obs.refit && r < 2) {  // tile 0's rows 0 and 1 (wave-uniform)
                 if (r == 0) {
@@ -1079,7 +1144,14 @@ __global__ __launch_bounds__(NSEG == 1 ? 256 : 64 * NSEG) __attribute__((amdgpu_
         cntE += __builtin_popcount(newE);
 
 #pragma unroll
-        for (int t = 0; t < 5; ++t) dring[t] = dring[t + 1];
+        for (int t = 0; t < ND - 1; ++t) dring[t] = dring[t + 1];
+        if constexpr (SMASK) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                mP[j] = mC[j];
+                mC[j] = mN[j];
+            }
+        }
     };
 #pragma unroll 1
     for (int i = 0; i < SH; i += 2) {
