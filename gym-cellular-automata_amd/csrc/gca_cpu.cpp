@@ -15,6 +15,7 @@
 //   gca_helicopter_step  helicopter.py:220-236 + ca_env.py:27-48 (gca_heli.hip), the batched env step's twin
 //   gca_helicopter_rollout  K of those steps with per-step records (gca_heli.hip), the resident rollout's twin
 //   gca_bulldozer_reset_where  bulldozer.py:221-275 + ca_env.py:64-81 (gca_reset.hip), the per-env reset's twin
+//   gca_policy_observation  the batched envs' policy observation (gca_policy_obs.hip), pinned by tests/_policy_obs_ref.py
 //   gca_philox        Random123 Philox4x32-10 (KAT hook)
 #include <stdarg.h>
 #include <stdint.h>
@@ -415,6 +416,62 @@ extern "C" int gca_bulldozer_reset_where(const gca_bulldozer_params* p, uint64_t
         done[e] = 0;
         hit[e] = 0;
         steps_elapsed[e] = 0;
+    }
+    return GCA_OK;
+}
+
+// The policy observation of the batched envs (gca_policy_obs.hip) in plain loops. `form` is validated as the device
+// build validates it (alignment aside) and otherwise ignored.
+extern "C" int gca_policy_observation(const uint8_t* buf0, const uint8_t* buf1, const uint8_t* parity,
+                                      const int32_t* pos, int E, int H, int W, int empty, int tree, int fire, int radius,
+                                      int block, int form, uint8_t* local_out, float* coarse_out, void*) {
+    CPU_CHECK_ARG(buf0 && (buf1 || !parity), "policy_observation: buf0 required, and buf1 with parity");
+    CPU_CHECK_ARG(local_out || coarse_out, "policy_observation: local_out or coarse_out required");
+    CPU_CHECK_ARG(pos || !local_out, "policy_observation: local_out needs pos");
+    CPU_CHECK_ARG(E > 0 && H > 0 && W > 0, "policy_observation: E, H, W must be positive");
+    CPU_CHECK_ARG((int64_t)H * W < (1 << 30), "policy_observation: grid too large (H * W < 2^30)");
+    CPU_CHECK_ARG(((empty | tree | fire) & ~0xFF) == 0, "policy_observation: the codes must be u8 values");
+    CPU_CHECK_ARG(radius >= 0 && radius <= 31, "policy_observation: radius in [0, 31]");
+    CPU_CHECK_ARG(block >= 1 && block <= 64 && (block & (block - 1)) == 0,
+                  "policy_observation: block must be a power of two in [1, 64]");
+    CPU_CHECK_ARG(form >= 0 && form <= 2, "policy_observation: form 0 (by shape), 1 (generic) or 2 (rows)");
+    CPU_CHECK_ARG(form != 2 || ((W == 256 || W == 512) && (block == 8 || block == 16 || block == 32) && H % block == 0),
+                  "policy_observation: form 2 (rows) needs W = 256 / 512, block = 8 / 16 / 32 and H % block == 0");
+    const int64_t HW = (int64_t)H * W;
+    const int S = 2 * radius + 1, Hc = (H + block - 1) / block, Wc = (W + block - 1) / block;
+    const float inv = 1.0f / (float)(block * block);
+    for (int e = 0; e < E; ++e) {
+        const uint8_t* g = ((parity && parity[e]) ? buf1 : buf0) + e * HW;
+        if (local_out) {
+            uint8_t* out = local_out + (int64_t)e * S * S;
+            for (int i = 0; i < S; ++i)
+                for (int j = 0; j < S; ++j) {
+                    const int64_t r = (int64_t)pos[2 * e] - radius + i, c = (int64_t)pos[2 * e + 1] - radius + j;
+                    uint8_t cls = 3;
+                    if (r >= 0 && r < H && c >= 0 && c < W) {
+                        const int v = g[r * W + c];
+                        cls = v == tree ? 1 : (v == fire ? 2 : 0);
+                    }
+                    out[i * S + j] = cls;
+                }
+        }
+        if (coarse_out) {
+            float* C = coarse_out + (int64_t)e * 2 * Hc * Wc;
+            for (int bi = 0; bi < Hc; ++bi)
+                for (int bj = 0; bj < Wc; ++bj) {
+                    const int r1 = (bi + 1) * block < H ? (bi + 1) * block : H;
+                    const int c1 = (bj + 1) * block < W ? (bj + 1) * block : W;
+                    int32_t cT = 0, cF = 0;
+                    for (int r = bi * block; r < r1; ++r)
+                        for (int c = bj * block; c < c1; ++c) {
+                            const int v = g[(int64_t)r * W + c];
+                            cT += v == tree;
+                            cF += v == fire;
+                        }
+                    C[bi * Wc + bj] = (float)cT * inv;
+                    C[Hc * Wc + bi * Wc + bj] = (float)cF * inv;
+                }
+        }
     }
     return GCA_OK;
 }

@@ -233,6 +233,8 @@ _SIGNATURES = {
                              P, P, P, P, P, P, c_int, P], c_int),
     "gca_helicopter_rollout": ([c_int, c_int, c_int, c_int, c_uint64, c_int, P, c_uint64, c_int, P, P, P, P, P, P, P, P,
                                 P, c_int, c_int, P, P, P, P, P, c_int, P], c_int),
+    "gca_policy_observation": ([P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P],
+                               c_int),
     "gca_bench_copy": ([P, P, c_int64, c_int, P], c_int),
     "gca_bench_march_pattern": ([c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P], c_int),
 }
@@ -241,7 +243,7 @@ EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 # the subset libgca_cpu.so exports (tiny grids and the O(1)-per-env operators on host arrays)
 CPU_SYMBOLS = ("gca_last_error", "gca_version", "gca_philox", "gca_count_cells", "gca_move_modify",
                "gca_ds_count_draws", "gca_ds_step", "gca_helicopter_step", "gca_helicopter_rollout",
-               "gca_bulldozer_reset_where")
+               "gca_bulldozer_reset_where", "gca_policy_observation")
 
 _lib = None
 _lib_cpu = None

@@ -31,6 +31,7 @@ import numpy as np
 
 from ... import _device as dev
 from ..._lib import SLOT, BoundCall, call
+from .. import policy_obs
 from ..operators.move_modify import make_params
 from .bulldozer import ACTION_SETS, DEFAULT_WIND, bulldozer_timings, parse_wind
 
@@ -137,6 +138,7 @@ class BatchedForestFireBulldozerEnv:
         self._random_call = self._bound_meet_r = None
         self._reset_call = None
         self._rollout_call = None
+        self._observe_calls = {}
 
     # ------------------------------------------------------------------ state
     def grids(self):
@@ -194,6 +196,15 @@ class BatchedForestFireBulldozerEnv:
     def _obs(self):
         return (self.grids() if self.materialize_obs else None), self._ctx
 
+    def observe(self, radius=16, block=16, local_out=None, coarse_out=None, form=0):
+        """The policy observation of every env in one launch (gca_policy_observation, policy_obs.observe): `local`, uint8
+        (E, 2 radius + 1, 2 radius + 1), the classes of the cells around the bulldozer (0 other, 1 TREE, 2 FIRE, 3 outside
+        the grid), and `coarse`, float32 (E, 2, ceil(H / block), ceil(W / block)), the TREE and the FIRE share of every
+        block x block tile. Reads each env's current plane once: no grids() gather, no sync, and with both outputs given
+        (contiguous tensors of that dtype and shape on the env's device, written in place and returned) no allocation.
+        radius in [0, 31], block a power of two in [1, 64]; form 0 picks the kernel by shape."""
+        return policy_obs.observe(self, radius, block, local_out, coarse_out, form)
+
     def _action(self, action):
         """action as a contiguous int32 (E, 2) device tensor: the caller's own tensor when it is one (checked on every
         call: a tensor retyped or reshaped in place since the last step is converted, not misread), else converted
@@ -218,6 +229,7 @@ class BatchedForestFireBulldozerEnv:
         self._random_call = self._bound_meet_r = None
         self._reset_call = None
         self._rollout_call = None
+        self._observe_calls = {}
         self._views()
 
     def _views(self):

@@ -581,6 +581,27 @@ int gca_helicopter_rollout(int empty, int tree, int fire, int max_freeze, uint64
                            int32_t* pos, int32_t* counts, uint8_t* hit, double* reward, int64_t* steps_elapsed, int E,
                            void* stream);
 
+/* ------------------------------------------ policy observation of the batched envs (no reference counterpart)
+ * A compact observation of every env of a batched bulldozer / helicopter env, both parts in ONE launch that reads each
+ * env's current plane buf[parity[e]][e] (u8 [E][H][W]) once; pinned by the numpy restatement tests/_policy_obs_ref.py.
+ *   local_out  u8 [E][S][S], S = 2 radius + 1: entry (i, j) is the class of cell (pos[e][0] - radius + i,
+ *              pos[e][1] - radius + j): 1 the cell equals `tree`, 2 it equals `fire`, 0 any other in-grid cell, 3 outside
+ *              the grid. A position outside the grid is no error: the window is class 3 wherever it misses the grid.
+ *   coarse_out f32 [E][2][Hc][Wc], Hc = ceil(H / block), Wc = ceil(W / block): channel 0 the number of `tree` cells of
+ *              block (bi, bj) times 1 / block^2, channel 1 the same for `fire`; a block that sticks out of the grid
+ *              counts its in-grid cells only. Counts <= 4096 and the scale is a power of two: every value is exact.
+ * Classification is by equality with the codes (three values in [0, 255]) in every form. radius in [0, 31]; block a
+ * power of two in [1, 64]; H * W < 2^30. local_out or coarse_out may be NULL (that part is skipped; both NULL is an
+ * argument error). parity == NULL: every env reads buf0 (buf1 may then be NULL).
+ * form: 1 the generic form (any H, W, block); 2 the rows form, for W = 256 / 512, block = 8 / 16 / 32, H % block == 0
+ * and 8-B aligned planes (anything else is an argument error): a wave holds whole image rows, sums SWAR equality flags
+ * per byte over a block-row and adds them across the lanes of a block by DPP; 0 picks the rows form exactly when it
+ * applies. Both forms give the same bytes. One launch, no allocation, no sync, no atomics: capturable. The host build
+ * runs plain loops (`form` is validated the same way, alignment aside, and otherwise ignored). */
+int gca_policy_observation(const uint8_t* buf0, const uint8_t* buf1, const uint8_t* parity, const int32_t* pos, int E,
+                           int H, int W, int empty, int tree, int fire, int radius, int block, int form,
+                           uint8_t* local_out, float* coarse_out, void* stream);
+
 /* ------------------------------------------ measurement yardsticks (bench.py; no reference counterpart)
  * gca_bench_copy: a 16-B device copy of nbytes (one element per thread, one pass) (a multiple of 16, 16-B aligned), nt != 0 non-temporal
  * loads and stores: the practical HBM ceiling the bench reports beside the 8 TB/s spec.
