@@ -16,11 +16,16 @@
 //   gca_helicopter_rollout  K of those steps with per-step records (gca_heli.hip), the resident rollout's twin
 //   gca_bulldozer_reset_where  bulldozer.py:221-275 + ca_env.py:64-81 (gca_reset.hip), the per-env reset's twin
 //   gca_policy_observation  the batched envs' policy observation (gca_policy_obs.hip), pinned by tests/_policy_obs_ref.py
+//   gca_helicopter_policy_act / gca_helicopter_policy_rollout  the policy network and the closed-loop rollout
+//                     (gca_heli.hip, gca_heli_policy_dev.h), in gca.h's summation order
 //   gca_philox        Random123 Philox4x32-10 (KAT hook)
+#include <math.h>
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+
+#include <vector>
 
 #include "../../include/gca.h"
 
@@ -472,6 +477,149 @@ extern "C" int gca_policy_observation(const uint8_t* buf0, const uint8_t* buf1, 
                     C[Hc * Wc + bi * Wc + bj] = (float)cF * inv;
                 }
         }
+    }
+    return GCA_OK;
+}
+
+// ---------------------------------------------------------------- the helicopter policy (gca.h "helicopter policy")
+// exp_f32 of gca_common.h restated with C99 fmaf / rintf (round to nearest even, the default mode): every step is one
+// correctly rounded IEEE operation, so the bits are the device's.
+static inline float exp_f32_host(float x) {
+    x = fminf(fmaxf(x, -80.0f), 80.0f);
+    const float kf = rintf(x * 1.44269504088896341f);
+    const int k = (int)kf;
+    float r = fmaf(kf, -0.693145751953125f, x);
+    r = fmaf(kf, -1.42860682030941723212e-6f, r);
+    float p = 1.98412698412698413e-4f;
+    p = fmaf(p, r, 1.38888888888888889e-3f);
+    p = fmaf(p, r, 8.33333333333333333e-3f);
+    p = fmaf(p, r, 4.16666666666666667e-2f);
+    p = fmaf(p, r, 1.66666666666666667e-1f);
+    p = fmaf(p, r, 0.5f);
+    p = fmaf(p, r * r, r);
+    p = p + 1.0f;
+    uint32_t bits;
+    memcpy(&bits, &p, 4);
+    bits += (uint32_t)k << 23;
+    memcpy(&p, &bits, 4);
+    return p;
+}
+
+static int policy_check_host(const gca_heli_policy* p) {
+    CPU_CHECK_ARG(p && p->w_local && p->w_coarse && p->b1 && p->w_out && p->b2, "helicopter_policy: null weights");
+    CPU_CHECK_ARG(p->radius >= 0 && p->radius <= 31, "helicopter_policy: radius in [0, 31]");
+    CPU_CHECK_ARG(p->block >= 1 && p->block <= 64 && (p->block & (p->block - 1)) == 0,
+                  "helicopter_policy: block must be a power of two in [1, 64]");
+    CPU_CHECK_ARG(p->hidden >= 32 && p->hidden <= 256 && (p->hidden & (p->hidden - 1)) == 0,
+                  "helicopter_policy: hidden must be a power of two in [32, 256]");
+    return GCA_OK;
+}
+
+// One env's outputs and action in gca.h's order. loc [S*S], coarse [C]; out [10] receives the logits and the value.
+static int32_t policy_eval_host(const gca_heli_policy* p, int C, const uint8_t* loc, const float* coarse,
+                                uint32_t env_id, uint32_t rs, uint64_t policy_seed, int greedy, float* out) {
+    const int S = 2 * p->radius + 1, SS = S * S, N = SS + C, Hd = p->hidden, G = 1024 / Hd;
+    float h[256];
+    for (int j = 0; j < Hd; ++j) {
+        float hj = p->b1[j];
+        for (int g = 0; g < G; ++g) {
+            float acc = 0.0f;
+            for (int n = g; n < N; n += G) {
+                if (n < SS) acc = acc + p->w_local[((size_t)n * 4 + (loc[n] & 3)) * Hd + j];
+                else acc = acc + p->w_coarse[(size_t)(n - SS) * Hd + j] * coarse[n - SS];
+            }
+            hj = hj + acc;
+        }
+        h[j] = hj > 0.0f ? hj : 0.0f;
+    }
+    for (int o = 0; o < 10; ++o) {
+        float q[16];
+        for (int r = 0; r < 16; ++r) {
+            float acc = 0.0f;
+            for (int j = r; j < Hd; j += 16) acc = acc + p->w_out[j * 10 + o] * h[j];
+            q[r] = acc;
+        }
+        for (int half = 8; half >= 1; half >>= 1)
+            for (int r = 0; r < half; ++r) q[r] = q[r] + q[r + half];
+        out[o] = p->b2[o] + q[0];
+    }
+    float m = out[0];
+    int32_t first = 0;
+    for (int i = 1; i < 9; ++i)
+        if (out[i] > m) {
+            m = out[i];
+            first = i;
+        }
+    if (greedy) return first;
+    float c[9], s = 0.0f;
+    for (int i = 0; i < 9; ++i) {
+        s = s + exp_f32_host(out[i] - m);
+        c[i] = s;
+    }
+    const u32x4 x = philox4x32_10(u32x4{0u, env_id, rs, GCA_TAG_POLICY}, (uint32_t)policy_seed,
+                                  (uint32_t)(policy_seed >> 32));
+    const float t = ((float)(x.x >> 8) * 0x1.0p-24f) * c[8];
+    for (int i = 0; i < 8; ++i)
+        if (t < c[i]) return i;
+    return 8;
+}
+
+static void policy_act_host(const gca_heli_policy* p, int C, const uint8_t* local, const float* coarse,
+                            const uint32_t* rng_step, int env_offset, uint64_t policy_seed, int greedy,
+                            int32_t* action, float* logits, float* value, int E) {
+    const size_t SS = (size_t)(2 * p->radius + 1) * (2 * p->radius + 1);
+    for (int e = 0; e < E; ++e) {
+        float out[10];
+        action[e] = policy_eval_host(p, C, local + e * SS, coarse + (size_t)e * C, (uint32_t)(env_offset + e),
+                                     rng_step[e], policy_seed, greedy, out);
+        if (logits) memcpy(logits + (size_t)e * 9, out, 9 * sizeof(float));
+        if (value) value[e] = out[9];
+    }
+}
+
+extern "C" int gca_helicopter_policy_act(const gca_heli_policy* p, int C, const uint8_t* local, const float* coarse,
+                                         const uint32_t* rng_step, int env_offset, uint64_t policy_seed, int greedy,
+                                         int32_t* action, float* logits, float* value, int E, void*) {
+    if (const int st = policy_check_host(p)) return st;
+    CPU_CHECK_ARG(local && coarse && rng_step && action, "helicopter_policy_act: null argument");
+    CPU_CHECK_ARG(E > 0, "helicopter_policy_act: E > 0");
+    CPU_CHECK_ARG(C >= 2 && C % 2 == 0 && C <= 15088, "helicopter_policy_act: C = 2 Hc Wc, at most 15088");
+    policy_act_host(p, C, local, coarse, rng_step, env_offset, policy_seed, greedy, action, logits, value, E);
+    return GCA_OK;
+}
+
+// K x (observation, act, step) in plain loops, the records' rows written as they come; `scratch` is not needed here.
+extern "C" int gca_helicopter_policy_rollout(int empty, int tree, int fire, int max_freeze, uint64_t seed,
+                                             int env_offset, const gca_heli_policy* p, uint64_t policy_seed, int greedy,
+                                             int K, int32_t* action_out, float* logits_out, float* value_out,
+                                             double* reward_out, uint8_t* hit_out, uint8_t* local_out,
+                                             float* coarse_out, void*, const double* thresholds, int32_t* freeze,
+                                             uint32_t* rng_step, uint8_t* parity, uint8_t* buf0, uint8_t* buf1, int H,
+                                             int W, int32_t* pos, int32_t* counts, uint8_t* hit, double* reward,
+                                             int64_t* steps_elapsed, int E, void*) {
+    CPU_CHECK_HELI_ARGS("helicopter_policy_rollout");
+    CPU_CHECK_ARG(K >= 0, "helicopter_policy_rollout: K >= 0");
+    if (const int st = policy_check_host(p)) return st;
+    const int S = 2 * p->radius + 1, Hc = (H + p->block - 1) / p->block, Wc = (W + p->block - 1) / p->block;
+    CPU_CHECK_ARG(2 * (int64_t)Hc * Wc <= 15088, "helicopter_policy_rollout: coarse map too large");
+    const int C = 2 * Hc * Wc;
+    const size_t SS = (size_t)S * S;
+    std::vector<int32_t> act((size_t)E);
+    std::vector<uint8_t> loc((size_t)E * SS);
+    std::vector<float> coa((size_t)E * C);
+    for (int k = 0; k < K; ++k) {
+        const size_t o = (size_t)k * (size_t)E;
+        int32_t* act_k = action_out ? action_out + o : act.data();
+        uint8_t* loc_k = local_out ? local_out + o * SS : loc.data();
+        float* coa_k = coarse_out ? coarse_out + o * C : coa.data();
+        if (const int st = gca_policy_observation(buf0, buf1, parity, pos, E, H, W, empty, tree, fire, p->radius,
+                                                  p->block, 0, loc_k, coa_k, nullptr))
+            return st;
+        policy_act_host(p, C, loc_k, coa_k, rng_step, env_offset, policy_seed, greedy, act_k,
+                        logits_out ? logits_out + o * 9 : nullptr, value_out ? value_out + o : nullptr, E);
+        helicopter_step_host(empty, tree, fire, max_freeze, seed, env_offset, act_k, 0, nullptr, thresholds, freeze,
+                             rng_step, parity, buf0, buf1, H, W, pos, counts, hit, reward, steps_elapsed, E,
+                             reward_out ? reward_out + o : nullptr, hit_out ? hit_out + o : nullptr);
     }
     return GCA_OK;
 }

@@ -22,7 +22,12 @@
 // helicopter_rollout_kernel: a workgroup per env keeps both grid planes in LDS (4-byte pitch, EMPTY padding) and the
 // env's scalars in registers for the K steps, the CA pass in the strip's SWAR form on LDS dwords for any W; one barrier
 // per step, no atomics, no `meet`. Grids whose planes do not fit in 64 KiB run K launches of the step kernel instead.
+//
+// gca_helicopter_policy_rollout: the same resident rollout with the agent inside (heli_rollout_body<true>): every step
+// takes its action from a small policy network evaluated on that step's observation (gca_heli_policy_dev.h), four more
+// barriers per step; gca_helicopter_policy_act is that network alone, one workgroup per env, on a given observation.
 #include "gca_common.h"
+#include "gca_heli_policy_dev.h"
 
 namespace {
 
@@ -390,6 +395,86 @@ __device__ __forceinline__ void heli_r2g(uint8_t* __restrict__ g, int r, int d, 
         if (4 * d + j < W) g[cell0 + j] = (uint8_t)(v >> (8 * j));
 }
 
+// ---- the policy of gca_helicopter_policy_rollout: the network and the (K, E, ...) records only that rollout has
+struct HeliPolArgs {
+    HeliPolicyW w;
+    int radius, lgB, Hc, Wc;
+    float inv;  // 1 / block^2
+    float* logits_out;
+    float* value_out;
+    uint8_t* local_out;
+    float* coarse_out;
+};
+
+// Step k's action of env e in the resident rollout: gca_policy_observation's window and coarse map taken from the
+// current LDS plane at the position BEFORE the move, then the network (heli_policy_eval, three barriers). The window's
+// classes are read where they are needed and never staged; the coarse map goes to LDS (it is shared by all hidden
+// units). Rows -1 / H, the dword after a row and the columns >= W hold EMPTY, which is neither TREE nor FIRE, but the
+// loops below stay inside the grid's own rows and dwords anyway. Every thread returns the same action.
+__device__ __forceinline__ int32_t heli_rollout_policy_act(const HeliRollArgs& a, const HeliPolArgs& q,
+                                                           uint32_t* heli_lds, int p, int k, int e, int tid, int row,
+                                                           int col, uint32_t env_id, uint32_t rs, uint32_t Tp,
+                                                           uint32_t Fp) {
+    const int H = a.H, W = a.W, D = a.D, PD = D + 1, NP = a.plane_words;
+    const uint32_t* S = heli_lds + p * NP;
+    const uint8_t* Sb = reinterpret_cast<const uint8_t*>(S);
+    float* cs = reinterpret_cast<float*>(heli_lds + 2 * NP + 16);
+    float* part = cs + ((q.w.C + 3) & ~3);
+    float* hs = part + POL_PART;
+    float* outs = hs + POL_THREADS;
+    const size_t rec = (size_t)k * (size_t)a.E + (size_t)e;
+    const uint32_t tree = Tp & 0xFFu, fire = Fp & 0xFFu;
+    const int B = 1 << q.lgB, tiles = q.Hc * q.Wc;
+    for (int t = tid; t < tiles; t += HELI_THREADS) {
+        const int bi = t / q.Wc, bj = t - bi * q.Wc;
+        const int r0 = bi << q.lgB, r1 = min(H, r0 + B), c0 = bj << q.lgB;
+        int32_t cT = 0, cF = 0;
+        if (q.lgB >= 2) {  // a tile's columns are whole dwords of the plane
+            const int d0 = c0 >> 2, d1 = min(D, (c0 + B) >> 2);
+            for (int r = r0; r < r1; ++r)
+                for (int d = d0; d < d1; ++d) {
+                    const uint32_t x = S[1 + (r + 1) * PD + d];
+                    cT += __popc(bytes_eq01(x, Tp));
+                    cF += __popc(bytes_eq01(x, Fp));
+                }
+        } else {
+            const int c1 = min(W, c0 + B);
+            for (int r = r0; r < r1; ++r)
+                for (int cc = c0; cc < c1; ++cc) {
+                    const uint32_t v = Sb[4 * (1 + (r + 1) * PD) + cc];
+                    cT += v == tree;
+                    cF += v == fire;
+                }
+        }
+        const float fT = (float)cT * q.inv, fF = (float)cF * q.inv;
+        cs[t] = fT;
+        cs[tiles + t] = fF;
+        if (q.coarse_out) {
+            float* o = q.coarse_out + rec * (size_t)(2 * tiles);
+            o[t] = fT;
+            o[tiles + t] = fF;
+        }
+    }
+    const uint32_t wr0 = (uint32_t)row - (uint32_t)q.radius, wc0 = (uint32_t)col - (uint32_t)q.radius;
+    auto class_at = [&](int, int wi, int wj) -> uint32_t {
+        const uint32_t r = wr0 + (uint32_t)wi, cc = wc0 + (uint32_t)wj;
+        const bool in = r < (uint32_t)H && cc < (uint32_t)W;
+        const uint32_t v = Sb[in ? 4u * (1u + (r + 1u) * (uint32_t)PD) + cc : 0u];
+        return !in ? 3u : (v == tree ? 1u : (v == fire ? 2u : 0u));
+    };
+    if (q.local_out) {
+        uint8_t* o = q.local_out + rec * (size_t)q.w.SS;
+        for (int n = tid; n < q.w.SS; n += HELI_THREADS) {
+            const int wi = n / q.w.S;
+            o[n] = (uint8_t)class_at(n, wi, n - wi * q.w.S);
+        }
+    }
+    const int32_t act = heli_policy_eval(q.w, cs, part, hs, outs, tid, env_id, rs,
+                                         q.logits_out ? q.logits_out + rec * 9 : nullptr,
+                                         q.value_out ? q.value_out + rec : nullptr, class_at);
+    return __builtin_amdgcn_readfirstlane(act);
+}
+
 // One workgroup (4 waves) per env, K steps. LDS: two planes of PD = D + 1 dwords per row, rows -1 .. H, one leading
 // dword; cell (r, c) is byte c of dword 1 + (r + 1) * PD of its plane, and the dword after a row's D, rows -1 and H
 // and the columns >= W of a row's last dword hold EMPTY for the whole launch (never FIRE, never stored to), so every
@@ -401,7 +486,8 @@ __device__ __forceinline__ void heli_r2g(uint8_t* __restrict__ g, int r, int d, 
 // The K loop, the item loop inside a CA pass and the one barrier per step have the same trip count in every thread
 // (K, `iters`, K): the barrier stands outside every condition, no thread leaves early, nothing waits for another
 // workgroup.
-__global__ __launch_bounds__(HELI_THREADS) void helicopter_rollout_kernel(HeliRollArgs a) {
+template <bool POLICY>
+__device__ __forceinline__ void heli_rollout_body(const HeliRollArgs a, const HeliPolArgs* pa) {
     extern __shared__ __attribute__((aligned(16))) uint32_t heli_lds[];
     const int e = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int H = a.H, W = a.W, D = a.D, PD = D + 1, NP = a.plane_words, K = a.K;
@@ -449,7 +535,9 @@ __global__ __launch_bounds__(HELI_THREADS) void helicopter_rollout_kernel(HeliRo
     uint32_t rec_h = 0u;
     for (int k = 0; k < K; ++k) {
         int32_t act;
-        if (a.actions) {  // 64 steps' actions per load: lane l holds step (k & ~63) + l
+        if constexpr (POLICY) {
+            act = heli_rollout_policy_act(a, *pa, heli_lds, p, k, e, tid, row, col, env_id, rs, c.Tp, c.Fp);
+        } else if (a.actions) {  // 64 steps' actions per load: lane l holds step (k & ~63) + l
             if ((k & 63) == 0) chunk = k + lane < K ? a.actions[(size_t)(k + lane) * a.E + e] : 0;
             act = __builtin_amdgcn_readlane(chunk, k & 63);
         } else {  // column 0 of gca_random_actions
@@ -619,6 +707,36 @@ __global__ __launch_bounds__(HELI_THREADS) void helicopter_rollout_kernel(HeliRo
     a.steps_elapsed[e] += K;
 }
 
+// gca_helicopter_rollout's kernel: the caller's actions or the random policy
+__global__ __launch_bounds__(HELI_THREADS) void helicopter_rollout_kernel(HeliRollArgs a) {
+    heli_rollout_body<false>(a, nullptr);
+}
+// gca_helicopter_policy_rollout's: the same steps, the action of each from the policy network (a.actions is not read).
+// LDS after the planes and the waves' words: heli_policy_lds_words(C) words of the network.
+__global__ __launch_bounds__(HELI_THREADS) void helicopter_policy_rollout_kernel(HeliRollArgs a, HeliPolArgs pa) {
+    heli_rollout_body<true>(a, &pa);
+}
+
+// gca_helicopter_policy_act: one workgroup per env on the observation the caller hands over. A class above 3 (never
+// written by gca_policy_observation) is taken modulo 4, so no weight row outside w_local is ever read.
+__global__ __launch_bounds__(POL_THREADS) void helicopter_policy_act_kernel(
+    HeliPolicyW w, const uint8_t* __restrict__ local, const float* __restrict__ coarse,
+    const uint32_t* __restrict__ rng_step, int env_offset, int32_t* __restrict__ action, float* __restrict__ logits,
+    float* __restrict__ value) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t heli_lds[];
+    const int e = blockIdx.x, tid = threadIdx.x;
+    float* cs = reinterpret_cast<float*>(heli_lds);
+    float* part = cs + ((w.C + 3) & ~3);
+    float* hs = part + POL_PART;
+    float* outs = hs + POL_THREADS;
+    for (int c = tid; c < w.C; c += POL_THREADS) cs[c] = coarse[(size_t)e * (size_t)w.C + c];
+    const uint8_t* __restrict__ loc = local + (size_t)e * (size_t)w.SS;
+    const int32_t act = heli_policy_eval(w, cs, part, hs, outs, tid, (uint32_t)(env_offset + e), rng_step[e],
+                                         logits ? logits + (size_t)e * 9 : nullptr, value ? value + e : nullptr,
+                                         [&](int n, int, int) -> uint32_t { return (uint32_t)loc[n] & 3u; });
+    if (tid == 0) action[e] = act;
+}
+
 // LDS of the resident rollout: two planes and the waves' words, within the 64 KiB a launch gets by default
 bool heli_rollout_fits(int H, int W, int* D, int* plane_words, size_t* lds_bytes) {
     const int64_t d = ((int64_t)W + 3) / 4;
@@ -724,6 +842,141 @@ extern "C" int gca_helicopter_rollout(int empty, int tree, int fire, int max_fre
         if (fast) hipLaunchKernelGGL(helicopter_step_kernel<true>, grid, block, 0, (hipStream_t)stream, a);
         else hipLaunchKernelGGL(helicopter_step_kernel<false>, grid, block, 0, (hipStream_t)stream, a);
         GCA_CHECK_LAUNCH("helicopter_rollout");
+    }
+    return GCA_OK;
+}
+
+// ---------------------------------------------------------------- the helicopter policy (gca.h "helicopter policy")
+namespace {
+
+// the checks gca_helicopter_policy_act and gca_helicopter_policy_rollout share, and the device's view of the weights
+int heli_policy_check(const gca_heli_policy* p, int C, uint64_t policy_seed, int greedy, HeliPolicyW* w) {
+    GCA_CHECK_ARG(p && p->w_local && p->w_coarse && p->b1 && p->w_out && p->b2, "helicopter_policy: null weights");
+    GCA_CHECK_ARG((((uintptr_t)p->w_local | (uintptr_t)p->w_coarse) & 15u) == 0,
+                  "helicopter_policy: w_local and w_coarse must be 16-B aligned");
+    GCA_CHECK_ARG(p->radius >= 0 && p->radius <= 31, "helicopter_policy: radius in [0, 31]");
+    GCA_CHECK_ARG(p->block >= 1 && p->block <= 64 && (p->block & (p->block - 1)) == 0,
+                  "helicopter_policy: block must be a power of two in [1, 64]");
+    GCA_CHECK_ARG(p->hidden >= 32 && p->hidden <= 256 && (p->hidden & (p->hidden - 1)) == 0,
+                  "helicopter_policy: hidden must be a power of two in [32, 256]");
+    w->w_local = p->w_local; w->w_coarse = p->w_coarse; w->b1 = p->b1; w->w_out = p->w_out; w->b2 = p->b2;
+    w->S = 2 * p->radius + 1;
+    w->SS = w->S * w->S;
+    w->C = C;
+    w->Hd = p->hidden;
+    w->lgHd = 5;
+    while ((1 << w->lgHd) < p->hidden) ++w->lgHd;
+    w->greedy = greedy != 0;
+    w->k0 = (uint32_t)policy_seed;
+    w->k1 = (uint32_t)(policy_seed >> 32);
+    return GCA_OK;
+}
+
+}  // namespace
+
+extern "C" int gca_helicopter_policy_act(const gca_heli_policy* p, int C, const uint8_t* local, const float* coarse,
+                                         const uint32_t* rng_step, int env_offset, uint64_t policy_seed, int greedy,
+                                         int32_t* action, float* logits, float* value, int E, void* stream) {
+    HeliPolicyW w;
+    if (const int st = heli_policy_check(p, C, policy_seed, greedy, &w)) return st;
+    GCA_CHECK_ARG(local && coarse && rng_step && action, "helicopter_policy_act: null argument");
+    GCA_CHECK_ARG(E > 0, "helicopter_policy_act: E > 0");
+    GCA_CHECK_ARG(C >= 2 && C % 2 == 0 && (size_t)heli_policy_lds_words(C) * 4 <= 65536,
+                  "helicopter_policy_act: C = 2 Hc Wc, at most 15088");
+    hipLaunchKernelGGL(helicopter_policy_act_kernel, dim3((unsigned)E), dim3(POL_THREADS),
+                       (size_t)heli_policy_lds_words(C) * 4, (hipStream_t)stream, w, local, coarse, rng_step,
+                       env_offset, action, logits, value);
+    GCA_CHECK_LAUNCH("helicopter_policy_act");
+    return GCA_OK;
+}
+
+extern "C" int gca_helicopter_policy_rollout(int empty, int tree, int fire, int max_freeze, uint64_t seed,
+                                             int env_offset, const gca_heli_policy* p, uint64_t policy_seed, int greedy,
+                                             int K, int32_t* action_out, float* logits_out, float* value_out,
+                                             double* reward_out, uint8_t* hit_out, uint8_t* local_out,
+                                             float* coarse_out, void* scratch, const double* thresholds,
+                                             int32_t* freeze, uint32_t* rng_step, uint8_t* parity, uint8_t* buf0,
+                                             uint8_t* buf1, int H, int W, int32_t* pos, int32_t* counts, uint8_t* hit,
+                                             double* reward, int64_t* steps_elapsed, int E, void* stream) {
+    GCA_CHECK_ARG(thresholds && freeze && rng_step && parity && buf0 && buf1 && pos && counts && hit && reward &&
+                      steps_elapsed,
+                  "helicopter_policy_rollout: null argument");
+    GCA_CHECK_ARG(E > 0 && H > 0 && W > 0 && max_freeze >= 0,
+                  "helicopter_policy_rollout: E, H, W > 0 and max_freeze >= 0");
+    GCA_CHECK_ARG(K >= 0, "helicopter_policy_rollout: K >= 0");
+    GCA_CHECK_ARG(buf0 != buf1, "helicopter_policy_rollout: buf0 and buf1 must differ");
+    GCA_CHECK_ARG((int64_t)H * W < (1 << 30), "helicopter_policy_rollout: grid too large");
+    GCA_CHECK_ARG(((empty | tree | fire) & ~0xFF) == 0 && empty != tree && tree != fire && empty != fire,
+                  "helicopter_policy_rollout: three distinct u8 codes");
+    GCA_CHECK_ARG(p && p->block >= 1, "helicopter_policy_rollout: policy required");
+    const int Hc = (H + p->block - 1) / p->block, Wc = (W + p->block - 1) / p->block;
+    const int64_t C64 = 2 * (int64_t)Hc * Wc;
+    GCA_CHECK_ARG(C64 < (1 << 30), "helicopter_policy_rollout: coarse map too large");
+    const int C = (int)C64;
+    HeliPolArgs q;
+    if (const int st = heli_policy_check(p, C, policy_seed, greedy, &q.w)) return st;
+    if (K == 0) return GCA_OK;
+    const bool aligned = (((uintptr_t)buf0 | (uintptr_t)buf1) & 3u) == 0;
+    const dim3 grid((unsigned)E), block(HELI_THREADS);
+    int D = 0, plane_words = 0;
+    size_t lds_bytes = 0;
+    if (heli_rollout_fits(H, W, &D, &plane_words, &lds_bytes) &&
+        lds_bytes + (size_t)heli_policy_lds_words(C) * 4 <= 65536) {
+        HeliRollArgs a;
+        a.empty = empty; a.tree = tree; a.fire = fire; a.max_freeze = max_freeze;
+        a.seed = seed; a.action_seed = 0; a.env_offset = env_offset; a.K = K; a.E = E;
+        a.actions = nullptr; a.action_out = action_out; a.reward_out = reward_out; a.hit_out = hit_out;
+        a.thr = thresholds; a.freeze = freeze; a.rng_step = rng_step; a.parity = parity; a.buf0 = buf0; a.buf1 = buf1;
+        a.H = H; a.W = W; a.D = D; a.plane_words = plane_words; a.dwords = (W % 4 == 0 && aligned) ? 1 : 0;
+        a.pos = pos; a.counts = counts; a.hit = hit; a.reward = reward; a.steps_elapsed = steps_elapsed;
+        q.radius = p->radius;
+        q.lgB = 0;
+        while ((1 << q.lgB) < p->block) ++q.lgB;
+        q.Hc = Hc; q.Wc = Wc;
+        q.inv = 1.0f / (float)(p->block * p->block);
+        q.logits_out = logits_out; q.value_out = value_out; q.local_out = local_out; q.coarse_out = coarse_out;
+        hipLaunchKernelGGL(helicopter_policy_rollout_kernel, grid, block,
+                           lds_bytes + (size_t)heli_policy_lds_words(C) * 4, (hipStream_t)stream, a, q);
+        GCA_CHECK_LAUNCH("helicopter_policy_rollout");
+        return GCA_OK;
+    }
+    // The planes and the network's words do not fit in LDS: K x (observation, act, step) launches. A step's action, window
+    // and coarse map go to their record rows, or to `scratch` where the caller keeps no such record.
+    const size_t SS = (size_t)q.w.SS;
+    GCA_CHECK_ARG(scratch || (action_out && local_out && coarse_out),
+                  "helicopter_policy_rollout: this shape runs K x 3 launches and needs `scratch` for the records not kept");
+    GCA_CHECK_ARG((size_t)heli_policy_lds_words(C) * 4 <= 65536, "helicopter_policy_rollout: coarse map too large");
+    int32_t* s_act = (int32_t*)scratch;
+    float* s_coarse = (float*)scratch + E;
+    uint8_t* s_local = (uint8_t*)(s_coarse + (size_t)E * C);
+    const bool fast = W % 256 == 0 && aligned;
+    HeliArgs a;
+    a.empty = empty; a.tree = tree; a.fire = fire; a.max_freeze = max_freeze;
+    a.seed = seed; a.action_seed = 0; a.env_offset = env_offset;
+    a.thr = thresholds; a.freeze = freeze; a.rng_step = rng_step;
+    a.parity = parity; a.buf0 = buf0; a.buf1 = buf1; a.H = H; a.W = W; a.pos = pos; a.counts = counts; a.hit = hit;
+    a.reward = reward; a.steps_elapsed = steps_elapsed;
+    a.meet = nullptr;
+    a.P = 1;
+    a.action_out = nullptr;
+    for (int k = 0; k < K; ++k) {
+        const size_t o = (size_t)k * (size_t)E;
+        int32_t* act_k = action_out ? action_out + o : s_act;
+        uint8_t* loc_k = local_out ? local_out + o * SS : s_local;
+        float* coa_k = coarse_out ? coarse_out + o * (size_t)C : s_coarse;
+        if (const int st = gca_policy_observation(buf0, buf1, parity, pos, E, H, W, empty, tree, fire, p->radius,
+                                                  p->block, 0, loc_k, coa_k, stream))
+            return st;
+        hipLaunchKernelGGL(helicopter_policy_act_kernel, grid, dim3(POL_THREADS), (size_t)heli_policy_lds_words(C) * 4,
+                           (hipStream_t)stream, q.w, loc_k, coa_k, rng_step, env_offset, act_k,
+                           logits_out ? logits_out + o * 9 : nullptr, value_out ? value_out + o : nullptr);
+        GCA_CHECK_LAUNCH("helicopter_policy_rollout");
+        a.action = act_k;
+        a.rec_reward = reward_out ? reward_out + o : nullptr;
+        a.rec_hit = hit_out ? hit_out + o : nullptr;
+        if (fast) hipLaunchKernelGGL(helicopter_step_kernel<true>, grid, block, 0, (hipStream_t)stream, a);
+        else hipLaunchKernelGGL(helicopter_step_kernel<false>, grid, block, 0, (hipStream_t)stream, a);
+        GCA_CHECK_LAUNCH("helicopter_policy_rollout");
     }
     return GCA_OK;
 }

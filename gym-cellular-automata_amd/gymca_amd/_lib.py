@@ -32,6 +32,7 @@ GCA_PINE_MAX = 8
 GCA_PINE_CDF = 17
 TAG_PINEC = 0x50434C00
 TAG_PINEC_AGE = 0x50434C41
+TAG_POLICY = 0x504F4C49
 GCA_PINEC_NMAX = 16
 GCA_PINEC_CDF = 48
 GCA_PINEC_LDS_MAX_HW = 262144
@@ -170,6 +171,22 @@ class ObsParams(ctypes.Structure):
     ]
 
 
+class HeliPolicy(ctypes.Structure):
+    """gca_heli_policy (include/gca.h): the dims and the five weight arrays' device (host build: host) addresses."""
+
+    _fields_ = [
+        ("radius", c_int32),
+        ("block", c_int32),
+        ("hidden", c_int32),
+        ("reserved", c_int32),
+        ("w_local", c_void_p),
+        ("w_coarse", c_void_p),
+        ("b1", c_void_p),
+        ("w_out", c_void_p),
+        ("b2", c_void_p),
+    ]
+
+
 P = c_void_p  # device pointers travel as plain addresses
 _SIGNATURES = {
     "gca_last_error": ([], ctypes.c_char_p),
@@ -235,6 +252,11 @@ _SIGNATURES = {
                                 P, c_int, c_int, P, P, P, P, P, c_int, P], c_int),
     "gca_policy_observation": ([P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P],
                                c_int),
+    "gca_helicopter_policy_act": ([POINTER(HeliPolicy), c_int, P, P, P, c_int, c_uint64, c_int, P, P, P, c_int, P],
+                                  c_int),
+    "gca_helicopter_policy_rollout": ([c_int, c_int, c_int, c_int, c_uint64, c_int, POINTER(HeliPolicy), c_uint64,
+                                       c_int, c_int, P, P, P, P, P, P, P, P, P, P, P, P, P, P, c_int, c_int, P, P, P, P,
+                                       P, c_int, P], c_int),
     "gca_bench_copy": ([P, P, c_int64, c_int, P], c_int),
     "gca_bench_march_pattern": ([c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P], c_int),
 }
@@ -243,7 +265,8 @@ EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 # the subset libgca_cpu.so exports (tiny grids and the O(1)-per-env operators on host arrays)
 CPU_SYMBOLS = ("gca_last_error", "gca_version", "gca_philox", "gca_count_cells", "gca_move_modify",
                "gca_ds_count_draws", "gca_ds_step", "gca_helicopter_step", "gca_helicopter_rollout",
-               "gca_bulldozer_reset_where", "gca_policy_observation")
+               "gca_bulldozer_reset_where", "gca_policy_observation", "gca_helicopter_policy_act",
+               "gca_helicopter_policy_rollout")
 
 _lib = None
 _lib_cpu = None

@@ -1,4 +1,5 @@
 from .batched import BatchedForestFireHelicopterEnv
 from .helicopter import ForestFireHelicopterEnv
+from .policy import HelicopterPolicy
 
-__all__ = ["ForestFireHelicopterEnv", "BatchedForestFireHelicopterEnv"]
+__all__ = ["ForestFireHelicopterEnv", "BatchedForestFireHelicopterEnv", "HelicopterPolicy"]

@@ -3,7 +3,9 @@
 The batched form of helicopter.py's MDP (reference helicopter.py:220-236 + ca_env.py:27-48). gca_helicopter_step
 does the whole step of every env: the action (the caller's, or drawn inside the step), Move, the Drossel–Schwabl CA
 when the env's freeze countdown is 0, Modify {FIRE: EMPTY} at the moved position, freeze, cell counts and reward.
-rollout(actions) runs K such steps in one launch (gca_helicopter_rollout: the env's grid stays in LDS between steps).
+rollout(actions) runs K such steps in one launch (gca_helicopter_rollout: the env's grid stays in LDS between steps);
+rollout_policy(policy, K) closes the loop inside that launch: a HelicopterPolicy (policy.py) picks every step's action
+from that step's observation (gca_helicopter_policy_rollout), and act(policy) is the same network as one launch.
 
 Grids live in two buffers; env e's current grid is buf[parity[e]][e], so an env whose countdown is still running
 moves no bytes beyond the one cell Modify may patch. The CA's draws are Philox keyed by (cell, global env id,
@@ -185,6 +187,7 @@ class BatchedForestFireHelicopterEnv:
         self._sample_call = None
         self._rollout_call = None
         self._observe_calls = {}
+        self._policy_calls = {}
         self._info = {"hit": self.hit}
         self._ctx = {"ca_params": self.ca_params, "position": self.pos, "freeze": self.freeze}
 
@@ -310,6 +313,129 @@ class BatchedForestFireHelicopterEnv:
            None if action_out is None else action_out.data_ptr(), reward_out.data_ptr(), hit_out.data_ptr(),
            dev.raw_stream(self._dev_index))
         return reward_out, hit_out
+
+    # ------------------------------------------------------------------ the policy inside the env's launches
+    def _check_policy(self, policy, who):
+        from .policy import HelicopterPolicy
+
+        if not isinstance(policy, HelicopterPolicy):
+            raise ValueError(f"{who}: policy must be a HelicopterPolicy")
+        if policy.shape != (self.nrows, self.ncols):
+            raise ValueError(f"{who}: the policy was built for a {policy.shape} grid, the env is "
+                             f"{(self.nrows, self.ncols)}")
+        if policy.device != self.device:
+            raise ValueError(f"{who}: the policy lives on {policy.device}, the env on {self.device}")
+        return policy
+
+    def _check_tensor(self, out, dtype, shape, who, what):
+        import torch
+
+        if not (type(out) is torch.Tensor and out.dtype is dtype and out.get_device() == self._dev_index
+                and tuple(out.shape) == tuple(shape) and out.is_contiguous()):
+            raise ValueError(f"{who}: {what} must be a contiguous {str(dtype).replace('torch.', '')} {tuple(shape)} "
+                             "tensor on the env's device")
+        return out
+
+    def _policy_call(self, kind, policy, make):
+        """The pre-bound call of `kind` for this policy; bound again when a policy tensor was replaced (its version
+        moved) or the env rebound. The entry keeps the policy's tensors of that version alive."""
+        key = (kind, id(policy))
+        pc = self._policy_calls.get(key)
+        if pc is None or pc[0] != policy.version or pc[1] is not policy:
+            pc = self._policy_calls[key] = (policy.version, policy) + tuple(make())
+        return pc
+
+    def act(self, policy, local=None, coarse=None, seed=0, greedy=False, action_out=None, logits_out=None,
+            value_out=None):
+        """The policy's action for every env: observe(policy.radius, policy.block) unless both `local` and `coarse` are
+        given (tensors of observe's dtypes and shapes), then ONE launch of the network (gca_helicopter_policy_act).
+        Returns (action int32 (E,), logits float32 (E, 9), value float32 (E,)), written into the given outputs or
+        allocated. The draw is keyed by (seed, global env id, the env's rng_step); greedy=True takes the first maximum
+        instead. No env state changes, so the value of the state after a rollout is free of side effects. No sync."""
+        import torch
+
+        policy = self._check_policy(policy, "act")
+        E = self.num_envs
+        ls, cs = policy_obs.output_shapes(self, policy.radius, policy.block)
+        if (local is None) != (coarse is None):
+            raise ValueError("act: give both local and coarse, or neither")
+        if local is None:
+            local, coarse = self.observe(policy.radius, policy.block)
+        else:
+            self._check_tensor(local, torch.uint8, ls, "act", "local")
+            self._check_tensor(coarse, torch.float32, cs, "act", "coarse")
+        kw = dict(device=self.device)
+        action_out = torch.empty(E, dtype=torch.int32, **kw) if action_out is None else \
+            self._check_tensor(action_out, torch.int32, (E,), "act", "action_out")
+        logits_out = torch.empty((E, 9), dtype=torch.float32, **kw) if logits_out is None else \
+            self._check_tensor(logits_out, torch.float32, (E, 9), "act", "logits_out")
+        value_out = torch.empty(E, dtype=torch.float32, **kw) if value_out is None else \
+            self._check_tensor(value_out, torch.float32, (E,), "act", "value_out")
+        pc = self._policy_call("act", policy, lambda: (BoundCall(
+            "gca_helicopter_policy_act", policy.struct, policy.C, SLOT, SLOT, dev.ptr(self.rng_step), self.env_offset,
+            SLOT, SLOT, SLOT, SLOT, SLOT, E, SLOT, keep=(self.rng_step,) + policy.tensors()),))
+        pc[2](local.data_ptr(), coarse.data_ptr(), int(seed) & (2**64 - 1), 1 if greedy else 0, action_out.data_ptr(),
+              logits_out.data_ptr(), value_out.data_ptr(), dev.raw_stream(self._dev_index))
+        return action_out, logits_out, value_out
+
+    _POLICY_RECORDS = ("action", "logits", "value", "reward", "hit", "local", "coarse")
+
+    def rollout_policy(self, policy, K, seed=0, greedy=False, record=_POLICY_RECORDS, action_out=None,
+                       logits_out=None, value_out=None, reward_out=None, hit_out=None, local_out=None,
+                       coarse_out=None):
+        """K closed-loop env steps of every env in one call: bit for bit K x (observe(policy.radius, policy.block),
+        act(policy, seed=seed, greedy=greedy), step(action)) -- a PPO collection loop's on-policy experience. Returns a
+        dict of the records named in `record` (and of every record whose output tensor is given), row k what step k
+        saw and did: action int32 (K, E), logits float32 (K, E, 9), value float32 (K, E), reward float64 (K, E), hit uint8
+        (K, E), local uint8 (K, E, S, S), coarse float32 (K, E, 2, Hc, Wc); step k's observation is of the state before
+        step k. Given outputs must be contiguous tensors of that dtype and shape on the env's device. Afterwards the env
+        is in the state the K steps leave, so step / rollout / rollout_policy interleave freely. Where the grid's two
+        planes and the network's scratch fit in LDS all of it is ONE launch (gca_helicopter_policy_rollout), other shapes
+        run 3 K launches with the same results; no sync either way."""
+        import torch
+
+        policy = self._check_policy(policy, "rollout_policy")
+        K = int(K)
+        if K < 0:
+            raise ValueError("rollout_policy: K >= 0")
+        E = self.num_envs
+        ls, cs = policy_obs.output_shapes(self, policy.radius, policy.block)
+        spec = {"action": (torch.int32, (K, E)), "logits": (torch.float32, (K, E, 9)),
+                "value": (torch.float32, (K, E)), "reward": (torch.float64, (K, E)), "hit": (torch.uint8, (K, E)),
+                "local": (torch.uint8, (K,) + ls), "coarse": (torch.float32, (K,) + cs)}
+        unknown = [r for r in record if r not in spec]
+        if unknown:
+            raise ValueError(f"rollout_policy: unknown records {unknown}; choose from {self._POLICY_RECORDS}")
+        given = {"action": action_out, "logits": logits_out, "value": value_out, "reward": reward_out, "hit": hit_out,
+                 "local": local_out, "coarse": coarse_out}
+        recs = {}
+        for name in self._POLICY_RECORDS:
+            dtype, shape = spec[name]
+            if given[name] is not None:
+                recs[name] = self._check_tensor(given[name], dtype, shape, "rollout_policy", f"{name}_out")
+            elif name in record:
+                recs[name] = torch.empty(shape, dtype=dtype, device=self.device)
+        if K == 0:
+            return recs
+
+        def make():
+            H, W = self.nrows, self.ncols
+            # the K x 3 launch path keeps a step's action / window / coarse map here when the caller keeps no record
+            scratch = torch.empty(E * (4 + 4 * policy.C + policy.S * policy.S), dtype=torch.uint8, device=self.device)
+            return BoundCall(
+                "gca_helicopter_policy_rollout", self._empty, self._tree, self._fire, self.max_freeze,
+                self.seed_value & (2**64 - 1), self.env_offset, policy.struct, SLOT, SLOT, SLOT, SLOT, SLOT, SLOT, SLOT,
+                SLOT, SLOT, SLOT, dev.ptr(scratch), dev.ptr(self.thresholds), dev.ptr(self.freeze),
+                dev.ptr(self.rng_step), dev.ptr(self.parity), dev.ptr(self.buf[0]), dev.ptr(self.buf[1]), H, W,
+                dev.ptr(self.pos), dev.ptr(self.counts), dev.ptr(self.hit), dev.ptr(self.reward),
+                dev.ptr(self.steps_elapsed), E, SLOT,
+                keep=self._bound_tensors() + policy.tensors() + (scratch,)),
+
+        pc = self._policy_call("rollout", policy, make)
+        p = lambda name: recs[name].data_ptr() if name in recs else None
+        pc[2](int(seed) & (2**64 - 1), 1 if greedy else 0, K, p("action"), p("logits"), p("value"), p("reward"),
+              p("hit"), p("local"), p("coarse"), dev.raw_stream(self._dev_index))
+        return recs
 
     def sample_actions(self, out=None, tag=9):
         """Uniform random actions in [0, 9) for every env on the device -- the batched `action_space.sample()`: column

@@ -46,6 +46,7 @@ extern "C" {
 #define GCA_TAG_HIDDEN_CELL 0x48494443u /* 'HIDC' : per-cell hidden-layer draws          */
 #define GCA_TAG_PINEC      0x50434C00u /* 'PCL\0' (+1+m): classic pinecone count / pinecone m */
 #define GCA_TAG_PINEC_AGE  0x50434C41u /* 'PCLA' : age of a classic pinecone ignition        */
+#define GCA_TAG_POLICY     0x504F4C49u /* 'POLI' : the helicopter policy's action draw          */
 
 /* ------------------------------------------------------------------ generic */
 
@@ -601,6 +602,72 @@ int gca_helicopter_rollout(int empty, int tree, int fire, int max_freeze, uint64
 int gca_policy_observation(const uint8_t* buf0, const uint8_t* buf1, const uint8_t* parity, const int32_t* pos, int E,
                            int H, int W, int empty, int tree, int fire, int radius, int block, int form,
                            uint8_t* local_out, float* coarse_out, void* stream);
+
+/* ------------------------------------------ helicopter policy (the agent of the reference's PPO collection loop,
+ * agents/jax_ppo.py:866-899: observe, network, softmax sample, step, record -- here inside the env's own launches)
+ * A two-layer MLP over gca_policy_observation(radius, block)'s tensors. S = 2 radius + 1, C = 2 Hc Wc, Hd = hidden, a
+ * power of two in [32, 256]. All f32; every multiply and every add below is rounded on its own (no fma).
+ *   inputs   term n, n = 0 .. S*S + C - 1:  n < S*S:  t_n[j] = w_local[n][local_n][j]  (a table lookup, no multiply;
+ *            local_n the class 0..3 of window cell n, row-major; a class above 3 counts modulo 4)
+ *            n >= S*S: t_n[j] = w_coarse[c][j] * coarse_c, c = n - S*S (coarse flattened (2, Hc, Wc) row-major)
+ *   hidden   G = 1024 / Hd groups. p_g[j] = ((0 + t_g[j]) + t_{g+G}[j]) + t_{g+2G}[j] + ...: group g's terms in
+ *            increasing n, left to right, starting from 0.0f (a group without terms is 0.0f).
+ *            h_j = relu(((b1[j] + p_0[j]) + p_1[j]) + ... + p_{G-1}[j]), relu(x) = x > 0 ? x : 0.
+ *   heads    out_o, o = 0..9: q_r = ((0 + w_out[r][o] * h_r) + w_out[r+16][o] * h_{r+16}) + ..., r = 0..15 (j = r,
+ *            r + 16, ... < Hd, left to right from 0.0f); then the pairwise tree a_r = q_r + q_{r+8} (r < 8),
+ *            b_r = a_r + a_{r+4} (r < 4), c_r = b_r + b_{r+2} (r < 2), d = c_0 + c_1; out_o = b2[o] + d.
+ *            Outputs 0..8 are the action logits l_i, output 9 is the value.
+ *   sampling m = l_0, then for i = 1..8: if l_i > m then m = l_i (the first maximum). greedy != 0: the action is the
+ *            index of that first maximum, nothing is drawn. Otherwise p_i = exp_f32(l_i - m) (the deterministic expf of
+ *            DESIGN.md), c_i = c_{i-1} + p_i for i = 0..8 (c_{-1} = 0.0f), u = u01_f32(x.x) of Philox((0, env_offset +
+ *            e, rng_step[e], GCA_TAG_POLICY), policy_seed); the action is the first i with u * c_8 < c_i, else 8.
+ *            Non-finite weights still give an action in [0, 8]; nothing else is promised for them.
+ * The order depends on (S, C, Hd) only: never on E, K, the launch shape or the path that runs. The device (one 256-thread
+ * workgroup per env: a thread owns four consecutive units, Hd / 4 threads a weight row, which leaves the G groups; 16
+ * lanes per output meet in an xor butterfly), the host build and the numpy restatement
+ * tests/_helicopter_policy_ref.py all follow it, so they agree bit for bit.
+ * Layouts: w_local f32 [S*S][4][Hd] and w_coarse f32 [C][Hd] (both 16-B aligned on the device), b1 f32 [Hd], w_out
+ * f32 [Hd][10], b2 f32 [10] (device arrays; the struct itself is a host struct read at call time). */
+typedef struct {
+    int32_t radius, block;     /* gca_policy_observation's: radius in [0, 31], block a power of two in [1, 64] */
+    int32_t hidden;            /* Hd                                                                            */
+    int32_t reserved;          /* 0                                                                             */
+    const float* w_local;
+    const float* w_coarse;
+    const float* b1;
+    const float* w_out;
+    const float* b2;
+} gca_heli_policy;
+
+/* The policy's action for E envs on a given observation, ONE launch (a workgroup per env), no allocation, no sync:
+ * capturable. local u8 [E][S][S] and coarse f32 [E][C] as gca_policy_observation writes them (C = 2 Hc Wc is given; the
+ * network has no other use for the grid's shape and p->block is not read). Writes action i32 [E], logits f32 [E][9]
+ * (nullable) and value f32 [E] (nullable). No env state changes: rng_step is read only, so the value of the state after
+ * a rollout (the bootstrap) is free of side effects. C even, and small enough for the coarse map in LDS (C <= 15088). */
+int gca_helicopter_policy_act(const gca_heli_policy* p, int C, const uint8_t* local, const float* coarse,
+                              const uint32_t* rng_step, int env_offset, uint64_t policy_seed, int greedy,
+                              int32_t* action, float* logits, float* value, int E, void* stream);
+
+/* K closed-loop env steps of E envs: bit for bit K x (gca_policy_observation(p->radius, p->block) of the state before the
+ * step -- the position before the move, the current plane after the previous step --, gca_helicopter_policy_act on it,
+ * gca_helicopter_step with that action). The arguments are gca_helicopter_rollout's with the actions replaced by the
+ * policy. Records, each nullable, row k = what step k saw and did: action_out i32 (K, E), logits_out f32 (K, E, 9),
+ * value_out f32 (K, E), reward_out f64 (K, E), hit_out u8 (K, E), local_out u8 (K, E, S, S), coarse_out f32
+ * (K, E, 2, Hc, Wc). The state tensors afterwards are those of the K x 3 calls.
+ * Where the two LDS planes of gca_helicopter_rollout plus 4 * (C rounded up to 4 + 1296) bytes of the network fit in
+ * 64 KiB, everything runs in ONE launch: the window and the block counts come from the LDS plane, the hidden partials
+ * and the outputs live in LDS, the weights are read from global memory; five barriers per step. Other shapes run the
+ * K x 3 launches on the stream with the same results; they keep a step's action, window and coarse map in the record
+ * rows, or, for a record the caller does not keep, in `scratch`: E * (4 + 4 C + S*S) bytes of device memory, 4-byte
+ * aligned (nullable when the three records are given or the shape is resident; pass it always to be shape-agnostic).
+ * Launches only: capturable. K == 0 is a no-op, K < 0 and every other argument error is reported before any launch. */
+int gca_helicopter_policy_rollout(int empty, int tree, int fire, int max_freeze, uint64_t seed, int env_offset,
+                                  const gca_heli_policy* p, uint64_t policy_seed, int greedy, int K,
+                                  int32_t* action_out, float* logits_out, float* value_out, double* reward_out,
+                                  uint8_t* hit_out, uint8_t* local_out, float* coarse_out, void* scratch,
+                                  const double* thresholds, int32_t* freeze, uint32_t* rng_step, uint8_t* parity,
+                                  uint8_t* buf0, uint8_t* buf1, int H, int W, int32_t* pos, int32_t* counts,
+                                  uint8_t* hit, double* reward, int64_t* steps_elapsed, int E, void* stream);
 
 /* ------------------------------------------ measurement yardsticks (bench.py; no reference counterpart)
  * gca_bench_copy: a 16-B device copy of nbytes (one element per thread, one pass) (a multiple of 16, 16-B aligned), nt != 0 non-temporal
