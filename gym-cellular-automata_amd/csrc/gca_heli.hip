@@ -99,6 +99,58 @@ __device__ __forceinline__ bool heli_draw(const HeliCtx& c, uint32_t cell, bool 
     return v < (is_tree ? c.it_fire : c.it_tree);
 }
 
+// the codes, the key and the env id of a context; the caller adds the two thresholds and, per CA pass, step, prow, pcol
+__device__ __forceinline__ HeliCtx heli_ctx(int empty, int tree, int fire, uint64_t seed, uint32_t env_id) {
+    HeliCtx c;
+    c.Ep = rep4((uint32_t)empty);
+    c.Tp = rep4((uint32_t)tree);
+    c.Fp = rep4((uint32_t)fire);
+    c.k0 = (uint32_t)seed;
+    c.k1 = (uint32_t)(seed >> 32);
+    c.env_id = env_id;
+    return c;
+}
+
+// column 0 of gca_random_actions
+__device__ __forceinline__ int32_t heli_random_action(uint32_t env_id, uint32_t rs, uint64_t action_seed) {
+    const u32x4 x = philox4x32_10(u32x4{0u, env_id, rs, GCA_TAG_ACTION}, (uint32_t)action_seed,
+                                  (uint32_t)(action_seed >> 32));
+    return randint_ms(x.x, 0, 9);
+}
+
+// helicopter.py:120-135: dot([0, 1, -1], counts / ncells) = cT / n - cF / n (0 * x and the first add are exact)
+__device__ __forceinline__ double heli_reward(int32_t cT, int32_t cF, double n) {
+    return __dsub_rn(__ddiv_rn((double)cT, n), __ddiv_rn((double)cF, n));
+}
+
+// The next state of the dword x at (row r, columns col0 .. col0 + 3) from its byte masks: fB FIRE, em EMPTY, ign TREE
+// with a burning neighbour, dT the other TREE, win the winning draws. Modify is folded in: the helicopter's cell, if it
+// would be FIRE, becomes EMPTY (hit). Cells of no known code keep their byte.
+struct HeliNext {
+    uint32_t out;        // the four new cell codes
+    int32_t nE, nT, nF;  // how many of them are EMPTY / TREE / FIRE
+    uint32_t hit;        // 1 when Modify put a fire out here
+};
+__device__ __forceinline__ HeliNext heli_next4(const HeliCtx& c, uint32_t x, uint32_t fB, uint32_t em, uint32_t ign,
+                                               uint32_t dT, uint32_t win, int r, int col0) {
+    uint32_t nF = ign | (dT & win);
+    const uint32_t nT = (dT & ~win) | (em & win);
+    uint32_t nE = (em & ~win) | fB;
+    const uint32_t dc = (uint32_t)(c.pcol - col0);
+    const uint32_t mk = (r == c.prow && dc < 4u) ? (1u << (8 * dc)) : 0u;
+    const uint32_t hw = nF & mk;
+    nF ^= hw;
+    nE |= hw;
+    const uint32_t known = nE | nT | nF;  // 0x01 where the cell holds one of the three codes
+    HeliNext n;
+    n.out = nE * (c.Ep & 0xFFu) + nT * (c.Tp & 0xFFu) + nF * (c.Fp & 0xFFu) + (x & ~(known * 0xFFu));
+    n.nE = __popc(nE);
+    n.nT = __popc(nT);
+    n.nF = __popc(nF);
+    n.hit = hw != 0u ? 1u : 0u;
+    return n;
+}
+
 // rows [r0, min(r0 + HELI_SH, H)) x columns [256 ch, 256 ch + 256) of one env, by one wave
 __device__ __forceinline__ void heli_strip(const uint8_t* __restrict__ S, uint8_t* __restrict__ D, int r0, int ch,
                                            int nch, int H, int W, int lane, const HeliCtx& c, int32_t& cE, int32_t& cT,
@@ -128,23 +180,12 @@ __device__ __forceinline__ void heli_strip(const uint8_t* __restrict__ S, uint8_
                 win |= (d && w) ? (1u << (8 * j)) : 0u;
             }
         }
-        uint32_t nF = ign | (dT & win);
-        const uint32_t nT = (dT & ~win) | (em & win);
-        uint32_t nE = (em & ~win) | B.f;
-        // Modify folded into the store: the helicopter's cell, if it would be FIRE, is written EMPTY
-        const uint32_t dc = (uint32_t)(c.pcol - col0);
-        const uint32_t mk = (R == c.prow && dc < 4u) ? (1u << (8 * dc)) : 0u;
-        const uint32_t hw = nF & mk;
-        nF ^= hw;
-        nE |= hw;
-        hit += hw != 0u;
-        const uint32_t known = nE | nT | nF;  // 0x01 where the cell holds one of the three codes
-        const uint32_t out = nE * (c.Ep & 0xFFu) + nT * (c.Tp & 0xFFu) + nF * (c.Fp & 0xFFu) +
-                             (B.x & ~(known * 0xFFu));
-        *reinterpret_cast<uint32_t*>(D + cell0) = out;
-        cE += __popc(nE);
-        cT += __popc(nT);
-        cF += __popc(nF);
+        const HeliNext n = heli_next4(c, B.x, B.f, em, ign, dT, win, R, col0);
+        *reinterpret_cast<uint32_t*>(D + cell0) = n.out;
+        cE += n.nE;
+        cT += n.nT;
+        cF += n.nF;
+        hit += (int32_t)n.hit;
         A = B;
         B = C;
     }
@@ -226,13 +267,8 @@ __global__ __launch_bounds__(HELI_THREADS) void helicopter_step_kernel(HeliArgs 
     const uint32_t rs = a.rng_step[e];
     const uint32_t env_id = (uint32_t)(a.env_offset + e);
     int32_t act;
-    if (a.action) {
-        act = a.action[e];
-    } else {  // column 0 of gca_random_actions
-        const u32x4 x = philox4x32_10(u32x4{0u, env_id, rs, GCA_TAG_ACTION}, (uint32_t)a.action_seed,
-                                      (uint32_t)(a.action_seed >> 32));
-        act = randint_ms(x.x, 0, 9);
-    }
+    if (a.action) act = a.action[e];
+    else act = heli_random_action(env_id, rs, a.action_seed);
     const int32_t fz = a.freeze[e];
     const bool odd = a.parity[e] != 0;
     const int32_t prow0 = a.pos[2 * e], pcol0 = a.pos[2 * e + 1];
@@ -249,13 +285,7 @@ __global__ __launch_bounds__(HELI_THREADS) void helicopter_step_kernel(HeliArgs 
     uint8_t* nxt = (odd ? a.buf0 : a.buf1) + e * HW;
     int32_t cE = 0, cT = 0, cF = 0, hitc = 0;
     if (do_ca) {
-        HeliCtx c;
-        c.Ep = rep4((uint32_t)a.empty);
-        c.Tp = rep4((uint32_t)a.tree);
-        c.Fp = rep4((uint32_t)a.fire);
-        c.k0 = (uint32_t)a.seed;
-        c.k1 = (uint32_t)(a.seed >> 32);
-        c.env_id = env_id;
+        HeliCtx c = heli_ctx(a.empty, a.tree, a.fire, a.seed, env_id);
         c.step = rs;
         c.it_fire = heli_int_threshold(thr_fire);
         c.it_tree = heli_int_threshold(thr_tree);
@@ -338,9 +368,7 @@ __global__ __launch_bounds__(HELI_THREADS) void helicopter_step_kernel(HeliArgs 
     a.counts[3 * e + 1] = nT;
     a.counts[3 * e + 2] = nF;
     a.hit[e] = hh;
-    // helicopter.py:120-135: dot([0, 1, -1], counts / ncells) = cT / n - cF / n (0 * x and the first add are exact)
-    const double n = (double)HW;
-    const double rw = __dsub_rn(__ddiv_rn((double)nT, n), __ddiv_rn((double)nF, n));
+    const double rw = heli_reward(nT, nF, (double)HW);
     a.reward[e] = rw;
     if (a.rec_reward) a.rec_reward[e] = rw;
     if (a.rec_hit) a.rec_hit[e] = hh;
@@ -500,13 +528,7 @@ __device__ __forceinline__ void heli_rollout_body(const HeliRollArgs a, const He
     int p = a.parity[e] != 0;
     int row = a.pos[2 * e], col = a.pos[2 * e + 1];
     int32_t c0 = a.counts[3 * e + 0], c1 = a.counts[3 * e + 1], c2 = a.counts[3 * e + 2];
-    HeliCtx c;
-    c.Ep = rep4((uint32_t)a.empty);
-    c.Tp = rep4((uint32_t)a.tree);
-    c.Fp = rep4((uint32_t)a.fire);
-    c.k0 = (uint32_t)a.seed;
-    c.k1 = (uint32_t)(a.seed >> 32);
-    c.env_id = env_id;
+    HeliCtx c = heli_ctx(a.empty, a.tree, a.fire, a.seed, env_id);
     c.it_fire = heli_int_threshold(a.thr[2 * e]);
     c.it_tree = heli_int_threshold(a.thr[2 * e + 1]);
     const uint32_t fire = (uint32_t)a.fire;
@@ -540,10 +562,8 @@ __device__ __forceinline__ void heli_rollout_body(const HeliRollArgs a, const He
         } else if (a.actions) {  // 64 steps' actions per load: lane l holds step (k & ~63) + l
             if ((k & 63) == 0) chunk = k + lane < K ? a.actions[(size_t)(k + lane) * a.E + e] : 0;
             act = __builtin_amdgcn_readlane(chunk, k & 63);
-        } else {  // column 0 of gca_random_actions
-            const u32x4 x = philox4x32_10(u32x4{0u, env_id, rs, GCA_TAG_ACTION}, (uint32_t)a.action_seed,
-                                          (uint32_t)(a.action_seed >> 32));
-            act = randint_ms(x.x, 0, 9);
+        } else {
+            act = heli_random_action(env_id, rs, a.action_seed);
         }
         move_pos(clampi_dev(act, 0, 8), row, col, H, W, 0x007, 0x1C0, 0x049, 0x124);
         const bool do_ca = fz == 0;
@@ -588,20 +608,10 @@ __device__ __forceinline__ void heli_rollout_body(const HeliRollArgs a, const He
                     }
                 }
                 if (active) {
-                    uint32_t nF = ign | (dT & win);
-                    const uint32_t nT = (dT & ~win) | (em & win);
-                    uint32_t nE = (em & ~win) | fB;
-                    // Modify folded into the store: the helicopter's cell, if it would be FIRE, is written EMPTY
-                    const uint32_t dc = (uint32_t)(col - 4 * d);
-                    const uint32_t mk = (r == row && dc < 4u) ? (1u << (8 * dc)) : 0u;
-                    const uint32_t hw = nF & mk;
-                    nF ^= hw;
-                    nE |= hw;
-                    const uint32_t known = nE | nT | nF;
-                    Dst[idx] = nE * (c.Ep & 0xFFu) + nT * (c.Tp & 0xFFu) + nF * (c.Fp & 0xFFu) +
-                               (x & ~(known * 0xFFu));
-                    w0 += (uint32_t)__popc(nE) + ((uint32_t)__popc(nT) << 16);
-                    w1 += (uint32_t)__popc(nF) + ((hw != 0u ? 1u : 0u) << 16);
+                    const HeliNext n = heli_next4(c, x, fB, em, ign, dT, win, r, 4 * d);
+                    Dst[idx] = n.out;
+                    w0 += (uint32_t)n.nE + ((uint32_t)n.nT << 16);
+                    w1 += (uint32_t)n.nF + (n.hit << 16);
                 }
                 d += d_step;
                 r += r_step;
@@ -667,10 +677,7 @@ __device__ __forceinline__ void heli_rollout_body(const HeliRollArgs a, const He
             const size_t o = (size_t)((k & ~63) + lane) * a.E + e;
             if (a.action_out) a.action_out[o] = chunk;
             if (a.hit_out) a.hit_out[o] = (uint8_t)rec_h;
-            if (a.reward_out) {
-                const double n = (double)HW;
-                a.reward_out[o] = __dsub_rn(__ddiv_rn((double)rec_t, n), __ddiv_rn((double)rec_f, n));
-            }
+            if (a.reward_out) a.reward_out[o] = heli_reward(rec_t, rec_f, (double)HW);
         }
     }
     // ---- exit (the last step's barrier stands between every LDS store and these reads): the current plane, and after
@@ -701,8 +708,7 @@ __device__ __forceinline__ void heli_rollout_body(const HeliRollArgs a, const He
     a.counts[3 * e + 1] = c1;
     a.counts[3 * e + 2] = c2;
     a.hit[e] = (uint8_t)hh;
-    const double n = (double)HW;
-    a.reward[e] = __dsub_rn(__ddiv_rn((double)c1, n), __ddiv_rn((double)c2, n));
+    a.reward[e] = heli_reward(c1, c2, (double)HW);
     a.rng_step[e] = rs;
     a.steps_elapsed[e] += K;
 }
@@ -737,14 +743,49 @@ __global__ __launch_bounds__(POL_THREADS) void helicopter_policy_act_kernel(
     if (tid == 0) action[e] = act;
 }
 
-// LDS of the resident rollout: two planes and the waves' words, within the 64 KiB a launch gets by default
-bool heli_rollout_fits(int H, int W, int* D, int* plane_words, size_t* lds_bytes) {
-    const int64_t d = ((int64_t)W + 3) / 4;
-    const int64_t words = (1 + ((int64_t)H + 2) * (d + 1) + 3) & ~(int64_t)3;
+// ---------------------------------------------------------------- host side
+// The entry points that step the envs put their arguments into a HeliArgs `a` first (one workgroup per env, no `meet`);
+// these are their shared argument checks, `who` heading the message.
+int heli_check_env(const char* who, const HeliArgs& a, int E) {
+    const char* bad = nullptr;
+    if (!(a.thr && a.freeze && a.rng_step && a.parity && a.buf0 && a.buf1 && a.pos && a.counts && a.hit && a.reward &&
+          a.steps_elapsed))
+        bad = "null argument";
+    else if (!(E > 0 && a.H > 0 && a.W > 0 && a.max_freeze >= 0)) bad = "E, H, W > 0 and max_freeze >= 0";
+    else if (a.buf0 == a.buf1) bad = "buf0 and buf1 must differ";
+    else if ((int64_t)a.H * a.W >= (1 << 30)) bad = "grid too large";
+    else if (((a.empty | a.tree | a.fire) & ~0xFF) != 0 || a.empty == a.tree || a.tree == a.fire || a.empty == a.fire)
+        bad = "three distinct u8 codes";
+    if (!bad) return GCA_OK;
+    gca_set_error("argument: %s: %s", who, bad);
+    return GCA_ERR_ARG;
+}
+
+bool heli_aligned(const HeliArgs& a) { return (((uintptr_t)a.buf0 | (uintptr_t)a.buf1) & 3u) == 0; }
+// whether the step kernel can run in its FAST form
+bool heli_fast(const HeliArgs& a) { return a.W % 256 == 0 && heli_aligned(a); }
+
+void launch_heli_step(bool fast, dim3 grid, void* stream, const HeliArgs& a) {
+    const dim3 block(HELI_THREADS);
+    if (fast) hipLaunchKernelGGL(helicopter_step_kernel<true>, grid, block, 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(helicopter_step_kernel<false>, grid, block, 0, (hipStream_t)stream, a);
+}
+
+// The resident rollout's arguments (the fields the two structs share from `s`) and its LDS bytes: two planes and the
+// waves' words. False when those exceed the 64 KiB a launch gets by default.
+bool heli_roll_args(const HeliArgs& s, int K, int E, const int32_t* actions, int32_t* action_out, double* reward_out,
+                    uint8_t* hit_out, HeliRollArgs* a, size_t* lds_bytes) {
+    const int64_t d = ((int64_t)s.W + 3) / 4;
+    const int64_t words = (1 + ((int64_t)s.H + 2) * (d + 1) + 3) & ~(int64_t)3;
     const int64_t bytes = 2 * words * 4 + 16 * 4;
     if (bytes > 65536) return false;
-    *D = (int)d;
-    *plane_words = (int)words;
+    a->empty = s.empty; a->tree = s.tree; a->fire = s.fire; a->max_freeze = s.max_freeze;
+    a->seed = s.seed; a->action_seed = s.action_seed; a->env_offset = s.env_offset; a->K = K; a->E = E;
+    a->actions = actions; a->action_out = action_out; a->reward_out = reward_out; a->hit_out = hit_out;
+    a->thr = s.thr; a->freeze = s.freeze; a->rng_step = s.rng_step; a->parity = s.parity;
+    a->buf0 = s.buf0; a->buf1 = s.buf1; a->H = s.H; a->W = s.W; a->D = (int)d; a->plane_words = (int)words;
+    a->dwords = (s.W % 4 == 0 && heli_aligned(s)) ? 1 : 0;
+    a->pos = s.pos; a->counts = s.counts; a->hit = s.hit; a->reward = s.reward; a->steps_elapsed = s.steps_elapsed;
     *lds_bytes = (size_t)bytes;
     return true;
 }
@@ -757,16 +798,12 @@ extern "C" int gca_helicopter_step(int empty, int tree, int fire, int max_freeze
                                    uint8_t* buf0, uint8_t* buf1, int H, int W, int32_t* pos, int32_t* counts,
                                    uint8_t* hit, double* reward, int64_t* steps_elapsed, uint64_t* meet, int E,
                                    void* stream) {
-    GCA_CHECK_ARG(thresholds && freeze && rng_step && parity && buf0 && buf1 && pos && counts && hit && reward &&
-                      steps_elapsed,
-                  "helicopter_step: null argument");
-    GCA_CHECK_ARG(E > 0 && H > 0 && W > 0 && max_freeze >= 0, "helicopter_step: E, H, W > 0 and max_freeze >= 0");
-    GCA_CHECK_ARG(buf0 != buf1, "helicopter_step: buf0 and buf1 must differ");
-    GCA_CHECK_ARG((int64_t)H * W < (1 << 30), "helicopter_step: grid too large");
-    GCA_CHECK_ARG(((empty | tree | fire) & ~0xFF) == 0 && empty != tree && tree != fire && empty != fire,
-                  "helicopter_step: three distinct u8 codes");
+    HeliArgs a{empty,  tree,     fire,   max_freeze, seed, action_seed, env_offset, action, action_out, thresholds,
+               freeze, rng_step, parity, buf0,       buf1, H,           W,          pos,    counts,     hit,
+               reward, steps_elapsed, nullptr, 1, nullptr, nullptr};
+    if (const int st = heli_check_env("helicopter_step", a, E)) return st;
     const int64_t HW = (int64_t)H * W;
-    const bool fast = W % 256 == 0 && (((uintptr_t)buf0 | (uintptr_t)buf1) & 3u) == 0;
+    const bool fast = heli_fast(a);
     // the parts' word packs 20-bit counts: larger grids (and every grid without `meet`) run one workgroup per env;
     // parts only while the launch is small (E * P < 1024 workgroups) and every part keeps at least two strips / rows
     const int units = fast ? (H + HELI_SH - 1) / HELI_SH : H;
@@ -774,19 +811,9 @@ extern "C" int gca_helicopter_step(int empty, int tree, int fire, int max_freeze
     if (meet && HW + 1 < (1 << 20))
         while (P < 8 && (int64_t)E * P < 1024 && 2 * P <= units) P *= 2;
     GCA_CHECK_ARG((int64_t)E * P < (1ll << 31), "helicopter_step: too many workgroups");
-    HeliArgs a;
-    a.empty = empty; a.tree = tree; a.fire = fire; a.max_freeze = max_freeze;
-    a.seed = seed; a.action_seed = action_seed; a.env_offset = env_offset;
-    a.action = action; a.action_out = action_out; a.thr = thresholds; a.freeze = freeze; a.rng_step = rng_step;
-    a.parity = parity; a.buf0 = buf0; a.buf1 = buf1; a.H = H; a.W = W; a.pos = pos; a.counts = counts; a.hit = hit;
-    a.reward = reward; a.steps_elapsed = steps_elapsed;
     a.meet = P > 1 ? (unsigned long long*)meet : nullptr;
     a.P = P;
-    a.rec_reward = nullptr;
-    a.rec_hit = nullptr;
-    const dim3 grid((unsigned)((int64_t)E * P)), block(HELI_THREADS);
-    if (fast) hipLaunchKernelGGL(helicopter_step_kernel<true>, grid, block, 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(helicopter_step_kernel<false>, grid, block, 0, (hipStream_t)stream, a);
+    launch_heli_step(fast, dim3((unsigned)((int64_t)E * P)), stream, a);
     GCA_CHECK_LAUNCH("helicopter_step");
     return GCA_OK;
 }
@@ -797,50 +824,29 @@ extern "C" int gca_helicopter_rollout(int empty, int tree, int fire, int max_fre
                                       uint32_t* rng_step, uint8_t* parity, uint8_t* buf0, uint8_t* buf1, int H, int W,
                                       int32_t* pos, int32_t* counts, uint8_t* hit, double* reward,
                                       int64_t* steps_elapsed, int E, void* stream) {
-    GCA_CHECK_ARG(thresholds && freeze && rng_step && parity && buf0 && buf1 && pos && counts && hit && reward &&
-                      steps_elapsed,
-                  "helicopter_rollout: null argument");
-    GCA_CHECK_ARG(E > 0 && H > 0 && W > 0 && max_freeze >= 0, "helicopter_rollout: E, H, W > 0 and max_freeze >= 0");
+    HeliArgs a{empty,  tree,     fire,   max_freeze, seed, action_seed, env_offset, nullptr, nullptr, thresholds,
+               freeze, rng_step, parity, buf0,       buf1, H,           W,          pos,     counts,  hit,
+               reward, steps_elapsed, nullptr, 1, nullptr, nullptr};
+    if (const int st = heli_check_env("helicopter_rollout", a, E)) return st;
     GCA_CHECK_ARG(K >= 0, "helicopter_rollout: K >= 0");
-    GCA_CHECK_ARG(buf0 != buf1, "helicopter_rollout: buf0 and buf1 must differ");
-    GCA_CHECK_ARG((int64_t)H * W < (1 << 30), "helicopter_rollout: grid too large");
-    GCA_CHECK_ARG(((empty | tree | fire) & ~0xFF) == 0 && empty != tree && tree != fire && empty != fire,
-                  "helicopter_rollout: three distinct u8 codes");
     if (K == 0) return GCA_OK;
-    const bool aligned = (((uintptr_t)buf0 | (uintptr_t)buf1) & 3u) == 0;
-    const dim3 grid((unsigned)E), block(HELI_THREADS);
-    int D = 0, plane_words = 0;
+    const dim3 grid((unsigned)E);
+    HeliRollArgs ra;
     size_t lds_bytes = 0;
-    if (heli_rollout_fits(H, W, &D, &plane_words, &lds_bytes)) {
-        HeliRollArgs a;
-        a.empty = empty; a.tree = tree; a.fire = fire; a.max_freeze = max_freeze;
-        a.seed = seed; a.action_seed = action_seed; a.env_offset = env_offset; a.K = K; a.E = E;
-        a.actions = actions; a.action_out = action_out; a.reward_out = reward_out; a.hit_out = hit_out;
-        a.thr = thresholds; a.freeze = freeze; a.rng_step = rng_step; a.parity = parity; a.buf0 = buf0; a.buf1 = buf1;
-        a.H = H; a.W = W; a.D = D; a.plane_words = plane_words; a.dwords = (W % 4 == 0 && aligned) ? 1 : 0;
-        a.pos = pos; a.counts = counts; a.hit = hit; a.reward = reward; a.steps_elapsed = steps_elapsed;
-        hipLaunchKernelGGL(helicopter_rollout_kernel, grid, block, lds_bytes, (hipStream_t)stream, a);
+    if (heli_roll_args(a, K, E, actions, action_out, reward_out, hit_out, &ra, &lds_bytes)) {
+        hipLaunchKernelGGL(helicopter_rollout_kernel, grid, dim3(HELI_THREADS), lds_bytes, (hipStream_t)stream, ra);
         GCA_CHECK_LAUNCH("helicopter_rollout");
         return GCA_OK;
     }
     // the planes do not fit in LDS: K launches of the step kernel, one workgroup per env, each writing its record row
-    const bool fast = W % 256 == 0 && aligned;
-    HeliArgs a;
-    a.empty = empty; a.tree = tree; a.fire = fire; a.max_freeze = max_freeze;
-    a.seed = seed; a.action_seed = action_seed; a.env_offset = env_offset;
-    a.thr = thresholds; a.freeze = freeze; a.rng_step = rng_step;
-    a.parity = parity; a.buf0 = buf0; a.buf1 = buf1; a.H = H; a.W = W; a.pos = pos; a.counts = counts; a.hit = hit;
-    a.reward = reward; a.steps_elapsed = steps_elapsed;
-    a.meet = nullptr;
-    a.P = 1;
+    const bool fast = heli_fast(a);
     for (int k = 0; k < K; ++k) {
         const size_t o = (size_t)k * (size_t)E;
         a.action = actions ? actions + o : nullptr;
         a.action_out = action_out ? action_out + o : nullptr;
         a.rec_reward = reward_out ? reward_out + o : nullptr;
         a.rec_hit = hit_out ? hit_out + o : nullptr;
-        if (fast) hipLaunchKernelGGL(helicopter_step_kernel<true>, grid, block, 0, (hipStream_t)stream, a);
-        else hipLaunchKernelGGL(helicopter_step_kernel<false>, grid, block, 0, (hipStream_t)stream, a);
+        launch_heli_step(fast, grid, stream, a);
         GCA_CHECK_LAUNCH("helicopter_rollout");
     }
     return GCA_OK;
@@ -898,16 +904,11 @@ extern "C" int gca_helicopter_policy_rollout(int empty, int tree, int fire, int 
                                              int32_t* freeze, uint32_t* rng_step, uint8_t* parity, uint8_t* buf0,
                                              uint8_t* buf1, int H, int W, int32_t* pos, int32_t* counts, uint8_t* hit,
                                              double* reward, int64_t* steps_elapsed, int E, void* stream) {
-    GCA_CHECK_ARG(thresholds && freeze && rng_step && parity && buf0 && buf1 && pos && counts && hit && reward &&
-                      steps_elapsed,
-                  "helicopter_policy_rollout: null argument");
-    GCA_CHECK_ARG(E > 0 && H > 0 && W > 0 && max_freeze >= 0,
-                  "helicopter_policy_rollout: E, H, W > 0 and max_freeze >= 0");
+    HeliArgs a{empty,  tree,     fire,   max_freeze, seed, 0, env_offset, nullptr, nullptr, thresholds,
+               freeze, rng_step, parity, buf0,       buf1, H, W,          pos,     counts,  hit,
+               reward, steps_elapsed, nullptr, 1, nullptr, nullptr};
+    if (const int st = heli_check_env("helicopter_policy_rollout", a, E)) return st;
     GCA_CHECK_ARG(K >= 0, "helicopter_policy_rollout: K >= 0");
-    GCA_CHECK_ARG(buf0 != buf1, "helicopter_policy_rollout: buf0 and buf1 must differ");
-    GCA_CHECK_ARG((int64_t)H * W < (1 << 30), "helicopter_policy_rollout: grid too large");
-    GCA_CHECK_ARG(((empty | tree | fire) & ~0xFF) == 0 && empty != tree && tree != fire && empty != fire,
-                  "helicopter_policy_rollout: three distinct u8 codes");
     GCA_CHECK_ARG(p && p->block >= 1, "helicopter_policy_rollout: policy required");
     const int Hc = (H + p->block - 1) / p->block, Wc = (W + p->block - 1) / p->block;
     const int64_t C64 = 2 * (int64_t)Hc * Wc;
@@ -916,27 +917,19 @@ extern "C" int gca_helicopter_policy_rollout(int empty, int tree, int fire, int 
     HeliPolArgs q;
     if (const int st = heli_policy_check(p, C, policy_seed, greedy, &q.w)) return st;
     if (K == 0) return GCA_OK;
-    const bool aligned = (((uintptr_t)buf0 | (uintptr_t)buf1) & 3u) == 0;
-    const dim3 grid((unsigned)E), block(HELI_THREADS);
-    int D = 0, plane_words = 0;
+    const dim3 grid((unsigned)E);
+    HeliRollArgs ra;
     size_t lds_bytes = 0;
-    if (heli_rollout_fits(H, W, &D, &plane_words, &lds_bytes) &&
+    if (heli_roll_args(a, K, E, nullptr, action_out, reward_out, hit_out, &ra, &lds_bytes) &&
         lds_bytes + (size_t)heli_policy_lds_words(C) * 4 <= 65536) {
-        HeliRollArgs a;
-        a.empty = empty; a.tree = tree; a.fire = fire; a.max_freeze = max_freeze;
-        a.seed = seed; a.action_seed = 0; a.env_offset = env_offset; a.K = K; a.E = E;
-        a.actions = nullptr; a.action_out = action_out; a.reward_out = reward_out; a.hit_out = hit_out;
-        a.thr = thresholds; a.freeze = freeze; a.rng_step = rng_step; a.parity = parity; a.buf0 = buf0; a.buf1 = buf1;
-        a.H = H; a.W = W; a.D = D; a.plane_words = plane_words; a.dwords = (W % 4 == 0 && aligned) ? 1 : 0;
-        a.pos = pos; a.counts = counts; a.hit = hit; a.reward = reward; a.steps_elapsed = steps_elapsed;
         q.radius = p->radius;
         q.lgB = 0;
         while ((1 << q.lgB) < p->block) ++q.lgB;
         q.Hc = Hc; q.Wc = Wc;
         q.inv = 1.0f / (float)(p->block * p->block);
         q.logits_out = logits_out; q.value_out = value_out; q.local_out = local_out; q.coarse_out = coarse_out;
-        hipLaunchKernelGGL(helicopter_policy_rollout_kernel, grid, block,
-                           lds_bytes + (size_t)heli_policy_lds_words(C) * 4, (hipStream_t)stream, a, q);
+        hipLaunchKernelGGL(helicopter_policy_rollout_kernel, grid, dim3(HELI_THREADS),
+                           lds_bytes + (size_t)heli_policy_lds_words(C) * 4, (hipStream_t)stream, ra, q);
         GCA_CHECK_LAUNCH("helicopter_policy_rollout");
         return GCA_OK;
     }
@@ -949,16 +942,7 @@ extern "C" int gca_helicopter_policy_rollout(int empty, int tree, int fire, int 
     int32_t* s_act = (int32_t*)scratch;
     float* s_coarse = (float*)scratch + E;
     uint8_t* s_local = (uint8_t*)(s_coarse + (size_t)E * C);
-    const bool fast = W % 256 == 0 && aligned;
-    HeliArgs a;
-    a.empty = empty; a.tree = tree; a.fire = fire; a.max_freeze = max_freeze;
-    a.seed = seed; a.action_seed = 0; a.env_offset = env_offset;
-    a.thr = thresholds; a.freeze = freeze; a.rng_step = rng_step;
-    a.parity = parity; a.buf0 = buf0; a.buf1 = buf1; a.H = H; a.W = W; a.pos = pos; a.counts = counts; a.hit = hit;
-    a.reward = reward; a.steps_elapsed = steps_elapsed;
-    a.meet = nullptr;
-    a.P = 1;
-    a.action_out = nullptr;
+    const bool fast = heli_fast(a);
     for (int k = 0; k < K; ++k) {
         const size_t o = (size_t)k * (size_t)E;
         int32_t* act_k = action_out ? action_out + o : s_act;
@@ -974,8 +958,7 @@ extern "C" int gca_helicopter_policy_rollout(int empty, int tree, int fire, int 
         a.action = act_k;
         a.rec_reward = reward_out ? reward_out + o : nullptr;
         a.rec_hit = hit_out ? hit_out + o : nullptr;
-        if (fast) hipLaunchKernelGGL(helicopter_step_kernel<true>, grid, block, 0, (hipStream_t)stream, a);
-        else hipLaunchKernelGGL(helicopter_step_kernel<false>, grid, block, 0, (hipStream_t)stream, a);
+        launch_heli_step(fast, grid, stream, a);
         GCA_CHECK_LAUNCH("helicopter_policy_rollout");
     }
     return GCA_OK;

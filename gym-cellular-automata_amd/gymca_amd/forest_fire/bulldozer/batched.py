@@ -31,36 +31,26 @@ import numpy as np
 
 from ... import _device as dev
 from ..._lib import SLOT, BoundCall, call
-from .. import policy_obs
+from .._batched import BatchedEnvBase, check_tensor, rollout_actions, seed64
 from ..operators.move_modify import make_params
 from .bulldozer import ACTION_SETS, DEFAULT_WIND, bulldozer_timings, parse_wind
 
 
-# state the pre-bound calls hold by address (step, step_random, sample_actions): assigning one of these attributes
-# validates the replacement and drops the bound calls (rebind), so the next step binds the new tensor
-_BOUND_STATE = frozenset({"buf", "parity", "accu", "steps", "dir_mask", "counts", "pos", "rng_step", "done", "hit",
-                          "reward", "wind", "steps_elapsed", "params", "_meet", "_act_buf", "episode",
-                          "last_episode_length", "_terminated", "_truncated_u8"})
+class BatchedForestFireBulldozerEnv(BatchedEnvBase):
+    # state the pre-bound calls hold by address (step, step_random, sample_actions): assigning one of these attributes
+    # validates the replacement and drops the bound calls (BatchedEnvBase.__setattr__)
+    _BOUND_STATE = frozenset({"buf", "parity", "accu", "steps", "dir_mask", "counts", "pos", "rng_step", "done", "hit",
+                              "reward", "wind", "steps_elapsed", "params", "_meet", "_act_buf", "episode",
+                              "last_episode_length", "_terminated", "_truncated_u8"})
+    _BOUND_READY = "_fused_call"
 
-
-class BatchedForestFireBulldozerEnv:
-    def __setattr__(self, name, value):
-        d = self.__dict__
-        if name in _BOUND_STATE and "_fused_call" in d and d.get(name) is not value:
-            old = d.get(name)
-            if name == "params":
-                if type(value) is not type(old):
-                    raise TypeError(f"params must stay a {type(old).__name__}")
-            elif name == "_meet" and value is None:
-                pass
-            elif not (dev.is_device_tensor(value) and value.dtype == old.dtype and value.shape == old.shape
-                      and value.device == old.device and value.is_contiguous()):
-                raise ValueError(f"env.{name}: the replacement must be a contiguous {old.dtype} tensor of shape "
-                                 f"{tuple(old.shape)} on {old.device} (or update the tensor in place)")
-            object.__setattr__(self, name, value)
-            self.rebind()
-            return
-        object.__setattr__(self, name, value)
+    def _check_replacement(self, name, old, value):
+        # the two bound attributes that are no tensor: params keeps its type, _meet may be switched off
+        if name == "params":
+            if type(value) is not type(old):
+                raise TypeError(f"params must stay a {type(old).__name__}")
+        elif not (name == "_meet" and value is None):
+            super()._check_replacement(name, old, value)
 
     def __init__(self, num_envs, nrows, ncols, device=None, seed=0, env_offset=0, speed_move=0.12, speed_act=0.03,
                  t_move=None, t_shoot=None, t_any=0.001, p_tree=0.90, p_empty=0.10, wind=DEFAULT_WIND,
@@ -86,7 +76,7 @@ class BatchedForestFireBulldozerEnv:
             p.t_move[a] = 0.0 if a == 4 else t_act_move  # not_move costs _t_act_none (bulldozer.py:285)
         p.t_shoot[0], p.t_shoot[1] = 0.0, t_act_shoot
         p.t_any = t_any
-        p.seed = self.seed_value & (2**64 - 1)
+        p.seed = seed64(self.seed_value)
         p.env_offset = self.env_offset
         p.empty, p.tree, p.fire = self._empty, self._tree, self._fire
         self.params = p
@@ -124,7 +114,7 @@ class BatchedForestFireBulldozerEnv:
         self.last_episode_length = torch.zeros(E, dtype=torch.int64, **kw)
         self._terminated = torch.zeros(E, dtype=torch.uint8, **kw)
         self._truncated_u8 = torch.zeros(E, dtype=torch.uint8, **kw)
-        self._reset_seed = self.seed_value
+        self._reset_seed = p.seed
         self._reset_cdf = torch.tensor([p_empty, p_empty + p_tree, 1.0], dtype=torch.float32, device=self.device)
         self._reset_vals = torch.tensor([self._empty, self._tree, self._fire], dtype=torch.uint8, device=self.device)
         # the eager step's host path: persistent outputs and pre-bound C-ABI calls, so a step is
@@ -141,12 +131,6 @@ class BatchedForestFireBulldozerEnv:
         self._observe_calls = {}
 
     # ------------------------------------------------------------------ state
-    def grids(self):
-        """(E, H, W) uint8 view of every env's current grid (one gather pass)."""
-        import torch
-
-        return torch.where(self.parity.bool()[:, None, None], self.buf[1], self.buf[0])
-
     def reset(self, seed=None, grids=None, positions=None):
         """Reset all envs. Initial distribution of bulldozer.py:233-275: the grid from Philox per cell, the fire /
         bulldozer noise from per-env draws keyed by the global env id (_seeding), so a sharded env reproduces the
@@ -167,7 +151,7 @@ class BatchedForestFireBulldozerEnv:
                                device=self.device)
             vals = torch.tensor([self._empty, self._tree, self._fire], dtype=torch.uint8, device=self.device)
             call("gca_fill_categorical", dev.ptr(self.buf[0]), H * W, E, self.env_offset,
-                 (self.seed_value if seed is None else int(seed)) & (2**64 - 1), dev.ptr(cdf), dev.ptr(vals), 3, st)
+                 seed64(s), dev.ptr(cdf), dev.ptr(vals), 3, st)
             # one FIRE around the lower-left quadrant, noise in [0, N/12) (bulldozer.py:221-253)
             fr = 3 * H // 4 + noise(1, H)
             fc = W // 4 + noise(2, W)
@@ -175,9 +159,7 @@ class BatchedForestFireBulldozerEnv:
             self.buf[0][idx, torch.as_tensor(fr, device=self.device), torch.as_tensor(fc, device=self.device)] = \
                 self._fire
         if positions is not None:
-            pos = np.asarray(positions).reshape(E, 2)
-            if not ((pos[:, 0] >= 0) & (pos[:, 0] < H) & (pos[:, 1] >= 0) & (pos[:, 1] < W)).all():
-                raise ValueError(f"reset: every position must lie inside the {H}x{W} grid")
+            pos = self._check_positions(positions)
         else:
             pos = np.stack([H // 4 + noise(3, H), 3 * W // 4 + noise(4, W)], axis=1)
         self.pos.copy_(torch.as_tensor(pos.astype(np.int32), device=self.device))
@@ -188,35 +170,10 @@ class BatchedForestFireBulldozerEnv:
         self.rng_step.zero_()
         self.steps_elapsed.zero_()
         self.episode.zero_()
-        self._reset_seed = s  # reset_where draws the later episodes from the same seed
+        self._reset_seed = seed64(s)  # reset_where draws the later episodes from the same seed
         call("gca_count_cells", dev.ptr(self.buf[0]), E, H, W, self._empty, self._tree, self._fire,
              dev.ptr(self.counts), st)
         return self._obs(), {"hit": self.hit}
-
-    def _obs(self):
-        return (self.grids() if self.materialize_obs else None), self._ctx
-
-    def observe(self, radius=16, block=16, local_out=None, coarse_out=None, form=0):
-        """The policy observation of every env in one launch (gca_policy_observation, policy_obs.observe): `local`, uint8
-        (E, 2 radius + 1, 2 radius + 1), the classes of the cells around the bulldozer (0 other, 1 TREE, 2 FIRE, 3 outside
-        the grid), and `coarse`, float32 (E, 2, ceil(H / block), ceil(W / block)), the TREE and the FIRE share of every
-        block x block tile. Reads each env's current plane once: no grids() gather, no sync, and with both outputs given
-        (contiguous tensors of that dtype and shape on the env's device, written in place and returned) no allocation.
-        radius in [0, 31], block a power of two in [1, 64]; form 0 picks the kernel by shape."""
-        return policy_obs.observe(self, radius, block, local_out, coarse_out, form)
-
-    def _action(self, action):
-        """action as a contiguous int32 (E, 2) device tensor: the caller's own tensor when it is one (checked on every
-        call: a tensor retyped or reshaped in place since the last step is converted, not misread), else converted
-        into the env's action buffer."""
-        import torch
-
-        if (type(action) is torch.Tensor and action.dtype is torch.int32 and action.get_device() == self._dev_index
-                and action.shape == self._act_shape and action.is_contiguous()):
-            return action
-        src = action if dev.is_device_tensor(action) else torch.as_tensor(np.asarray(action))
-        self._act_buf.copy_(src.reshape(self.num_envs, 2))
-        return self._act_buf
 
     def rebind(self):
         """Drop the pre-bound step calls. The env's state tensors (buf, accu, steps, done, wind, rng_step, parity, pos,
@@ -257,7 +214,7 @@ class BatchedForestFireBulldozerEnv:
                 dev.ptr(self.hit), dev.ptr(self.steps_elapsed), E, SLOT,
                 keep=self._bound_tensors() + (self._reset_cdf, self._reset_vals, self._terminated, self._truncated_u8,
                                               self.episode, self.last_episode_length))
-        rc(self._reset_seed & (2**64 - 1), mask_ptr, max_steps, set_episode, dev.raw_stream(self._dev_index))
+        rc(self._reset_seed, mask_ptr, max_steps, set_episode, dev.raw_stream(self._dev_index))
 
     def _autoreset(self):
         """The reset launch that follows a step under autoreset=True: the envs that are done, or at their time limit,
@@ -330,16 +287,14 @@ class BatchedForestFireBulldozerEnv:
         import torch
 
         out = self._act_buf if action_out is None else action_out
-        if not (type(out) is torch.Tensor and out.dtype is torch.int32 and out.get_device() == self._dev_index
-                and out.shape == self._act_shape and out.is_contiguous()):
-            raise ValueError("step_random: action_out must be a contiguous int32 (E, 2) tensor on the env's device")
+        check_tensor(out, torch.int32, self._act_shape, self._dev_index, "step_random", "action_out")
         key = (seed, out.data_ptr())
         rc = self._random_call
         if rc is None or rc[0] != key or rc[1] is not out or self._bound_meet_r is not self._meet:
             E, H, W = self.num_envs, self.nrows, self.ncols
             meet = self._meet
             self._random_call = (key, out, BoundCall(
-                "gca_bulldozer_step_fused_random", self.params, int(seed) & (2**64 - 1), dev.ptr(out),
+                "gca_bulldozer_step_fused_random", self.params, seed64(seed), dev.ptr(out),
                 dev.ptr(self.accu), dev.ptr(self.steps), dev.ptr(self.done), dev.ptr(self.wind), 9,
                 dev.ptr(self.rng_step), dev.ptr(self.parity), dev.ptr(self.buf[0]), dev.ptr(self.buf[1]), H, W,
                 dev.ptr(self.pos), dev.ptr(self.counts), dev.ptr(self.hit), dev.ptr(self.reward),
@@ -368,25 +323,15 @@ class BatchedForestFireBulldozerEnv:
         for name, t, dt, shape in (("action_out", action_out, torch.int32, (K, E, 2)),
                                    ("reward_out", reward_out, torch.float64, (K, E)),
                                    ("done_out", done_out, torch.uint8, (K, E))):
-            if t is not None and not (type(t) is torch.Tensor and t.dtype == dt and tuple(t.shape) == shape
-                                      and t.device == self.device and t.is_contiguous()):
-                raise ValueError(f"rollout_random: {name} must be a contiguous {dt} {shape} tensor on the env's device")
+            if t is not None:
+                check_tensor(t, dt, shape, self._dev_index, "rollout_random", name)
         H, W = self.nrows, self.ncols
-        call("gca_bulldozer_rollout_random", self.params, int(seed) & (2**64 - 1), K, dev.ptr(action_out),
+        call("gca_bulldozer_rollout_random", self.params, seed64(seed), K, dev.ptr(action_out),
              dev.ptr(reward_out), dev.ptr(done_out), dev.ptr(self.accu), dev.ptr(self.steps), dev.ptr(self.done),
              dev.ptr(self.wind), 9, dev.ptr(self.rng_step), dev.ptr(self.parity), dev.ptr(self.buf[0]),
              dev.ptr(self.buf[1]), H, W, dev.ptr(self.pos), dev.ptr(self.counts), dev.ptr(self.hit), dev.ptr(self.reward),
              dev.ptr(self.steps_elapsed), E, dev.stream_ptr(self.device))
         return reward_out, done_out
-
-    def _check_record(self, out, dtype, shape, what):
-        import torch
-
-        if not (type(out) is torch.Tensor and out.dtype is dtype and out.get_device() == self._dev_index
-                and tuple(out.shape) == shape and out.is_contiguous()):
-            raise ValueError(f"rollout: {what} must be a contiguous {str(dtype).replace('torch.', '')} "
-                             f"{'(K, E, 2)' if len(shape) == 3 else '(K, E)'} tensor on the env's device")
-        return out
 
     def rollout(self, actions=None, K=None, seed=9, action_out=None, reward_out=None, terminated_out=None,
                 truncated_out=None):
@@ -408,43 +353,12 @@ class BatchedForestFireBulldozerEnv:
         import torch
 
         E = self.num_envs
-        if actions is None:
-            if K is None:
-                raise ValueError("rollout: K is needed with actions=None")
-            K, a = int(K), None
-        else:
-            a = actions
-            if not (type(a) is torch.Tensor and a.dtype is torch.int32 and a.get_device() == self._dev_index
-                    and a.is_contiguous()):
-                if dev.is_device_tensor(a):
-                    if a.is_floating_point() or a.dtype is torch.bool:
-                        raise ValueError("rollout: actions must be integers")
-                    if a.device != self.device:
-                        raise ValueError(f"rollout: actions live on {a.device}, the env on {self.device}")
-                    a = a.to(torch.int32).contiguous()
-                elif isinstance(a, torch.Tensor):
-                    raise ValueError(f"rollout: actions live on {a.device}, the env on {self.device}")
-                else:
-                    h = np.asarray(a)
-                    if h.dtype.kind not in "iu":
-                        raise ValueError("rollout: actions must be integers")
-                    a = dev.to_device(h.astype(np.int32), torch.int32, self.device)
-            if a.dim() != 3 or a.shape[1] != E or a.shape[2] != 2:
-                raise ValueError(f"rollout: actions must have shape (K, {E}, 2), got {tuple(a.shape)}")
-            if K is not None and int(K) != a.shape[0]:
-                raise ValueError(f"rollout: K = {K} disagrees with actions of shape {tuple(a.shape)}")
-            K = int(a.shape[0])
-        if K < 0:
-            raise ValueError("rollout: K >= 0")
-        kw = dict(device=self.device)
-        reward_out = torch.empty((K, E), dtype=torch.float64, **kw) if reward_out is None else \
-            self._check_record(reward_out, torch.float64, (K, E), "reward_out")
-        terminated_out = torch.empty((K, E), dtype=torch.uint8, **kw) if terminated_out is None else \
-            self._check_record(terminated_out, torch.uint8, (K, E), "terminated_out")
-        truncated_out = torch.empty((K, E), dtype=torch.uint8, **kw) if truncated_out is None else \
-            self._check_record(truncated_out, torch.uint8, (K, E), "truncated_out")
+        a, K = rollout_actions(actions, K, E, (2,), self.device, self._dev_index, "rollout", convert_host_tensor=False)
+        reward_out = self._out(reward_out, torch.float64, (K, E), "rollout", "reward_out")
+        terminated_out = self._out(terminated_out, torch.uint8, (K, E), "rollout", "terminated_out")
+        truncated_out = self._out(truncated_out, torch.uint8, (K, E), "rollout", "truncated_out")
         if action_out is not None:
-            self._check_record(action_out, torch.int32, (K, E, 2), "action_out")
+            check_tensor(action_out, torch.int32, (K, E, 2), self._dev_index, "rollout", "action_out")
         if K == 0:
             return reward_out, terminated_out, truncated_out
         if not self.fused:
@@ -475,9 +389,9 @@ class BatchedForestFireBulldozerEnv:
                 dev.ptr(self.steps_elapsed), E, SLOT,
                 keep=self._bound_tensors() + (self._reset_cdf, self._reset_vals, self._terminated, self._truncated_u8,
                                               self.episode, self.last_episode_length))
-        rc(None if a is None else a.data_ptr(), int(seed) & (2**64 - 1), K,
+        rc(None if a is None else a.data_ptr(), seed64(seed), K,
            None if action_out is None else action_out.data_ptr(), reward_out.data_ptr(), terminated_out.data_ptr(),
-           truncated_out.data_ptr(), 1 if self.autoreset else 0, self._reset_seed & (2**64 - 1),
+           truncated_out.data_ptr(), 1 if self.autoreset else 0, self._reset_seed,
            (self.max_episode_steps or 0) if self.autoreset else 0, dev.raw_stream(self._dev_index))
         return reward_out, terminated_out, truncated_out
 
@@ -488,14 +402,12 @@ class BatchedForestFireBulldozerEnv:
         import torch
 
         out = self._act_buf if out is None else out
-        if not (type(out) is torch.Tensor and out.dtype is torch.int32 and out.get_device() == self._dev_index
-                and out.shape == self._act_shape and out.is_contiguous()):
-            raise ValueError("sample_actions: out must be a contiguous int32 (E, 2) tensor on the env's device")
+        check_tensor(out, torch.int32, self._act_shape, self._dev_index, "sample_actions", "out")
         sc = self._sample_call
         if sc is None or sc[0] is not out or sc[1] != tag or sc[2] != out.data_ptr():
             self._sample_call = (out, tag, out.data_ptr(),
-                                 BoundCall("gca_random_actions", dev.ptr(out), self.num_envs, self.env_offset, tag,
-                                           dev.ptr(self.rng_step), SLOT, keep=(out, self.rng_step)))
+                                 BoundCall("gca_random_actions", dev.ptr(out), self.num_envs, self.env_offset,
+                                           seed64(tag), dev.ptr(self.rng_step), SLOT, keep=(out, self.rng_step)))
         self._sample_call[3](dev.raw_stream(self._dev_index))
         return out
 

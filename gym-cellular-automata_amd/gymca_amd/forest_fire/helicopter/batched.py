@@ -17,27 +17,16 @@ import numpy as np
 from ... import _device as dev
 from ..._lib import SLOT, BoundCall, call
 from .. import policy_obs
+from .._batched import BatchedEnvBase, check_tensor, rollout_actions, seed64
 from ..operators.ca_DrosselSchwabl import choice_threshold
 
-# state the pre-bound calls hold by address (step, step_random, sample_actions): assigning one of these attributes
-# validates the replacement and drops the bound calls (rebind), so the next step binds the new tensor
-_BOUND_STATE = frozenset({"buf", "parity", "freeze", "pos", "counts", "rng_step", "hit", "reward", "steps_elapsed",
-                          "thresholds", "_meet", "_act_buf", "_act2"})
 
-
-class BatchedForestFireHelicopterEnv:
-    def __setattr__(self, name, value):
-        d = self.__dict__
-        if name in _BOUND_STATE and "_step_call" in d and d.get(name) is not value:
-            old = d.get(name)
-            if not (dev.is_device_tensor(value) and value.dtype == old.dtype and value.shape == old.shape
-                    and value.device == old.device and value.is_contiguous()):
-                raise ValueError(f"env.{name}: the replacement must be a contiguous {old.dtype} tensor of shape "
-                                 f"{tuple(old.shape)} on {old.device} (or update the tensor in place)")
-            object.__setattr__(self, name, value)
-            self.rebind()
-            return
-        object.__setattr__(self, name, value)
+class BatchedForestFireHelicopterEnv(BatchedEnvBase):
+    # state the pre-bound calls hold by address (step, step_random, sample_actions): assigning one of these attributes
+    # validates the replacement and drops the bound calls (BatchedEnvBase.__setattr__)
+    _BOUND_STATE = frozenset({"buf", "parity", "freeze", "pos", "counts", "rng_step", "hit", "reward", "steps_elapsed",
+                              "thresholds", "_meet", "_act_buf", "_act2"})
+    _BOUND_READY = "_step_call"
 
     def __init__(self, num_envs, nrows, ncols, device=None, seed=0, env_offset=0, speed=0.5, freeze=None,
                  p_fire=0.033, p_tree=0.333, materialize_obs=True):
@@ -82,25 +71,12 @@ class BatchedForestFireHelicopterEnv:
         self.rebind()
 
     # ------------------------------------------------------------------ state
-    def grids(self):
-        """(E, H, W) uint8: every env's current grid (one gather pass)."""
-        import torch
-
-        return torch.where(self.parity.bool()[:, None, None], self.buf[1], self.buf[0])
-
     def _recount(self):
         E, H, W = self.num_envs, self.nrows, self.ncols
         self.buf[0].copy_(self.grids())
         self.parity.zero_()
         call("gca_count_cells", dev.ptr(self.buf[0]), E, H, W, self._empty, self._tree, self._fire,
              dev.ptr(self.counts), dev.stream_ptr(self.device))
-
-    def _check_positions(self, positions):
-        E, H, W = self.num_envs, self.nrows, self.ncols
-        pos = np.asarray(positions).reshape(E, 2)
-        if not ((pos[:, 0] >= 0) & (pos[:, 0] < H) & (pos[:, 1] >= 0) & (pos[:, 1] < W)).all():
-            raise ValueError(f"every position must lie inside the {H}x{W} grid")
-        return pos.astype(np.int32)
 
     def reset(self, seed=None, grids=None, positions=None):
         """Reset all envs: the grid uniform over {EMPTY, TREE, FIRE} (grid_space.sample(), helicopter.py:33-42) from
@@ -115,7 +91,7 @@ class BatchedForestFireHelicopterEnv:
             cdf = torch.tensor([1.0 / 3.0, 2.0 / 3.0, 1.0], dtype=torch.float32, device=self.device)
             vals = torch.tensor([self._empty, self._tree, self._fire], dtype=torch.uint8, device=self.device)
             call("gca_fill_categorical", dev.ptr(self.buf[0]), H * W, E, self.env_offset,
-                 (self.seed_value if seed is None else int(seed)) & (2**64 - 1), dev.ptr(cdf), dev.ptr(vals), 3,
+                 seed64(self.seed_value if seed is None else seed), dev.ptr(cdf), dev.ptr(vals), 3,
                  dev.stream_ptr(self.device))
         if positions is not None:
             self.pos.copy_(torch.as_tensor(self._check_positions(positions), device=self.device))
@@ -153,30 +129,6 @@ class BatchedForestFireHelicopterEnv:
             self.rng_step.copy_(dev.to_device(r, torch.int32, self.device).reshape(E))
         self._recount()
 
-    def _obs(self):
-        return (self.grids() if self.materialize_obs else None), self._ctx
-
-    def observe(self, radius=16, block=16, local_out=None, coarse_out=None, form=0):
-        """The policy observation of every env in one launch (gca_policy_observation, policy_obs.observe): `local`, uint8
-        (E, 2 radius + 1, 2 radius + 1), the classes of the cells around the helicopter (0 other, 1 TREE, 2 FIRE, 3 outside
-        the grid), and `coarse`, float32 (E, 2, ceil(H / block), ceil(W / block)), the TREE and the FIRE share of every
-        block x block tile. Reads each env's current plane once: no grids() gather, no sync, and with both outputs given
-        (contiguous tensors of that dtype and shape on the env's device, written in place and returned) no allocation.
-        radius in [0, 31], block a power of two in [1, 64]; form 0 picks the kernel by shape."""
-        return policy_obs.observe(self, radius, block, local_out, coarse_out, form)
-
-    def _action(self, action):
-        """action as a contiguous int32 (E,) device tensor: the caller's own tensor when it is one (checked on every
-        call), else converted into the env's action buffer."""
-        import torch
-
-        if (type(action) is torch.Tensor and action.dtype is torch.int32 and action.get_device() == self._dev_index
-                and action.shape == self._act_shape and action.is_contiguous()):
-            return action
-        src = action if dev.is_device_tensor(action) else torch.as_tensor(np.asarray(action))
-        self._act_buf.copy_(src.reshape(self.num_envs))
-        return self._act_buf
-
     def rebind(self):
         """Drop the pre-bound calls. The state tensors are bound by address on the first step and every method here
         updates them in place; assigning a new tensor to one of them calls this by itself (__setattr__, which also
@@ -199,7 +151,7 @@ class BatchedForestFireHelicopterEnv:
         E, H, W = self.num_envs, self.nrows, self.ncols
         return BoundCall(
             "gca_helicopter_step", self._empty, self._tree, self._fire, self.max_freeze,
-            self.seed_value & (2**64 - 1), self.env_offset, action, action_seed, action_out,
+            seed64(self.seed_value), self.env_offset, action, action_seed, action_out,
             dev.ptr(self.thresholds), dev.ptr(self.freeze), dev.ptr(self.rng_step), dev.ptr(self.parity),
             dev.ptr(self.buf[0]), dev.ptr(self.buf[1]), H, W, dev.ptr(self.pos), dev.ptr(self.counts),
             dev.ptr(self.hit), dev.ptr(self.reward), dev.ptr(self.steps_elapsed), dev.ptr(self._meet), E, SLOT,
@@ -222,34 +174,20 @@ class BatchedForestFireHelicopterEnv:
         sc(a.data_ptr(), dev.raw_stream(self._dev_index))
         return self._result()
 
-    def _check_out(self, out, who):
-        import torch
-
-        if not (type(out) is torch.Tensor and out.dtype is torch.int32 and out.get_device() == self._dev_index
-                and out.shape == self._act_shape and out.is_contiguous()):
-            raise ValueError(f"{who}: the output must be a contiguous int32 (E,) tensor on the env's device")
-        return out
-
     def step_random(self, seed=9, action_out=None):
         """One env step of every env under a uniform random policy, the action drawn INSIDE the step exactly as
         sample_actions(out, tag=seed) draws it before step(out): the two in one launch, bit for bit. The drawn actions
         go to `action_out` (a contiguous int32 (E,) device tensor, default the env's action buffer)."""
-        out = self._check_out(self._act_buf if action_out is None else action_out, "step_random")
+        import torch
+
+        out = check_tensor(self._act_buf if action_out is None else action_out, torch.int32, self._act_shape,
+                           self._dev_index, "step_random", "action_out")
         key = (seed, out.data_ptr())
         rc = self._random_call
         if rc is None or rc[0] != key or rc[1] is not out:
-            rc = self._random_call = (key, out, self._bind(None, int(seed) & (2**64 - 1), dev.ptr(out), keep=(out,)))
+            rc = self._random_call = (key, out, self._bind(None, seed64(seed), dev.ptr(out), keep=(out,)))
         rc[2](dev.raw_stream(self._dev_index))
         return self._result()
-
-    def _check_record(self, out, dtype, K, who, what):
-        import torch
-
-        if not (type(out) is torch.Tensor and out.dtype is dtype and out.get_device() == self._dev_index
-                and tuple(out.shape) == (K, self.num_envs) and out.is_contiguous()):
-            raise ValueError(f"{who}: {what} must be a contiguous {str(dtype).replace('torch.', '')} (K, E) tensor on "
-                             "the env's device")
-        return out
 
     def rollout(self, actions=None, K=None, seed=9, action_out=None, reward_out=None, hit_out=None):
         """K env steps of every env in one call: exactly K step(actions[k]) calls (frame-skip / action-repeat, open-loop
@@ -264,39 +202,11 @@ class BatchedForestFireHelicopterEnv:
         import torch
 
         E = self.num_envs
-        if actions is None:
-            if K is None:
-                raise ValueError("rollout: K is needed with actions=None")
-            K, a = int(K), None
-        else:
-            a = actions
-            if not (type(a) is torch.Tensor and a.dtype is torch.int32 and a.get_device() == self._dev_index
-                    and a.is_contiguous()):
-                if dev.is_device_tensor(a):
-                    if a.is_floating_point() or a.dtype is torch.bool:
-                        raise ValueError("rollout: actions must be integers")
-                    if a.device != self.device:
-                        raise ValueError(f"rollout: actions live on {a.device}, the env on {self.device}")
-                    a = a.to(torch.int32).contiguous()
-                else:
-                    h = np.asarray(a)
-                    if h.dtype.kind not in "iu":
-                        raise ValueError("rollout: actions must be integers")
-                    a = dev.to_device(h.astype(np.int32), torch.int32, self.device)
-            if a.dim() != 2 or a.shape[1] != E:
-                raise ValueError(f"rollout: actions must have shape (K, {E}), got {tuple(a.shape)}")
-            if K is not None and int(K) != a.shape[0]:
-                raise ValueError(f"rollout: K = {K} disagrees with actions of shape {tuple(a.shape)}")
-            K = int(a.shape[0])
-        if K < 0:
-            raise ValueError("rollout: K >= 0")
-        kw = dict(device=self.device)
-        reward_out = torch.empty((K, E), dtype=torch.float64, **kw) if reward_out is None else \
-            self._check_record(reward_out, torch.float64, K, "rollout", "reward_out")
-        hit_out = torch.empty((K, E), dtype=torch.uint8, **kw) if hit_out is None else \
-            self._check_record(hit_out, torch.uint8, K, "rollout", "hit_out")
+        a, K = rollout_actions(actions, K, E, (), self.device, self._dev_index, "rollout", convert_host_tensor=True)
+        reward_out = self._out(reward_out, torch.float64, (K, E), "rollout", "reward_out")
+        hit_out = self._out(hit_out, torch.uint8, (K, E), "rollout", "hit_out")
         if action_out is not None:
-            self._check_record(action_out, torch.int32, K, "rollout", "action_out")
+            check_tensor(action_out, torch.int32, (K, E), self._dev_index, "rollout", "action_out")
         if K == 0:
             return reward_out, hit_out
         rc = self._rollout_call
@@ -304,12 +214,12 @@ class BatchedForestFireHelicopterEnv:
             H, W = self.nrows, self.ncols
             rc = self._rollout_call = BoundCall(
                 "gca_helicopter_rollout", self._empty, self._tree, self._fire, self.max_freeze,
-                self.seed_value & (2**64 - 1), self.env_offset, SLOT, SLOT, SLOT, SLOT, SLOT, SLOT,
+                seed64(self.seed_value), self.env_offset, SLOT, SLOT, SLOT, SLOT, SLOT, SLOT,
                 dev.ptr(self.thresholds), dev.ptr(self.freeze), dev.ptr(self.rng_step), dev.ptr(self.parity),
                 dev.ptr(self.buf[0]), dev.ptr(self.buf[1]), H, W, dev.ptr(self.pos), dev.ptr(self.counts),
                 dev.ptr(self.hit), dev.ptr(self.reward), dev.ptr(self.steps_elapsed), E, SLOT,
                 keep=self._bound_tensors())
-        rc(None if a is None else a.data_ptr(), int(seed) & (2**64 - 1), K,
+        rc(None if a is None else a.data_ptr(), seed64(seed), K,
            None if action_out is None else action_out.data_ptr(), reward_out.data_ptr(), hit_out.data_ptr(),
            dev.raw_stream(self._dev_index))
         return reward_out, hit_out
@@ -326,15 +236,6 @@ class BatchedForestFireHelicopterEnv:
         if policy.device != self.device:
             raise ValueError(f"{who}: the policy lives on {policy.device}, the env on {self.device}")
         return policy
-
-    def _check_tensor(self, out, dtype, shape, who, what):
-        import torch
-
-        if not (type(out) is torch.Tensor and out.dtype is dtype and out.get_device() == self._dev_index
-                and tuple(out.shape) == tuple(shape) and out.is_contiguous()):
-            raise ValueError(f"{who}: {what} must be a contiguous {str(dtype).replace('torch.', '')} {tuple(shape)} "
-                             "tensor on the env's device")
-        return out
 
     def _policy_call(self, kind, policy, make):
         """The pre-bound call of `kind` for this policy; bound again when a policy tensor was replaced (its version
@@ -362,19 +263,15 @@ class BatchedForestFireHelicopterEnv:
         if local is None:
             local, coarse = self.observe(policy.radius, policy.block)
         else:
-            self._check_tensor(local, torch.uint8, ls, "act", "local")
-            self._check_tensor(coarse, torch.float32, cs, "act", "coarse")
-        kw = dict(device=self.device)
-        action_out = torch.empty(E, dtype=torch.int32, **kw) if action_out is None else \
-            self._check_tensor(action_out, torch.int32, (E,), "act", "action_out")
-        logits_out = torch.empty((E, 9), dtype=torch.float32, **kw) if logits_out is None else \
-            self._check_tensor(logits_out, torch.float32, (E, 9), "act", "logits_out")
-        value_out = torch.empty(E, dtype=torch.float32, **kw) if value_out is None else \
-            self._check_tensor(value_out, torch.float32, (E,), "act", "value_out")
+            check_tensor(local, torch.uint8, ls, self._dev_index, "act", "local")
+            check_tensor(coarse, torch.float32, cs, self._dev_index, "act", "coarse")
+        action_out = self._out(action_out, torch.int32, (E,), "act", "action_out")
+        logits_out = self._out(logits_out, torch.float32, (E, 9), "act", "logits_out")
+        value_out = self._out(value_out, torch.float32, (E,), "act", "value_out")
         pc = self._policy_call("act", policy, lambda: (BoundCall(
             "gca_helicopter_policy_act", policy.struct, policy.C, SLOT, SLOT, dev.ptr(self.rng_step), self.env_offset,
             SLOT, SLOT, SLOT, SLOT, SLOT, E, SLOT, keep=(self.rng_step,) + policy.tensors()),))
-        pc[2](local.data_ptr(), coarse.data_ptr(), int(seed) & (2**64 - 1), 1 if greedy else 0, action_out.data_ptr(),
+        pc[2](local.data_ptr(), coarse.data_ptr(), seed64(seed), 1 if greedy else 0, action_out.data_ptr(),
               logits_out.data_ptr(), value_out.data_ptr(), dev.raw_stream(self._dev_index))
         return action_out, logits_out, value_out
 
@@ -411,10 +308,8 @@ class BatchedForestFireHelicopterEnv:
         recs = {}
         for name in self._POLICY_RECORDS:
             dtype, shape = spec[name]
-            if given[name] is not None:
-                recs[name] = self._check_tensor(given[name], dtype, shape, "rollout_policy", f"{name}_out")
-            elif name in record:
-                recs[name] = torch.empty(shape, dtype=dtype, device=self.device)
+            if given[name] is not None or name in record:
+                recs[name] = self._out(given[name], dtype, shape, "rollout_policy", f"{name}_out")
         if K == 0:
             return recs
 
@@ -424,7 +319,7 @@ class BatchedForestFireHelicopterEnv:
             scratch = torch.empty(E * (4 + 4 * policy.C + policy.S * policy.S), dtype=torch.uint8, device=self.device)
             return BoundCall(
                 "gca_helicopter_policy_rollout", self._empty, self._tree, self._fire, self.max_freeze,
-                self.seed_value & (2**64 - 1), self.env_offset, policy.struct, SLOT, SLOT, SLOT, SLOT, SLOT, SLOT, SLOT,
+                seed64(self.seed_value), self.env_offset, policy.struct, SLOT, SLOT, SLOT, SLOT, SLOT, SLOT, SLOT,
                 SLOT, SLOT, SLOT, dev.ptr(scratch), dev.ptr(self.thresholds), dev.ptr(self.freeze),
                 dev.ptr(self.rng_step), dev.ptr(self.parity), dev.ptr(self.buf[0]), dev.ptr(self.buf[1]), H, W,
                 dev.ptr(self.pos), dev.ptr(self.counts), dev.ptr(self.hit), dev.ptr(self.reward),
@@ -433,7 +328,7 @@ class BatchedForestFireHelicopterEnv:
 
         pc = self._policy_call("rollout", policy, make)
         p = lambda name: recs[name].data_ptr() if name in recs else None
-        pc[2](int(seed) & (2**64 - 1), 1 if greedy else 0, K, p("action"), p("logits"), p("value"), p("reward"),
+        pc[2](seed64(seed), 1 if greedy else 0, K, p("action"), p("logits"), p("value"), p("reward"),
               p("hit"), p("local"), p("coarse"), dev.raw_stream(self._dev_index))
         return recs
 
@@ -441,11 +336,14 @@ class BatchedForestFireHelicopterEnv:
         """Uniform random actions in [0, 9) for every env on the device -- the batched `action_space.sample()`: column
         0 of gca_random_actions (Philox keyed by (tag, global env id, the env's rng_step)) -- into `out` (a contiguous
         int32 (E,) device tensor) or the env's action buffer. Returns the tensor."""
-        out = self._check_out(self._act_buf if out is None else out, "sample_actions")
+        import torch
+
+        out = check_tensor(self._act_buf if out is None else out, torch.int32, self._act_shape, self._dev_index,
+                           "sample_actions", "out")
         sc = self._sample_call
         if sc is None or sc[0] != tag:
             sc = self._sample_call = (tag, BoundCall("gca_random_actions", dev.ptr(self._act2), self.num_envs,
-                                                     self.env_offset, int(tag) & (2**64 - 1), dev.ptr(self.rng_step),
+                                                     self.env_offset, seed64(tag), dev.ptr(self.rng_step),
                                                      SLOT, keep=(self._act2, self.rng_step)))
         sc[1](dev.raw_stream(self._dev_index))
         out.copy_(self._act2[:, 0])

@@ -13,6 +13,7 @@ share the fields it reads (buf, parity, pos, the three codes).
 """
 from .. import _device as dev
 from .._lib import SLOT, BoundCall
+from ._batched import check_tensor
 
 
 def output_shapes(env, radius, block):
@@ -20,16 +21,6 @@ def output_shapes(env, radius, block):
     E, H, W = env.num_envs, env.nrows, env.ncols
     S = 2 * radius + 1
     return (E, S, S), (E, 2, -(-H // block), -(-W // block))
-
-
-def _check_out(env, out, dtype, shape, what):
-    import torch
-
-    if not (type(out) is torch.Tensor and out.dtype is dtype and out.get_device() == env._dev_index
-            and tuple(out.shape) == shape and out.is_contiguous()):
-        raise ValueError(f"observe: {what} must be a contiguous {str(dtype).replace('torch.', '')} {shape} tensor on "
-                         "the env's device")
-    return out
 
 
 def observe(env, radius=16, block=16, local_out=None, coarse_out=None, form=0):
@@ -49,9 +40,9 @@ def observe(env, radius=16, block=16, local_out=None, coarse_out=None, form=0):
         raise ValueError("observe: form must be 0 (by shape), 1 (generic) or 2 (rows)")
     ls, cs = output_shapes(env, radius, block)
     local_out = torch.empty(ls, dtype=torch.uint8, device=env.device) if local_out is None else \
-        _check_out(env, local_out, torch.uint8, ls, "local_out")
+        check_tensor(local_out, torch.uint8, ls, env._dev_index, "observe", "local_out")
     coarse_out = torch.empty(cs, dtype=torch.float32, device=env.device) if coarse_out is None else \
-        _check_out(env, coarse_out, torch.float32, cs, "coarse_out")
+        check_tensor(coarse_out, torch.float32, cs, env._dev_index, "observe", "coarse_out")
     calls = env._observe_calls
     key = (radius, block, form)
     oc = calls.get(key)

@@ -286,14 +286,14 @@ def test_rollout_validation(device):
     r, h = env.rollout(good[:0])
     assert tuple(r.shape) == (0, E) and tuple(h.shape) == (0, E)
     ref.assert_states_equal(_state(env), before, "K = 0")
-    # int64 device actions and a replaced bound tensor both work
+    # int64 device actions, host arrays and tensors and a replaced bound tensor all work
     twin = _env(device, g, 1)
     env.rollout(good.to(torch.int64) + 5)
     new_pos = env.pos.clone()
     env.pos = new_pos
     env.rollout(good + 3)
     twin.rollout(np.full((K, E), 5))
-    twin.rollout(np.full((K, E), 3))
+    twin.rollout(torch.full((K, E), 3))  # a host tensor: the helicopter converts it like a numpy array
     ref.assert_states_equal(_state(env), _state(twin), "converted actions, rebound pos")
     assert env._ctx["position"] is new_pos
     assert not env._meet.any().item() and not twin._meet.any().item()
