@@ -85,6 +85,10 @@ __device__ __forceinline__ void move_pos(int a, int& row, int& col, int H, int W
 __device__ __forceinline__ int cell_category(int v, int empty, int tree, int fire) {
     return v == empty ? 0 : (v == tree ? 1 : (v == fire ? 2 : -1));
 }
+// _award (bulldozer.py:180-213) from the TREE and FIRE counts of the post-Modify grid; _is_done (:215-216) is cF == 0
+__device__ __forceinline__ double bdz_reward(int32_t cT, int32_t cF) {
+    return (cT + cF) > 0 ? -((double)cF / (double)(cT + cF)) : (double)NAN;
+}
 
 // WindyForestFire active-direction mask (ca_windy.py:53-77): bit d set iff roll[d] < wind[d]
 // (the reference marks d as failed iff wind <= roll). d indexes the 3x3 row-major, centre skipped.

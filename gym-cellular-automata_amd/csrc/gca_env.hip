@@ -8,9 +8,6 @@
 
 #include "gca_common.h"
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return clampi_dev(v, lo, hi); }
-__device__ __forceinline__ int category(int v, int empty, int tree, int fire) { return cell_category(v, empty, tree, fire); }
-
 // ================================================================== ForestFireBulldozer
 __global__ void bulldozer_pre_kernel(gca_bulldozer_params p, const int32_t* __restrict__ action,
                                      double* __restrict__ accu, int32_t* __restrict__ steps,
@@ -23,7 +20,7 @@ __global__ void bulldozer_pre_kernel(gca_bulldozer_params p, const int32_t* __re
         steps[e] = -1;
         return;
     }
-    const int a0 = clampi(action[2 * e], 0, 8), a1 = clampi(action[2 * e + 1], 0, 1);
+    const int a0 = clampi_dev(action[2 * e], 0, 8), a1 = clampi_dev(action[2 * e + 1], 0, 1);
     // RepeatCA.update: time_taken = t_acting(action) + t_perception(state); accu += time_taken
     const double time_action = p.t_move[a0] + p.t_shoot[a1];
     const double x = accu[e] + (time_action + p.t_any);
@@ -75,7 +72,7 @@ __global__ void bulldozer_post_kernel(gca_bulldozer_params p, int last_pass, con
     if (parity && n > last_pass) parity[e] ^= 1;
     uint8_t* grid = ((parity && parity[e]) ? buf1 : buf0) + (int64_t)e * H * W;
     // MoveModify (move_modify.py:128-134): Move, then Modify at the new position
-    const int a0 = clampi(action[2 * e], 0, 8), a1 = action[2 * e + 1];
+    const int a0 = clampi_dev(action[2 * e], 0, 8), a1 = action[2 * e + 1];
     int row = pos[2 * e], col = pos[2 * e + 1];
     move_pos(a0, row, col, H, W, p.up_mask, p.down_mask, p.left_mask, p.right_mask);
     pos[2 * e] = row;
@@ -87,15 +84,15 @@ __global__ void bulldozer_post_kernel(gca_bulldozer_params p, int last_pass, con
         if (nv >= 0) {
             grid[(int64_t)row * W + col] = (uint8_t)nv;
             h = 1;
-            const int c_old = category(v, p.empty, p.tree, p.fire), c_new = category(nv, p.empty, p.tree, p.fire);
+            const int c_old = cell_category(v, p.empty, p.tree, p.fire), c_new = cell_category(nv, p.empty, p.tree, p.fire);
             if (c_old >= 0) counts[3 * e + c_old] -= 1;
             if (c_new >= 0) counts[3 * e + c_new] += 1;
         }
     }
     hit[e] = h;
-    // _award (bulldozer.py:180-213) and _is_done (:215-216) on the post-Modify grid
+    // _award and _is_done (bulldozer.py:215-216) on the post-Modify grid
     const int t = counts[3 * e + 1], f = counts[3 * e + 2];
-    reward[e] = (t + f) > 0 ? -((double)f / (double)(t + f)) : (double)NAN;
+    reward[e] = bdz_reward(t, f);
     done[e] = f == 0 ? 1 : 0;
     rng_step[e] += (uint32_t)n;
 }
@@ -155,7 +152,7 @@ __global__ void advenv_post_kernel(gca_advenv_params p, const int32_t* __restric
                                   (uint32_t)(p.seed >> 32));
     if (u01_f32(x.x) < p.p_wind_change) wind_index[e] = (wind_index[e] + randint_ms(x.y, 1, 8)) % p.n_winds;
     // RepeatCAJax time bookkeeping (repeat_ca_jax.py:191-198), f32 like the JAX env
-    const int a0 = clampi(action[2 * e], 0, 8), a1 = clampi(action[2 * e + 1], 0, 1);
+    const int a0 = clampi_dev(action[2 * e], 0, 8), a1 = clampi_dev(action[2 * e + 1], 0, 1);
     const float time_taken = __fadd_rn(__fadd_rn(p.t_move[a0], p.t_shoot[a1]), p.t_any);
     const float na = __fadd_rn(accu[e], time_taken);
     accu[e] = __fsub_rn(na, truncf(na));

@@ -19,7 +19,7 @@
 //    horizontal ones from byte funnel shifts plus the neighbour lane's edge dword.
 //    Reward/done counts of the new grid are fused (wave reduction + 3 atomics).
 #include "gca_common.h"
-#include "gca_reset_dev.h"  // the in-launch reset of the rollout kernel
+#include "gca_reset_dev.h"  // the in-launch reset of the rollout kernel, wave_sum3
 
 // windy_fast_kernel: row chunks in flight ahead of the one being computed (r01o: 2 / 4 / 8 measured slower than 1)
 constexpr int WINDY_AHEAD = 1;
@@ -447,7 +447,7 @@ __global__ __launch_bounds__(256) void windy_rows_kernel(uint8_t* __restrict__ b
 // ------------------------------------------------------------------ the whole ForestFireBulldozer env step, fused
 // The env's direction mask (windy_mask bit for bit) drawn inside one wave, no barrier: lane j < 4 draws Philox block j
 // (directions 2j, 2j+1) against the env's wind, two ballots gather the bits; the result is wave-uniform (an SGPR).
-// Shared by both fused step kernels so their draw order cannot drift apart.
+// Shared by both fused step kernels and the rollout kernel so their draw order cannot drift apart.
 __device__ __forceinline__ uint32_t wave_windy_mask(const gca_bulldozer_params& p, const double (&wl)[9], int e,
                                                     uint32_t rs, int lane) {
     bool b0 = false, b1 = false;
@@ -604,7 +604,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
     counts[3 * e + 1] = cT;
     counts[3 * e + 2] = cF;
     hit[e] = h;
-    reward[e] = (cT + cF) > 0 ? -((double)cF / (double)(cT + cF)) : (double)NAN;
+    reward[e] = bdz_reward(cT, cF);
     done[e] = cF == 0 ? 1 : 0;
     rng_step[e] = rs + (uint32_t)n;
     if (steps_elapsed) steps_elapsed[e] = se + 1;
@@ -669,7 +669,7 @@ __global__ __launch_bounds__(256) void bulldozer_step_fused_parts_kernel(
             windy_rows_strip_f<NW, SHv, RDv, STD>(S, Dst, s * SHv, H, get_mask, lofs, rep4(p.empty),
                                                            rep4(p.tree), rep4(p.fire), cntT, cntF, cntV);
 #pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
+        for (int off = 32; off > 0; off >>= 1) {  // (not wave_sum3: DESIGN.md, "What the fused bulldozer kernels share")
             cntT += __shfl_xor(cntT, off);
             cntF += __shfl_xor(cntF, off);
             cntV += __shfl_xor(cntV, off);
@@ -738,7 +738,7 @@ __global__ __launch_bounds__(256) void bulldozer_step_fused_parts_kernel(
     counts[3 * e + 1] = cT;
     counts[3 * e + 2] = cF;
     hit[e] = hh;
-    reward[e] = (cT + cF) > 0 ? -((double)cF / (double)(cT + cF)) : (double)NAN;
+    reward[e] = bdz_reward(cT, cF);
     done[e] = cF == 0 ? 1 : 0;
     rng_step[e] = rs + (uint32_t)n;
     if (steps_elapsed) steps_elapsed[e] = se + 1;
@@ -934,7 +934,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
                 cF = B[2];
                 h = (uint8_t)B[3];
             }
-            rew = (cT + cF) > 0 ? -((double)cF / (double)(cT + cF)) : (double)NAN;
+            rew = bdz_reward(cT, cF);
             was_done = cF == 0;
             rs += (uint32_t)n;
             se += 1;
@@ -1093,28 +1093,60 @@ extern "C" int gca_windy_step(uint8_t* buf0, uint8_t* buf1, const uint8_t* parit
     return GCA_OK;
 }
 
+// The argument checks the fused step and both rollouts share, in the order they fire; `who` prefixes the message. have:
+// p and every required per-env pointer are given. K: the rollouts' step count (NULL: the single step's two own texts).
+static int bdz_check_fused(const char* who, bool have, const gca_bulldozer_params* p, int E, int H, int W,
+                           const void* buf0, const void* buf1, int64_t wind_stride, const int* K) {
+    const char* bad = nullptr;
+    if (!(have && E > 0 && H > 0 && (!K || *K >= 0)))
+        bad = K ? "null argument, empty batch or K < 0" : "null argument or empty batch";
+    else if (!(W == 256 || W == 512)) bad = "W must be 256 or 512 (the row-stream CA)";
+    else if (!(p->empty == 0 && p->empty < p->tree && p->tree < p->fire && p->fire < 256))
+        bad = "cell codes must be empty = 0 < tree < fire < 256 (the closed-form rule)";
+    else if (((((uintptr_t)buf0) | ((uintptr_t)buf1)) & 15u) != 0) bad = "buffers 16-B aligned";
+    else if (!(wind_stride >= 0)) bad = "wind_stride >= 0";
+    else if (K && !((int64_t)*K * E < ((int64_t)1 << 40))) bad = "K x E too large";
+    else {
+        // at most one CA step per env step: accu < 1 on entry, so (t_move + t_shoot) + t_any < 1 for every action
+        double tmax = 0.0;
+        for (int a = 0; a < 9; ++a)
+            for (int b = 0; b < 2; ++b) tmax = fmax(tmax, (p->t_move[a] + p->t_shoot[b]) + p->t_any);
+        if (!(tmax < 1.0))
+            bad = K ? "an action can take >= 1 time unit (several CA passes per step)"
+                    : "an action can take >= 1 time unit (several CA passes per step): "
+                      "use gca_bulldozer_pre / gca_windy_step / gca_bulldozer_post";
+    }
+    if (!bad) return GCA_OK;
+    gca_set_error("argument: %s: %s", who, bad);
+    return GCA_ERR_ARG;
+}
+
+// threads of the one-workgroup kernels (the fused step, the rollout): a wave per strip of the grid, 16 at the most
+static int bdz_threads(int H, int W) {
+    const int fsh = W == 256 ? FUSED_SH<1> : FUSED_SH<2>;
+    const int strips = (H + fsh - 1) / fsh;
+    return 64 * (strips < 16 ? strips : 16);
+}
+
+// SOLO (bulldozer_rollout_random_kernel's comment): no effect maps a FIRE cell or onto FIRE
+static bool bdz_modify_keeps_fire(const gca_bulldozer_params& p) {
+    for (int v = 0; v < 256; ++v) {
+        const int nv = p.effect[v];
+        if (nv >= 0 && (v == p.fire) != (nv == p.fire)) return false;
+    }
+    return true;
+}
+
 static int bulldozer_step_fused_impl(const gca_bulldozer_params* p, const int32_t* action, FusedPolicy pol,
                                      double* accu, int32_t* steps, uint8_t* done, const double* wind,
                                      int64_t wind_stride, uint32_t* rng_step, uint8_t* parity, uint8_t* buf0,
                                      uint8_t* buf1, int H, int W, int32_t* pos, int32_t* counts, uint8_t* hit,
                                      double* reward, int64_t* steps_elapsed, uint64_t* meet, int E, void* stream) {
-    GCA_CHECK_ARG(p && accu && steps && done && wind && rng_step && parity && buf0 && buf1 && pos && counts &&
-                      hit && reward && E > 0 && H > 0,
-                  "bulldozer_step_fused: null argument or empty batch");
-    GCA_CHECK_ARG(W == 256 || W == 512, "bulldozer_step_fused: W must be 256 or 512 (the row-stream CA)");
-    GCA_CHECK_ARG(p->empty == 0 && p->empty < p->tree && p->tree < p->fire && p->fire < 256,
-                  "bulldozer_step_fused: cell codes must be empty = 0 < tree < fire < 256 (the closed-form rule)");
-    GCA_CHECK_ARG(((((uintptr_t)buf0) | ((uintptr_t)buf1)) & 15u) == 0, "bulldozer_step_fused: buffers 16-B aligned");
-    GCA_CHECK_ARG(wind_stride >= 0, "bulldozer_step_fused: wind_stride >= 0");
-    // at most one CA step per env step: accu < 1 on entry, so (t_move + t_shoot) + t_any < 1 for every action
-    double tmax = 0.0;
-    for (int a = 0; a < 9; ++a)
-        for (int b = 0; b < 2; ++b) tmax = fmax(tmax, (p->t_move[a] + p->t_shoot[b]) + p->t_any);
-    GCA_CHECK_ARG(tmax < 1.0, "bulldozer_step_fused: an action can take >= 1 time unit (several CA passes per step): "
-                              "use gca_bulldozer_pre / gca_windy_step / gca_bulldozer_post");
-    const int fsh = W == 256 ? FUSED_SH<1> : FUSED_SH<2>;
-    const int strips = (H + fsh - 1) / fsh;
-    const int threads = 64 * (strips < 16 ? strips : 16);
+    const bool have =
+        p && accu && steps && done && wind && rng_step && parity && buf0 && buf1 && pos && counts && hit && reward;
+    if (const int status = bdz_check_fused("bulldozer_step_fused", have, p, E, H, W, buf0, buf1, wind_stride, nullptr))
+        return status;
+    const int threads = bdz_threads(H, W);
     hipStream_t st = (hipStream_t)stream;
     const bool std_codes = p->empty == 0 && p->tree == 3 && p->fire == 25;
 #define GCA_FUSED_LAUNCH(NWV, STDV)                                                                                 \
@@ -1170,54 +1202,59 @@ extern "C" int gca_bulldozer_step_fused_random(const gca_bulldozer_params* p, ui
                                      steps_elapsed, meet, E, stream);
 }
 
+// Both rollout entry points, after their checks: the instantiation picked from (W, the cell codes, SOLO, whose kernels,
+// autoreset, whose actions) and launched. ext_kernels = false (gca_bulldozer_rollout_random): the EXT = false
+// instantiations, which know at compile time that there is no caller's action, no truncated record and no reset.
+static int bulldozer_rollout_impl(const char* who, bool ext_kernels, int autoreset, const gca_bulldozer_params* p,
+                                  uint64_t action_seed, int K, int32_t* action_out, double* reward_out,
+                                  uint8_t* done_out, const RolloutExt& ext, double* accu, int32_t* steps, uint8_t* done,
+                                  const double* wind, int64_t wind_stride, uint32_t* rng_step, uint8_t* parity,
+                                  uint8_t* buf0, uint8_t* buf1, int H, int W, int32_t* pos, int32_t* counts,
+                                  uint8_t* hit, double* reward, int64_t* steps_elapsed, int E, void* stream) {
+    if (K == 0) return GCA_OK;
+    const int threads = bdz_threads(H, W);
+    hipStream_t st = (hipStream_t)stream;
+    const bool std_codes = p->empty == 0 && p->tree == 3 && p->fire == 25;
+    const bool solo = bdz_modify_keeps_fire(*p);
+#define GCA_ROLLOUT_LAUNCH(NWV, STDV, SOLOV, EXTV, RESETV, ACTV)                                                       \
+    hipLaunchKernelGGL((bulldozer_rollout_random_kernel<NWV, STDV, SOLOV, EXTV, RESETV, ACTV>), dim3((unsigned)E),     \
+                       dim3(threads), 0, st, *p, K, action_seed, action_out, reward_out, done_out, accu, steps, done,  \
+                       wind, wind_stride, rng_step, parity, buf0, buf1, H, pos, counts, hit, reward, steps_elapsed, E, \
+                       ext)
+#define GCA_ROLLOUT_PICK(NWV, EXTV, RESETV, ACTV)                                       \
+    do {                                                                                \
+        if (std_codes && solo) GCA_ROLLOUT_LAUNCH(NWV, true, true, EXTV, RESETV, ACTV); \
+        else if (solo) GCA_ROLLOUT_LAUNCH(NWV, false, true, EXTV, RESETV, ACTV);        \
+        else GCA_ROLLOUT_LAUNCH(NWV, false, false, EXTV, RESETV, ACTV);                 \
+    } while (0)
+#define GCA_ROLLOUT_MODE(NWV)                                           \
+    do {                                                                \
+        if (!ext_kernels) GCA_ROLLOUT_PICK(NWV, false, false, false);   \
+        else if (autoreset) GCA_ROLLOUT_PICK(NWV, true, true, false);   \
+        else if (ext.actions) GCA_ROLLOUT_PICK(NWV, true, false, true); \
+        else GCA_ROLLOUT_PICK(NWV, true, false, false);                 \
+    } while (0)
+    if (W == 256) GCA_ROLLOUT_MODE(1); else GCA_ROLLOUT_MODE(2);
+#undef GCA_ROLLOUT_MODE
+#undef GCA_ROLLOUT_PICK
+#undef GCA_ROLLOUT_LAUNCH
+    GCA_CHECK_LAUNCH(who);
+    return GCA_OK;
+}
+
 extern "C" int gca_bulldozer_rollout_random(const gca_bulldozer_params* p, uint64_t action_seed, int K,
                                             int32_t* action_out, double* reward_out, uint8_t* done_out, double* accu,
                                             int32_t* steps, uint8_t* done, const double* wind, int64_t wind_stride,
                                             uint32_t* rng_step, uint8_t* parity, uint8_t* buf0, uint8_t* buf1, int H,
                                             int W, int32_t* pos, int32_t* counts, uint8_t* hit, double* reward,
                                             int64_t* steps_elapsed, int E, void* stream) {
-    GCA_CHECK_ARG(p && accu && steps && done && wind && rng_step && parity && buf0 && buf1 && pos && counts && hit &&
-                      reward && E > 0 && H > 0 && K >= 0,
-                  "bulldozer_rollout_random: null argument, empty batch or K < 0");
-    GCA_CHECK_ARG(W == 256 || W == 512, "bulldozer_rollout_random: W must be 256 or 512 (the row-stream CA)");
-    GCA_CHECK_ARG(p->empty == 0 && p->empty < p->tree && p->tree < p->fire && p->fire < 256,
-                  "bulldozer_rollout_random: cell codes must be empty = 0 < tree < fire < 256 (the closed-form rule)");
-    GCA_CHECK_ARG(((((uintptr_t)buf0) | ((uintptr_t)buf1)) & 15u) == 0, "bulldozer_rollout_random: buffers 16-B aligned");
-    GCA_CHECK_ARG(wind_stride >= 0, "bulldozer_rollout_random: wind_stride >= 0");
-    GCA_CHECK_ARG((int64_t)K * E < ((int64_t)1 << 40), "bulldozer_rollout_random: K x E too large");
-    double tmax = 0.0;
-    for (int a = 0; a < 9; ++a)
-        for (int b = 0; b < 2; ++b) tmax = fmax(tmax, (p->t_move[a] + p->t_shoot[b]) + p->t_any);
-    GCA_CHECK_ARG(tmax < 1.0, "bulldozer_rollout_random: an action can take >= 1 time unit (several CA passes per step)");
-    if (K == 0) return GCA_OK;
-    const int fsh = W == 256 ? FUSED_SH<1> : FUSED_SH<2>;
-    const int strips = (H + fsh - 1) / fsh;
-    const int threads = 64 * (strips < 16 ? strips : 16);
-    hipStream_t st = (hipStream_t)stream;
-    const bool std_codes = p->empty == 0 && p->tree == 3 && p->fire == 25;
-    // SOLO: Modify never changes the FIRE count (the kernel's comment)
-    bool solo = true;
-    auto fire_cat = [&](int v) { return v == p->fire; };
-    for (int v = 0; v < 256; ++v) {
-        const int nv = p->effect[v];
-        if (nv >= 0 && fire_cat(v) != fire_cat(nv)) solo = false;
-    }
-#define GCA_ROLLOUT_LAUNCH(NWV, STDV, SOLOV)                                                                             \
-    hipLaunchKernelGGL((bulldozer_rollout_random_kernel<NWV, STDV, SOLOV>), dim3((unsigned)E), dim3(threads), 0, st, *p, \
-                       K, action_seed, action_out, reward_out, done_out, accu, steps, done, wind, wind_stride, rng_step,  \
-                       parity, buf0, buf1, H, pos, counts, hit, reward, steps_elapsed, E, RolloutExt{})
-    if (W == 256) {
-        if (std_codes && solo) GCA_ROLLOUT_LAUNCH(1, true, true);
-        else if (solo) GCA_ROLLOUT_LAUNCH(1, false, true);
-        else GCA_ROLLOUT_LAUNCH(1, false, false);
-    } else {
-        if (std_codes && solo) GCA_ROLLOUT_LAUNCH(2, true, true);
-        else if (solo) GCA_ROLLOUT_LAUNCH(2, false, true);
-        else GCA_ROLLOUT_LAUNCH(2, false, false);
-    }
-#undef GCA_ROLLOUT_LAUNCH
-    GCA_CHECK_LAUNCH("bulldozer_rollout_random");
-    return GCA_OK;
+    const char* who = "bulldozer_rollout_random";
+    const bool have =
+        p && accu && steps && done && wind && rng_step && parity && buf0 && buf1 && pos && counts && hit && reward;
+    if (const int status = bdz_check_fused(who, have, p, E, H, W, buf0, buf1, wind_stride, &K)) return status;
+    return bulldozer_rollout_impl(who, false, 0, p, action_seed, K, action_out, reward_out, done_out, RolloutExt{}, accu,
+                                  steps, done, wind, wind_stride, rng_step, parity, buf0, buf1, H, W, pos, counts, hit,
+                                  reward, steps_elapsed, E, stream);
 }
 
 // The rollout with the caller's actions (or the random policy) and, with `autoreset`, the per-env reset after every step
@@ -1230,20 +1267,10 @@ extern "C" int gca_bulldozer_rollout(const gca_bulldozer_params* p, const int32_
                                      uint8_t* parity, uint8_t* buf0, uint8_t* buf1, int H, int W, int32_t* pos,
                                      int32_t* counts, uint8_t* hit, double* reward, int64_t* steps_elapsed, int E,
                                      void* stream) {
-    // gca_bulldozer_rollout_random's checks
-    GCA_CHECK_ARG(p && accu && steps && done && wind && rng_step && parity && buf0 && buf1 && pos && counts && hit &&
-                      reward && E > 0 && H > 0 && K >= 0,
-                  "bulldozer_rollout: null argument, empty batch or K < 0");
-    GCA_CHECK_ARG(W == 256 || W == 512, "bulldozer_rollout: W must be 256 or 512 (the row-stream CA)");
-    GCA_CHECK_ARG(p->empty == 0 && p->empty < p->tree && p->tree < p->fire && p->fire < 256,
-                  "bulldozer_rollout: cell codes must be empty = 0 < tree < fire < 256 (the closed-form rule)");
-    GCA_CHECK_ARG(((((uintptr_t)buf0) | ((uintptr_t)buf1)) & 15u) == 0, "bulldozer_rollout: buffers 16-B aligned");
-    GCA_CHECK_ARG(wind_stride >= 0, "bulldozer_rollout: wind_stride >= 0");
-    GCA_CHECK_ARG((int64_t)K * E < ((int64_t)1 << 40), "bulldozer_rollout: K x E too large");
-    double tmax = 0.0;
-    for (int a = 0; a < 9; ++a)
-        for (int b = 0; b < 2; ++b) tmax = fmax(tmax, (p->t_move[a] + p->t_shoot[b]) + p->t_any);
-    GCA_CHECK_ARG(tmax < 1.0, "bulldozer_rollout: an action can take >= 1 time unit (several CA passes per step)");
+    const char* who = "bulldozer_rollout";
+    const bool have =
+        p && accu && steps && done && wind && rng_step && parity && buf0 && buf1 && pos && counts && hit && reward;
+    if (const int status = bdz_check_fused(who, have, p, E, H, W, buf0, buf1, wind_stride, &K)) return status;
     // gca_bulldozer_reset_where's checks (the reset's inputs and state are read only under autoreset)
     GCA_CHECK_ARG(buf0 != buf1, "bulldozer_rollout: buf0 and buf1 must differ");
     GCA_CHECK_ARG(H < 32768, "bulldozer_rollout: H < 32768");
@@ -1253,41 +1280,9 @@ extern "C" int gca_bulldozer_rollout(const gca_bulldozer_params* p, const int32_
                       "bulldozer_rollout: null argument (autoreset needs cdf, values, episode and steps_elapsed)");
         GCA_CHECK_ARG(p->env_offset >= 0, "bulldozer_rollout: env_offset >= 0");
     }
-    if (K == 0) return GCA_OK;
-    const int fsh = W == 256 ? FUSED_SH<1> : FUSED_SH<2>;
-    const int strips = (H + fsh - 1) / fsh;
-    const int threads = 64 * (strips < 16 ? strips : 16);
-    hipStream_t st = (hipStream_t)stream;
-    const bool std_codes = p->empty == 0 && p->tree == 3 && p->fire == 25;
-    // SOLO: Modify never changes the FIRE count (the kernel's comment)
-    bool solo = true;
-    for (int v = 0; v < 256; ++v) {
-        const int nv = p->effect[v];
-        if (nv >= 0 && (v == p->fire) != (nv == p->fire)) solo = false;
-    }
     const RolloutExt ext{actions, truncated_out, reset_seed, max_steps, cdf, values, episode, last_length, terminated,
                          truncated};
-#define GCA_ROLLOUT_LAUNCH(NWV, STDV, SOLOV, RESETV, ACTV)                                                             \
-    hipLaunchKernelGGL((bulldozer_rollout_random_kernel<NWV, STDV, SOLOV, true, RESETV, ACTV>), dim3((unsigned)E),     \
-                       dim3(threads), 0, st, *p, K, action_seed, action_out, reward_out, terminated_out, accu, steps,  \
-                       done, wind, wind_stride, rng_step, parity, buf0, buf1, H, pos, counts, hit, reward,             \
-                       steps_elapsed, E, ext)
-#define GCA_ROLLOUT_PICK(NWV, RESETV, ACTV)                                       \
-    do {                                                                          \
-        if (std_codes && solo) GCA_ROLLOUT_LAUNCH(NWV, true, true, RESETV, ACTV); \
-        else if (solo) GCA_ROLLOUT_LAUNCH(NWV, false, true, RESETV, ACTV);        \
-        else GCA_ROLLOUT_LAUNCH(NWV, false, false, RESETV, ACTV);                 \
-    } while (0)
-#define GCA_ROLLOUT_MODE(NWV)                                 \
-    do {                                                      \
-        if (autoreset) GCA_ROLLOUT_PICK(NWV, true, false);    \
-        else if (actions) GCA_ROLLOUT_PICK(NWV, false, true); \
-        else GCA_ROLLOUT_PICK(NWV, false, false);             \
-    } while (0)
-    if (W == 256) GCA_ROLLOUT_MODE(1); else GCA_ROLLOUT_MODE(2);
-#undef GCA_ROLLOUT_MODE
-#undef GCA_ROLLOUT_PICK
-#undef GCA_ROLLOUT_LAUNCH
-    GCA_CHECK_LAUNCH("bulldozer_rollout");
-    return GCA_OK;
+    return bulldozer_rollout_impl(who, true, autoreset, p, action_seed, K, action_out, reward_out, terminated_out, ext,
+                                  accu, steps, done, wind, wind_stride, rng_step, parity, buf0, buf1, H, W, pos, counts,
+                                  hit, reward, steps_elapsed, E, stream);
 }

@@ -137,3 +137,100 @@ def test_bound_call_converts_once_and_checks_arity():
         _lib.BoundCall("gca_bulldozer_step_fused", _lib.SLOT, *args[1:])
     with pytest.raises(TypeError):
         bc(0x4000)  # two per-call values expected
+
+
+# The fused bulldozer entry points' arguments by name, in each prototype's order (include/gca.h). Every call below is
+# refused by an argument check (or returns at K = 0) before any launch, so the pointers are never dereferenced.
+_STATE = ("accu", "steps", "done", "wind", "wind_stride", "rng_step", "parity", "buf0", "buf1", "H", "W", "pos", "counts",
+          "hit", "reward", "steps_elapsed")
+_FUSED_ORDER = {
+    "gca_bulldozer_step_fused": ("p", "action") + _STATE + ("meet", "E", "stream"),
+    "gca_bulldozer_step_fused_random": ("p", "action_seed", "action_out") + _STATE + ("meet", "E", "stream"),
+    "gca_bulldozer_rollout_random": ("p", "action_seed", "K", "action_out", "reward_out", "done_out") + _STATE +
+                                    ("E", "stream"),
+    "gca_bulldozer_rollout": ("p", "actions", "action_seed", "K", "action_out", "reward_out", "done_out", "truncated_out",
+                              "autoreset", "reset_seed", "max_steps", "cdf", "values", "episode", "last_length",
+                              "terminated", "truncated") + _STATE + ("E", "stream"),
+}
+_WHO = {"gca_bulldozer_step_fused": "bulldozer_step_fused", "gca_bulldozer_step_fused_random": "bulldozer_step_fused",
+        "gca_bulldozer_rollout_random": "bulldozer_rollout_random", "gca_bulldozer_rollout": "bulldozer_rollout"}
+_ROLLOUTS = ("gca_bulldozer_rollout_random", "gca_bulldozer_rollout")
+_T_STEP = ("an action can take >= 1 time unit (several CA passes per step): use gca_bulldozer_pre / gca_windy_step / "
+           "gca_bulldozer_post")
+_T_ROLL = "an action can take >= 1 time unit (several CA passes per step)"
+
+
+def _fused_call(name, **over):
+    """(status, message) of one fused bulldozer entry point with valid arguments but for `over` (p_* edits the params)."""
+    from gymca_amd import _lib
+    from gymca_amd.forest_fire.operators.move_modify import make_params
+
+    p = make_params(None, {3: 0})
+    p.empty, p.tree, p.fire, p.t_any = 0, 3, 25, 0.001
+    for a in range(9):
+        p.t_move[a] = 0.4
+    p.t_shoot[1] = 0.3
+    args = {n: 0x10000 + 0x100 * i for i, n in enumerate(
+        ("action", "action_out", "actions", "reward_out", "done_out", "truncated_out", "cdf", "values", "episode",
+         "last_length", "terminated", "truncated", "accu", "steps", "done", "wind", "rng_step", "parity", "buf0", "buf1",
+         "pos", "counts", "hit", "reward", "steps_elapsed", "meet"))}
+    args.update(p=p, action_seed=9, K=3, autoreset=0, reset_seed=5, max_steps=0, wind_stride=9, H=8, W=256, E=2,
+                stream=None)
+    for k, v in over.items():
+        if k.startswith("p_"):
+            setattr(p, k[2:], v)
+        else:
+            args[k] = v
+    lib = _lib.load()
+    status = getattr(lib, name)(*[args[n] for n in _FUSED_ORDER[name]])
+    return status, lib.gca_last_error().decode()
+
+
+@pytest.mark.parametrize("name", sorted(_FUSED_ORDER))
+def test_fused_bulldozer_argument_messages(name):
+    """Every argument check of gca_bulldozer_step_fused(_random), gca_bulldozer_rollout_random and gca_bulldozer_rollout:
+    the exact text a caller receives, per entry point, and which check fires first when several fail."""
+    who, roll = _WHO[name], name in _ROLLOUTS
+    null = "null argument, empty batch or K < 0" if roll else "null argument or empty batch"
+
+    def refused(text, **over):
+        status, msg = _fused_call(name, **over)
+        assert status == 1 and msg == f"argument: {who}: {text}", (over, status, msg)
+
+    for over in (dict(done=None), dict(p=None), dict(reward=None), dict(buf1=None), dict(E=0), dict(H=0),
+                 dict(done=None, W=128), dict(E=-1, buf0=0x10008)):
+        refused(null, **over)
+    refused("W must be 256 or 512 (the row-stream CA)", W=128)
+    refused("W must be 256 or 512 (the row-stream CA)", W=1024, buf0=0x10008, wind_stride=-1)
+    codes = "cell codes must be empty = 0 < tree < fire < 256 (the closed-form rule)"
+    for over in (dict(p_empty=1), dict(p_tree=25), dict(p_tree=30), dict(p_fire=256), dict(p_tree=0),
+                 dict(p_fire=256, buf1=0x10008)):
+        refused(codes, **over)
+    refused("buffers 16-B aligned", buf0=0x10008)
+    refused("buffers 16-B aligned", buf1=0x10004, wind_stride=-1)
+    refused("wind_stride >= 0", wind_stride=-1)
+    refused("wind_stride >= 0", wind_stride=-9, p_t_any=1.0)
+    refused(_T_ROLL if roll else _T_STEP, p_t_any=0.3)  # 0.4 + 0.3 + 0.3 >= 1
+    if roll:
+        refused(null, K=-1)
+        refused("K x E too large", K=2**31 - 1, E=2**10)
+        refused("K x E too large", K=2**31 - 1, E=2**10, p_t_any=0.3)
+        assert _fused_call(name, K=0)[0] == 0  # nothing to do: no launch
+    if name == "gca_bulldozer_step_fused":
+        refused("action required", action=None)
+        refused("action required", action=None, done=None, W=128)
+    if not roll:
+        refused("too many envs", E=2**29)  # with the meeting slots: 4 workgroups per env at the most
+    if name == "gca_bulldozer_rollout":
+        # the reset's own checks follow the shared ones, whether or not the call resets
+        refused("buf0 and buf1 must differ", buf1=0x10000 + 0x100 * 18)
+        refused(_T_ROLL, buf1=0x10000 + 0x100 * 18, p_t_any=0.3)
+        refused("H < 32768", H=32768)
+        refused("max_steps >= 0", max_steps=-1)
+        refused("max_steps >= 0", max_steps=-1, autoreset=1, cdf=None)
+        need = "null argument (autoreset needs cdf, values, episode and steps_elapsed)"
+        for over in (dict(cdf=None), dict(values=None), dict(episode=None), dict(steps_elapsed=None)):
+            refused(need, autoreset=1, **over)
+            assert _fused_call(name, K=0, **over)[0] == 0  # only read under autoreset
+        refused("env_offset >= 0", autoreset=1, p_env_offset=-1)
+        assert _fused_call(name, K=0, autoreset=1)[0] == 0
