@@ -18,6 +18,8 @@
 //   gca_policy_observation  the batched envs' policy observation (gca_policy_obs.hip), pinned by tests/_policy_obs_ref.py
 //   gca_helicopter_policy_act / gca_helicopter_policy_rollout  the policy network and the closed-loop rollout
 //                     (gca_heli.hip, gca_heli_policy_dev.h), in gca.h's summation order
+//   gca_gae / gca_helicopter_policy_grad(_workspace)  the PPO update (gca_ppo.hip): the GAE recurrence bit for bit, the
+//                     loss gradient in double as a second yardstick
 //   gca_philox        Random123 Philox4x32-10 (KAT hook)
 #include <math.h>
 #include <stdarg.h>
@@ -28,6 +30,7 @@
 #include <vector>
 
 #include "../../include/gca.h"
+#include "gca_ppo_plan.h"
 
 namespace {
 
@@ -621,5 +624,183 @@ extern "C" int gca_helicopter_policy_rollout(int empty, int tree, int fire, int 
                              rng_step, parity, buf0, buf1, H, W, pos, counts, hit, reward, steps_elapsed, E,
                              reward_out ? reward_out + o : nullptr, hit_out ? hit_out + o : nullptr);
     }
+    return GCA_OK;
+}
+
+// ---------------------------------------------------------------- the PPO update (gca.h "PPO update")
+// The recurrence of gca.h, one rounded f32 operation at a time (the file is built with -ffp-contract=off).
+extern "C" int gca_gae(const double* reward, const float* value, const float* next_value, const uint8_t* terminal,
+                       float gamma, float gamma_lambda, int K, int E, float* advantage, float* returns, void*) {
+    CPU_CHECK_ARG(K >= 0, "gae: K >= 0");
+    CPU_CHECK_ARG(E > 0, "gae: E > 0");
+    CPU_CHECK_ARG(reward && value && next_value && advantage && returns, "gae: null argument");
+    for (int e = 0; e < E; ++e) {
+        float A = 0.0f, nv = next_value[e];
+        for (int k = K - 1; k >= 0; --k) {
+            const size_t o = (size_t)k * E + e;
+            const float r = (float)reward[o];
+            const float nn = (terminal && terminal[o]) ? 0.0f : 1.0f;
+            const float v = value[o];
+            const float delta = (r + (gamma * nv) * nn) - v;
+            A = delta + (gamma_lambda * nn) * A;
+            advantage[o] = A;
+            returns[o] = A + v;
+            nv = v;
+        }
+    }
+    return GCA_OK;
+}
+
+extern "C" int64_t gca_helicopter_policy_grad_workspace(const gca_heli_policy* p, int C, int N) {
+    if (!p || p->radius < 0 || p->radius > 31 || p->hidden < 32 || p->hidden > 256 || (p->hidden & (p->hidden - 1)) ||
+        C < 2 || C % 2 || C > 15088 || N < 1) {
+        set_error("argument: %s", "helicopter_policy_grad_workspace: radius in [0, 31], hidden a power of two in "
+                                  "[32, 256], C = 2 Hc Wc at most 15088, N >= 1");
+        return -1;
+    }
+    const int S = 2 * p->radius + 1;
+    return ppo_plan(S * S, C, p->hidden, N).bytes;
+}
+
+static double lse9_host(const double* l) {
+    double m = l[0];
+    for (int i = 1; i < 9; ++i) m = l[i] > m ? l[i] : m;
+    double s = 0.0;
+    for (int i = 0; i < 9; ++i) s += exp(l[i] - m);
+    return m + log(s);
+}
+
+static bool ppo_overlap_host(const void* a, int64_t na, const void* b, int64_t nb) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
+}
+
+// Plain loops: the network, the loss and every gradient sum in double, rounded to f32 once. The workspace is checked
+// as on the device and not used.
+extern "C" int gca_helicopter_policy_grad(const gca_heli_policy* p, int C, const uint8_t* local, const float* coarse,
+                                          const int32_t* action, const float* old_logits, const float* advantage,
+                                          const float* returns, int64_t T, const int32_t* idx, int N, float clip_coef,
+                                          float ent_coef, float vf_coef, int norm_adv, float* g_w_local,
+                                          float* g_w_coarse, float* g_b1, float* g_w_out, float* g_b2, float* stats,
+                                          void* workspace, int64_t workspace_bytes, void*) {
+    if (const int st = policy_check_host(p)) return st;
+    CPU_CHECK_ARG(local && coarse && action && old_logits && advantage && returns,
+                  "helicopter_policy_grad: null record");
+    CPU_CHECK_ARG(g_w_local && g_w_coarse && g_b1 && g_w_out && g_b2 && stats && workspace,
+                  "helicopter_policy_grad: null output or workspace");
+    CPU_CHECK_ARG(C >= 2 && C % 2 == 0 && C <= 15088, "helicopter_policy_grad: C = 2 Hc Wc, at most 15088");
+    CPU_CHECK_ARG(T >= 1 && T < (1ll << 31), "helicopter_policy_grad: 1 <= T < 2^31");
+    CPU_CHECK_ARG(N >= 1, "helicopter_policy_grad: N >= 1");
+    CPU_CHECK_ARG(idx || N <= T, "helicopter_policy_grad: N <= T without idx");
+    CPU_CHECK_ARG(clip_coef >= 0.0f, "helicopter_policy_grad: clip_coef >= 0");
+    const int S = 2 * p->radius + 1, SS = S * S, Hd = p->hidden;
+    const PpoPlan pl = ppo_plan(SS, C, Hd, N);
+    CPU_CHECK_ARG(workspace_bytes >= pl.bytes,
+                  "helicopter_policy_grad: workspace smaller than gca_helicopter_policy_grad_workspace");
+    // the device's requirement, checked here too so that both builds refuse the same arguments
+    const uintptr_t aligned = (uintptr_t)workspace | (uintptr_t)p->w_local | (uintptr_t)p->w_coarse | (uintptr_t)p->b1;
+    CPU_CHECK_ARG((aligned & 15u) == 0,
+                  "helicopter_policy_grad: workspace, w_local, w_coarse and b1 16-B aligned");
+    const void* ptrs[11] = {g_w_local, g_w_coarse, g_b1, g_w_out, g_b2, stats,
+                            p->w_local, p->w_coarse, p->b1, p->w_out, p->b2};
+    const int64_t sizes[11] = {pl.off_wc * 4, (int64_t)C * Hd * 4, Hd * 4ll, Hd * 40ll, 40, 32,
+                               pl.off_wc * 4, (int64_t)C * Hd * 4, Hd * 4ll, Hd * 40ll, 40};
+    for (int i = 0; i < 6; ++i)
+        for (int j = i + 1; j < 11; ++j)
+            CPU_CHECK_ARG(!ppo_overlap_host(ptrs[i], sizes[i], ptrs[j], sizes[j]),
+                          "helicopter_policy_grad: the outputs may alias neither each other nor the weights");
+    if (idx)
+        for (int t = 0; t < N; ++t) CPU_CHECK_ARG(idx[t] >= 0 && idx[t] < T, "helicopter_policy_grad: idx outside [0, T)");
+    auto row_of = [&](int t) { return idx ? (size_t)idx[t] : (size_t)t; };
+    double mean = 0.0, var = 0.0;
+    for (int t = 0; t < N; ++t) mean += advantage[row_of(t)];
+    mean /= N;
+    for (int t = 0; t < N; ++t) {
+        const double d = advantage[row_of(t)] - mean;
+        var += d * d;
+    }
+    const double sd = sqrt(var / N), inv_n = 1.0 / N;
+    std::vector<double> gwl((size_t)SS * 4 * Hd, 0.0), gwc((size_t)C * Hd, 0.0), gb1(Hd, 0.0), gwo((size_t)Hd * 10, 0.0);
+    std::vector<double> a(Hd), h(Hd), da(Hd);
+    double gb2[10] = {0}, st[5] = {0};
+    for (int t = 0; t < N; ++t) {
+        const size_t row = row_of(t);
+        const uint8_t* loc = local + row * SS;
+        const float* co = coarse + row * C;
+        for (int j = 0; j < Hd; ++j) a[j] = p->b1[j];
+        for (int n = 0; n < SS; ++n) {
+            const float* w = p->w_local + ((size_t)n * 4 + (loc[n] & 3)) * Hd;
+            for (int j = 0; j < Hd; ++j) a[j] += w[j];
+        }
+        for (int c = 0; c < C; ++c) {
+            const float* w = p->w_coarse + (size_t)c * Hd;
+            const double x = co[c];
+            for (int j = 0; j < Hd; ++j) a[j] += w[j] * x;
+        }
+        double out[10], lo[9], d[10];
+        for (int o = 0; o < 10; ++o) out[o] = p->b2[o];
+        for (int j = 0; j < Hd; ++j) {
+            h[j] = a[j] > 0.0 ? a[j] : 0.0;
+            for (int o = 0; o < 10; ++o) out[o] += (double)p->w_out[j * 10 + o] * h[j];
+        }
+        for (int i = 0; i < 9; ++i) lo[i] = old_logits[row * 9 + i];
+        const int act = action[row] < 0 ? 0 : (action[row] > 8 ? 8 : action[row]);
+        const double lse = lse9_host(out), lse_old = lse9_host(lo);
+        const double logratio = (out[act] - lse) - (lo[act] - lse_old), ratio = exp(logratio);
+        double adv = advantage[row];
+        if (norm_adv) adv = (adv - mean) / (sd + 1e-8);
+        const double lo_c = 1.0 - (double)clip_coef, hi_c = 1.0 + (double)clip_coef;
+        const bool clipped = ratio < lo_c || ratio > hi_c;
+        const double pg1 = -adv * ratio, pg2 = -adv * (ratio < lo_c ? lo_c : (ratio > hi_c ? hi_c : ratio));
+        const double dpg_dr = (!clipped || pg1 > pg2) ? -adv : 0.0;
+        double pr[9], lp[9], ent = 0.0;
+        for (int i = 0; i < 9; ++i) {
+            lp[i] = out[i] - lse;
+            pr[i] = exp(lp[i]);
+            ent -= pr[i] * lp[i];
+        }
+        for (int i = 0; i < 9; ++i)
+            d[i] = (dpg_dr * ratio * ((i == act ? 1.0 : 0.0) - pr[i]) + (double)ent_coef * pr[i] * (lp[i] + ent)) * inv_n;
+        const double dv = out[9] - returns[row];
+        d[9] = (double)vf_coef * dv * inv_n;
+        st[0] += pg1 > pg2 ? pg1 : pg2;
+        st[1] += 0.5 * dv * dv;
+        st[2] += ent;
+        st[3] += (ratio - 1.0) - logratio;
+        st[4] += clipped ? 1.0 : 0.0;
+        for (int o = 0; o < 10; ++o) gb2[o] += d[o];
+        for (int j = 0; j < Hd; ++j) {
+            double dh = 0.0;
+            for (int o = 0; o < 10; ++o) {
+                gwo[(size_t)j * 10 + o] += h[j] * d[o];
+                dh += (double)p->w_out[j * 10 + o] * d[o];
+            }
+            da[j] = a[j] > 0.0 ? dh : 0.0;
+            gb1[j] += da[j];
+        }
+        for (int n = 0; n < SS; ++n) {
+            double* g = gwl.data() + ((size_t)n * 4 + (loc[n] & 3)) * Hd;
+            for (int j = 0; j < Hd; ++j) g[j] += da[j];
+        }
+        for (int c = 0; c < C; ++c) {
+            double* g = gwc.data() + (size_t)c * Hd;
+            const double x = co[c];
+            for (int j = 0; j < Hd; ++j) g[j] += x * da[j];
+        }
+    }
+    for (size_t i = 0; i < gwl.size(); ++i) g_w_local[i] = (float)gwl[i];
+    for (size_t i = 0; i < gwc.size(); ++i) g_w_coarse[i] = (float)gwc[i];
+    for (int j = 0; j < Hd; ++j) g_b1[j] = (float)gb1[j];
+    for (size_t i = 0; i < gwo.size(); ++i) g_w_out[i] = (float)gwo[i];
+    for (int o = 0; o < 10; ++o) g_b2[o] = (float)gb2[o];
+    const double pg = st[0] * inv_n, vl = st[1] * inv_n, en = st[2] * inv_n;
+    stats[0] = (float)(pg - (double)ent_coef * en + (double)vf_coef * vl);
+    stats[1] = (float)pg;
+    stats[2] = (float)vl;
+    stats[3] = (float)en;
+    stats[4] = (float)(st[3] * inv_n);
+    stats[5] = (float)(st[4] * inv_n);
+    stats[6] = (float)mean;
+    stats[7] = (float)sd;
     return GCA_OK;
 }

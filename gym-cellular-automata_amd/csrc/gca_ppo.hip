@@ -1,0 +1,613 @@
+// gca_ppo.hip — the learner's side of the helicopter policy (include/gca.h "PPO update"): gca_gae, the reference's
+// generalised advantage estimate in one launch, and gca_helicopter_policy_grad, the PPO clipped-surrogate loss, its
+// statistics and its gradient with respect to the five policy tensors over a minibatch of rollout_policy's records.
+//
+// gca_helicopter_policy_grad is four launches on the caller's stream, all sums in a fixed order (no atomics):
+//   adv     one workgroup: mean and population standard deviation of the minibatch's advantages (two passes, a
+//           sequential partial per thread, a tree over the threads) -> workspace header.
+//   fwd     one workgroup per tile of TS samples (64; 32 at Hd = 256). The tile's hidden layer is a tiled matvec: a
+//           thread owns four consecutive units of SPT samples; w_local goes through LDS in chunks of 1024 / Hd cells
+//           (16 KiB) with the chunk's class bytes, w_coarse in chunks of 32 rows with the tile's coarse values, so a
+//           weight row is loaded from L2 once per tile, not once per sample. Then relu -> LDS, the ten outputs (a
+//           thread per (sample, output), sixteen running sums over j mod 16 and a tree), the loss of each sample in one
+//           thread, d loss / d outputs, and d loss / d pre-activations. Writes da (N, Hd), h (N, Hd) and dout (N, 10) to the workspace
+//           and the tile's statistics and b2 gradient sums (a pairwise tree over the tile's samples).
+//   wgrad   G[r][j] = sum_s x[s][r] * D[s][j]: grid (row blocks, P sample splits). A thread owns one row r and four
+//           units: for a window cell the four class vectors (x the one-hot class: a select per class, so a class no
+//           sample selects stays exactly 0.0f), for a coarse row x = the coarse value, for b1 x = 1 (D = da), for a
+//           w_out column x = dout (D = h). Tiles of TS samples go through LDS; a tile's sum is added to the split's
+//           running sum per tile (the sums stay short: TS, then tiles per split, then P terms). Partials -> workspace.
+//   reduce  a thread per gradient element adds the P partials in increasing p; the last workgroup adds the tile
+//           partials (a sequential partial per thread over tiles t, t + 256, .., then a tree) into g_b2 and the stats.
+// fmaf is written out where a fused multiply-add is wanted (the build runs with -ffp-contract=off).
+#include "gca_common.h"
+#include "gca_ppo_plan.h"
+
+#define PPO_THREADS 256
+
+// ------------------------------------------------------------------ GAE
+__global__ __launch_bounds__(PPO_THREADS) void gae_kernel(const double* __restrict__ reward,
+                                                          const float* __restrict__ value,
+                                                          const float* __restrict__ next_value,
+                                                          const uint8_t* __restrict__ terminal, float gamma,
+                                                          float gamma_lambda, int K, int E,
+                                                          float* __restrict__ advantage, float* __restrict__ returns) {
+    const int e = blockIdx.x * PPO_THREADS + threadIdx.x;
+    if (e >= E) return;
+    float A = 0.0f, nv = next_value[e];
+    for (int k = K - 1; k >= 0; --k) {
+        const size_t o = (size_t)k * E + e;
+        const float r = (float)reward[o];
+        const float nn = (terminal && terminal[o]) ? 0.0f : 1.0f;
+        const float v = value[o];
+        const float delta = (r + (gamma * nv) * nn) - v;
+        A = delta + (gamma_lambda * nn) * A;
+        advantage[o] = A;
+        returns[o] = A + v;
+        nv = v;
+    }
+}
+
+extern "C" int gca_gae(const double* reward, const float* value, const float* next_value, const uint8_t* terminal,
+                       float gamma, float gamma_lambda, int K, int E, float* advantage, float* returns, void* stream) {
+    GCA_CHECK_ARG(K >= 0, "gae: K >= 0");
+    GCA_CHECK_ARG(E > 0, "gae: E > 0");
+    GCA_CHECK_ARG(reward && value && next_value && advantage && returns, "gae: null argument");
+    if (K == 0) return GCA_OK;
+    hipLaunchKernelGGL(gae_kernel, dim3((unsigned)((E + PPO_THREADS - 1) / PPO_THREADS)), dim3(PPO_THREADS), 0,
+                       (hipStream_t)stream, reward, value, next_value, terminal, gamma, gamma_lambda, K, E, advantage,
+                       returns);
+    GCA_CHECK_LAUNCH("gae");
+    return GCA_OK;
+}
+
+// ------------------------------------------------------------------ the minibatch
+struct PpoBatch {
+    const uint8_t* __restrict__ local;      // [T][SS]
+    const float* __restrict__ coarse;       // [T][C]
+    const int32_t* __restrict__ action;     // [T]
+    const float* __restrict__ old_logits;   // [T][9]
+    const float* __restrict__ advantage;    // [T]
+    const float* __restrict__ returns;      // [T]
+    const int32_t* __restrict__ idx;        // [N] or null
+    int N, T, SS, C;
+};
+
+// The record row of minibatch sample t < N. An index outside [0, T) cannot be refused without a sync: it is clamped,
+// so no address leaves the records.
+__device__ __forceinline__ int ppo_row(const PpoBatch& b, int t) {
+    return b.idx ? min(max(b.idx[t], 0), b.T - 1) : t;
+}
+
+// ------------------------------------------------------------------ adv: mean and standard deviation
+constexpr int PPO_ADV_THREADS = 1024;
+
+__device__ __forceinline__ float ppo_block_sum(float v, float* red, int tid) {
+    __syncthreads();  // the previous use of red
+    red[tid] = v;
+    __syncthreads();
+    for (int s = PPO_ADV_THREADS / 2; s >= 1; s >>= 1) {
+        if (tid < s) red[tid] = red[tid] + red[tid + s];
+        __syncthreads();
+    }
+    return red[0];
+}
+
+__global__ __launch_bounds__(PPO_ADV_THREADS) void ppo_adv_kernel(PpoBatch b, float* __restrict__ hdr) {
+    __shared__ float red[PPO_ADV_THREADS];
+    const int tid = threadIdx.x;
+    float s = 0.0f;
+    for (int t = tid; t < b.N; t += PPO_ADV_THREADS) s = s + b.advantage[ppo_row(b, t)];
+    const float mean = ppo_block_sum(s, red, tid) / (float)b.N;
+    float q = 0.0f;
+    for (int t = tid; t < b.N; t += PPO_ADV_THREADS) {
+        const float d = b.advantage[ppo_row(b, t)] - mean;
+        q = fmaf(d, d, q);
+    }
+    const float var = ppo_block_sum(q, red, tid) / (float)b.N;
+    if (tid == 0) {
+        hdr[0] = mean;
+        hdr[1] = sqrtf(var);
+    }
+}
+
+// ------------------------------------------------------------------ fwd: forward, loss, d loss / d pre-activations
+template <int HD>
+struct PpoCfg {
+    static constexpr int TS = HD == 256 ? 32 : 64;  // samples per tile (ppo_plan's TS)
+    static constexpr int Q = HD / 4;                // threads per hidden vector (four units each)
+    static constexpr int R = PPO_THREADS / Q;       // sample groups of the workgroup = rows per wgrad workgroup
+    static constexpr int SPT = TS / R;              // samples per thread
+    static constexpr int CH = 1024 / HD;            // window cells per w_local chunk: CH * 4 * HD = 4096 floats
+    static constexpr int CC = 32;                   // coarse rows per w_coarse chunk
+    static constexpr int WBUF = (CC * HD > 4096) ? CC * HD : 4096;  // floats of the weight chunk
+    static constexpr int XST = CC + 1;              // row stride of the tile's coarse chunk (odd: no bank conflicts)
+    static constexpr int HST = HD + 1;              // row stride of the tile's hidden vectors
+    static constexpr int UNI = (WBUF + TS * XST > TS * HST) ? WBUF + TS * XST : TS * HST;  // the two share LDS
+};
+
+struct PpoLossArgs {
+    float clip_coef, ent_coef, vf_coef, inv_n;
+    int norm_adv;
+};
+
+// The loss of ONE sample is a chain of scalar operations in one thread with two cancellations (logp_new - logp_old,
+// and the mean of pg under normalised advantages, whose terms nearly cancel): it runs in double and is rounded to f32
+// once per term. Every sum over samples, units or inputs is f32.
+// logsumexp of nine logits: the maximum, the sum of exp(l_i - max) left to right, max + log(sum)
+__device__ __forceinline__ double ppo_lse9(const double (&l)[9]) {
+    double m = l[0];
+#pragma unroll
+    for (int i = 1; i < 9; ++i) m = fmax(m, l[i]);
+    double s = 0.0;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) s = s + exp(l[i] - m);
+    return m + log(s);
+}
+
+__device__ __forceinline__ double ppo_pick9(const double (&l)[9], int a) {
+    double v = l[0];
+#pragma unroll
+    for (int i = 1; i < 9; ++i) v = (a == i) ? l[i] : v;
+    return v;
+}
+
+template <int HD>
+__global__ __launch_bounds__(PPO_THREADS) void ppo_fwd_kernel(
+    PpoBatch b, const float* __restrict__ w_local, const float* __restrict__ w_coarse, const float* __restrict__ b1,
+    const float* __restrict__ w_out, const float* __restrict__ b2, PpoLossArgs la, const float* __restrict__ hdr,
+    float* __restrict__ DA, float* __restrict__ H, float* __restrict__ DO, float* __restrict__ TP) {
+    using Cf = PpoCfg<HD>;
+    constexpr int TS = Cf::TS, Q = Cf::Q, R = Cf::R, SPT = Cf::SPT, CH = Cf::CH, CC = Cf::CC;
+    __shared__ __attribute__((aligned(16))) float uni[Cf::UNI];  // weight chunk + x chunk, later the hidden vectors
+    __shared__ float wo[HD * 10 + 12];                           // w_out, then b2
+    __shared__ float outs[TS * 11], douts[TS * 11], tsum[TS * PPO_TP];
+    __shared__ int rows[TS];
+    float* const wbuf = uni;
+    float* const xs = uni + Cf::WBUF;
+    uint8_t* const clsb = reinterpret_cast<uint8_t*>(xs);  // TS * CH <= 2048 bytes
+    float* const hs = uni;
+
+    const int tid = threadIdx.x, jq = tid % Q, sg = tid / Q;
+    const int64_t t0 = (int64_t)blockIdx.x * TS;
+    const int SS = b.SS, C = b.C;
+    for (int i = tid; i < HD * 10; i += PPO_THREADS) wo[i] = w_out[i];
+    if (tid < 10) wo[HD * 10 + tid] = b2[tid];
+    if (tid < TS) rows[tid] = t0 + tid < b.N ? ppo_row(b, (int)(t0 + tid)) : 0;
+    __syncthreads();
+
+    // a chunk's terms are summed on their own (acc) and the chunk's sum is added to the running sum (tot): no chain of
+    // additions is longer than a chunk plus the number of chunks, which keeps the f32 rounding of the pre-activations at
+    // the level of a blocked matmul
+    float4 acc[SPT], tot[SPT];
+#pragma unroll
+    for (int i = 0; i < SPT; ++i) tot[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    // the window: chunks of CH cells, their 4 x HD weights and the tile's class bytes through LDS
+    for (int c0 = 0; c0 < SS; c0 += CH) {
+        const int cnt = min(CH, SS - c0);
+        const float4* __restrict__ src = reinterpret_cast<const float4*>(w_local + (size_t)c0 * 4 * HD);
+        for (int i = tid; i < cnt * HD; i += PPO_THREADS) reinterpret_cast<float4*>(wbuf)[i] = src[i];
+        for (int i = tid; i < TS * CH; i += PPO_THREADS) {
+            const int s = i / CH, c = i % CH;
+            clsb[i] = c < cnt ? (b.local[(size_t)rows[s] * SS + c0 + c] & 3) : 0;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < SPT; ++i) acc[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        for (int c = 0; c < cnt; ++c) {
+#pragma unroll
+            for (int i = 0; i < SPT; ++i) {
+                const int cls = clsb[(sg + R * i) * CH + c];
+                const float4 w = reinterpret_cast<const float4*>(wbuf)[(c * 4 + cls) * Q + jq];
+                acc[i].x += w.x;
+                acc[i].y += w.y;
+                acc[i].z += w.z;
+                acc[i].w += w.w;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < SPT; ++i) {
+            tot[i].x += acc[i].x;
+            tot[i].y += acc[i].y;
+            tot[i].z += acc[i].z;
+            tot[i].w += acc[i].w;
+        }
+        __syncthreads();
+    }
+    // the coarse map: chunks of CC rows of w_coarse and the tile's CC coarse values per sample
+    for (int c0 = 0; c0 < C; c0 += CC) {
+        const int cnt = min(CC, C - c0);
+        const float4* __restrict__ src = reinterpret_cast<const float4*>(w_coarse + (size_t)c0 * HD);
+        for (int i = tid; i < cnt * Q; i += PPO_THREADS) reinterpret_cast<float4*>(wbuf)[i] = src[i];
+        for (int i = tid; i < TS * CC; i += PPO_THREADS) {
+            const int s = i / CC, c = i % CC;
+            xs[s * Cf::XST + c] = c < cnt ? b.coarse[(size_t)rows[s] * C + c0 + c] : 0.0f;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < SPT; ++i) acc[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        for (int c = 0; c < cnt; ++c) {
+            const float4 w = reinterpret_cast<const float4*>(wbuf)[c * Q + jq];
+#pragma unroll
+            for (int i = 0; i < SPT; ++i) {
+                const float x = xs[(sg + R * i) * Cf::XST + c];
+                acc[i].x = fmaf(w.x, x, acc[i].x);
+                acc[i].y = fmaf(w.y, x, acc[i].y);
+                acc[i].z = fmaf(w.z, x, acc[i].z);
+                acc[i].w = fmaf(w.w, x, acc[i].w);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < SPT; ++i) {
+            tot[i].x += acc[i].x;
+            tot[i].y += acc[i].y;
+            tot[i].z += acc[i].z;
+            tot[i].w += acc[i].w;
+        }
+        __syncthreads();
+    }
+    // relu; the hidden vectors to LDS (over the weight chunk: the barrier above ended its last read) and to the workspace
+    const float4 bb = reinterpret_cast<const float4*>(b1)[jq];
+    uint32_t posmask = 0;  // bit 4 i + k: unit 4 jq + k of sample i is active
+#pragma unroll
+    for (int i = 0; i < SPT; ++i) {
+        const int s = sg + R * i;
+        const bool valid = t0 + s < b.N;
+        float a[4] = {tot[i].x + bb.x, tot[i].y + bb.y, tot[i].z + bb.z, tot[i].w + bb.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const bool on = valid && a[k] > 0.0f;
+            posmask |= on ? (1u << (4 * i + k)) : 0u;
+            a[k] = on ? a[k] : 0.0f;
+            hs[s * Cf::HST + 4 * jq + k] = a[k];
+        }
+        reinterpret_cast<float4*>(H + (size_t)(t0 + s) * HD)[jq] = make_float4(a[0], a[1], a[2], a[3]);
+    }
+    __syncthreads();
+    // the ten outputs: a thread per (sample, output)
+    {
+        const int s = tid % TS;
+        for (int o = tid / TS; o < 10; o += PPO_THREADS / TS) {
+            float q[16];  // sixteen running sums over j mod 16, then a pairwise tree: no chain longer than HD / 16 + 4
+#pragma unroll
+            for (int k = 0; k < 16; ++k) q[k] = 0.0f;
+            const float* hrow = hs + s * Cf::HST;
+#pragma unroll 1
+            for (int j = 0; j < HD; j += 16) {
+#pragma unroll
+                for (int k = 0; k < 16; ++k) q[k] = fmaf(wo[(j + k) * 10 + o], hrow[j + k], q[k]);
+            }
+#pragma unroll
+            for (int half = 8; half >= 1; half >>= 1)
+#pragma unroll
+                for (int k = 0; k < half; ++k) q[k] = q[k] + q[k + half];
+            outs[s * 11 + o] = wo[HD * 10 + o] + q[0];
+        }
+    }
+    __syncthreads();
+    // the loss of one sample per thread
+    if (tid < TS) {
+        const int s = tid;
+        const bool valid = t0 + s < b.N;
+        float d[10], st[5];
+#pragma unroll
+        for (int o = 0; o < 10; ++o) d[o] = 0.0f;
+#pragma unroll
+        for (int o = 0; o < 5; ++o) st[o] = 0.0f;
+        if (valid) {
+            const int row = rows[s];
+            double l[9], lo[9];
+#pragma unroll
+            for (int i = 0; i < 9; ++i) {
+                l[i] = (double)outs[s * 11 + i];
+                lo[i] = (double)b.old_logits[(size_t)row * 9 + i];
+            }
+            const int a = min(max(b.action[row], 0), 8);
+            const double lse = ppo_lse9(l), lse_old = ppo_lse9(lo);
+            const double logratio = (ppo_pick9(l, a) - lse) - (ppo_pick9(lo, a) - lse_old);
+            const double ratio = exp(logratio);
+            double adv = (double)b.advantage[row];
+            if (la.norm_adv) adv = (adv - (double)hdr[0]) / ((double)hdr[1] + 1e-8);
+            const double lo_c = 1.0 - (double)la.clip_coef, hi_c = 1.0 + (double)la.clip_coef;
+            const bool clipped = ratio < lo_c || ratio > hi_c;
+            const double pg1 = -adv * ratio, pg2 = -adv * fmin(fmax(ratio, lo_c), hi_c);
+            const double dpg_dr = (!clipped || pg1 > pg2) ? -adv : 0.0;
+            double p[9], lp[9], ent = 0.0;
+#pragma unroll
+            for (int i = 0; i < 9; ++i) {
+                lp[i] = l[i] - lse;
+                p[i] = exp(lp[i]);
+                ent = ent - p[i] * lp[i];
+            }
+            const double g = dpg_dr * ratio, inv_n = 1.0 / (double)b.N;
+#pragma unroll
+            for (int i = 0; i < 9; ++i) {
+                const double onehot = (a == i) ? 1.0 : 0.0;
+                d[i] = (float)((g * (onehot - p[i]) + (double)la.ent_coef * (p[i] * (lp[i] + ent))) * inv_n);
+            }
+            const double dv = (double)outs[s * 11 + 9] - (double)b.returns[row];
+            d[9] = (float)(((double)la.vf_coef * dv) * inv_n);
+            st[0] = (float)fmax(pg1, pg2);
+            st[1] = (float)(0.5 * dv * dv);
+            st[2] = (float)ent;
+            st[3] = (float)((ratio - 1.0) - logratio);
+            st[4] = clipped ? 1.0f : 0.0f;
+        }
+#pragma unroll
+        for (int o = 0; o < 10; ++o) {
+            douts[s * 11 + o] = d[o];
+            DO[(size_t)(t0 + s) * 10 + o] = d[o];
+        }
+#pragma unroll
+        for (int o = 0; o < 5; ++o) tsum[s * PPO_TP + o] = st[o];
+#pragma unroll
+        for (int o = 0; o < 10; ++o) tsum[s * PPO_TP + 5 + o] = d[o];
+        tsum[s * PPO_TP + 15] = 0.0f;
+    }
+    __syncthreads();
+    // the tile's partial sums: a pairwise tree over the samples (s += s + half), the same order on every call
+    for (int half = TS / 2; half >= 1; half >>= 1) {
+        for (int i = tid; i < half * PPO_TP; i += PPO_THREADS) tsum[i] = tsum[i] + tsum[i + half * PPO_TP];
+        __syncthreads();
+    }
+    if (tid < PPO_TP) TP[(size_t)blockIdx.x * PPO_TP + tid] = tsum[tid];
+    // d loss / d pre-activation = relu'(a) * sum_o w_out[j][o] * dout[o]
+    float wr[4][10];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+        for (int o = 0; o < 10; ++o) wr[k][o] = wo[(4 * jq + k) * 10 + o];
+#pragma unroll
+    for (int i = 0; i < SPT; ++i) {
+        const int s = sg + R * i;
+        float da[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int o = 0; o < 10; ++o) {
+            const float dd = douts[s * 11 + o];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) da[k] = fmaf(wr[k][o], dd, da[k]);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) da[k] = ((posmask >> (4 * i + k)) & 1u) ? da[k] : 0.0f;
+        reinterpret_cast<float4*>(DA + (size_t)(t0 + s) * HD)[jq] = make_float4(da[0], da[1], da[2], da[3]);
+    }
+}
+
+// ------------------------------------------------------------------ wgrad: partial weight gradients
+template <int HD>
+__global__ __launch_bounds__(PPO_THREADS) void ppo_wgrad_kernel(PpoBatch b, PpoPlan pl, const float* __restrict__ DA,
+                                                                const float* __restrict__ H,
+                                                                const float* __restrict__ DO,
+                                                                float* __restrict__ part) {
+    using Cf = PpoCfg<HD>;
+    constexpr int TS = Cf::TS, Q = Cf::Q, R = Cf::R;
+    __shared__ __attribute__((aligned(16))) float dt[TS * HD];
+    __shared__ uint32_t xt[TS * R];
+    const int tid = threadIdx.x, jq = tid % Q, rl = tid / Q;
+    const int blk = blockIdx.x, SS = b.SS, C = b.C;
+    // kind 0: window cells (x = class), 1: coarse rows and b1 (x = coarse value / 1), 2: w_out columns (x = dout, D = h)
+    const int kind = blk < pl.nbL ? 0 : (blk < pl.nbL + pl.nbC ? 1 : 2);
+    const int r0 = (kind == 0 ? blk : kind == 1 ? blk - pl.nbL : blk - pl.nbL - pl.nbC) * R;
+    const int nrows = kind == 0 ? SS : kind == 1 ? C + 1 : 10;
+    const float* __restrict__ D = kind == 2 ? H : DA;
+    const int64_t tile0 = (int64_t)blockIdx.y * pl.tps;
+    const int64_t tile1 = min(tile0 + pl.tps, pl.ntiles);
+    float4 tot[4], acc[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) tot[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    for (int64_t tile = tile0; tile < tile1; ++tile) {
+        const int64_t t0 = tile * TS;
+        const float4* __restrict__ src = reinterpret_cast<const float4*>(D + (size_t)t0 * HD);
+        for (int i = tid; i < TS * Q; i += PPO_THREADS) reinterpret_cast<float4*>(dt)[i] = src[i];
+        for (int i = tid; i < TS * R; i += PPO_THREADS) {
+            const int s = i / R, r = r0 + i % R;
+            uint32_t x = 0u;  // a row past the block's last, or a sample past N (its D row is zero)
+            if (r < nrows && t0 + s < b.N) {
+                if (kind == 2) {
+                    x = __float_as_uint(DO[(size_t)(t0 + s) * 10 + r]);
+                } else {
+                    const int row = ppo_row(b, (int)(t0 + s));
+                    if (kind == 0) x = b.local[(size_t)row * SS + r] & 3u;
+                    else x = r < C ? __float_as_uint(b.coarse[(size_t)row * C + r]) : __float_as_uint(1.0f);
+                }
+            }
+            xt[i] = x;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < 4; ++k) acc[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (kind == 0) {
+#pragma unroll 4
+            for (int s = 0; s < TS; ++s) {
+                const float4 d = reinterpret_cast<const float4*>(dt)[s * Q + jq];
+                const uint32_t c = xt[s * R + rl];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const bool on = c == (uint32_t)k;  // a select, not a 0 / 1 factor: 0 * Inf would be NaN
+                    acc[k].x += on ? d.x : 0.0f;
+                    acc[k].y += on ? d.y : 0.0f;
+                    acc[k].z += on ? d.z : 0.0f;
+                    acc[k].w += on ? d.w : 0.0f;
+                }
+            }
+        } else {
+#pragma unroll 4
+            for (int s = 0; s < TS; ++s) {
+                const float4 d = reinterpret_cast<const float4*>(dt)[s * Q + jq];
+                const float x = __uint_as_float(xt[s * R + rl]);
+                acc[0].x = fmaf(x, d.x, acc[0].x);
+                acc[0].y = fmaf(x, d.y, acc[0].y);
+                acc[0].z = fmaf(x, d.z, acc[0].z);
+                acc[0].w = fmaf(x, d.w, acc[0].w);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            tot[k].x += acc[k].x;
+            tot[k].y += acc[k].y;
+            tot[k].z += acc[k].z;
+            tot[k].w += acc[k].w;
+        }
+        __syncthreads();
+    }
+    const int r = r0 + rl;
+    if (r >= nrows) return;
+    float* __restrict__ out = part + (size_t)blockIdx.y * pl.GF;
+    if (kind == 0) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) reinterpret_cast<float4*>(out + pl.off_wl + ((size_t)r * 4 + k) * HD)[jq] = tot[k];
+    } else if (kind == 1) {
+        // row C of this kind is b1, which follows w_coarse in the partial
+        reinterpret_cast<float4*>(out + pl.off_wc + (size_t)r * HD)[jq] = tot[0];
+    } else {
+        float* o = out + pl.off_wo + (size_t)(4 * jq) * 10 + r;
+        o[0] = tot[0].x;
+        o[10] = tot[0].y;
+        o[20] = tot[0].z;
+        o[30] = tot[0].w;
+    }
+}
+
+// ------------------------------------------------------------------ reduce: the partials, g_b2 and the stats
+struct PpoOut {
+    float *g_w_local, *g_w_coarse, *g_b1, *g_w_out, *g_b2, *stats;
+};
+
+__global__ __launch_bounds__(PPO_THREADS) void ppo_reduce_kernel(PpoPlan pl, PpoLossArgs la,
+                                                                 const float* __restrict__ part,
+                                                                 const float* __restrict__ TP,
+                                                                 const float* __restrict__ hdr, PpoOut out,
+                                                                 int elem_blocks) {
+    const int tid = threadIdx.x;
+    if ((int)blockIdx.x < elem_blocks) {
+        const int64_t e = (int64_t)blockIdx.x * PPO_THREADS + tid;
+        if (e >= pl.GF) return;
+        float s = 0.0f;
+        for (int p = 0; p < pl.P; ++p) s = s + part[(size_t)p * pl.GF + e];
+        if (e < pl.off_wc) out.g_w_local[e] = s;
+        else if (e < pl.off_b1) out.g_w_coarse[e - pl.off_wc] = s;
+        else if (e < pl.off_wo) out.g_b1[e - pl.off_b1] = s;
+        else out.g_w_out[e - pl.off_wo] = s;
+        return;
+    }
+    __shared__ float red[PPO_THREADS * PPO_TP];
+    float s[PPO_TP];
+#pragma unroll
+    for (int q = 0; q < PPO_TP; ++q) s[q] = 0.0f;
+    for (int64_t t = tid; t < pl.ntiles; t += PPO_THREADS) {
+#pragma unroll
+        for (int q = 0; q < 15; ++q) s[q] = s[q] + TP[(size_t)t * PPO_TP + q];
+    }
+#pragma unroll
+    for (int q = 0; q < PPO_TP; ++q) red[tid * PPO_TP + q] = s[q];
+    __syncthreads();
+    for (int st = PPO_THREADS / 2; st >= 1; st >>= 1) {
+        if (tid < st)
+            for (int q = 0; q < 15; ++q) red[tid * PPO_TP + q] = red[tid * PPO_TP + q] + red[(tid + st) * PPO_TP + q];
+        __syncthreads();
+    }
+    if (tid < 10) out.g_b2[tid] = red[5 + tid];
+    if (tid == 0) {
+        const float pg = red[0] * la.inv_n, vl = red[1] * la.inv_n, ent = red[2] * la.inv_n;
+        out.stats[0] = (pg - la.ent_coef * ent) + la.vf_coef * vl;
+        out.stats[1] = pg;
+        out.stats[2] = vl;
+        out.stats[3] = ent;
+        out.stats[4] = red[3] * la.inv_n;
+        out.stats[5] = red[4] * la.inv_n;
+        out.stats[6] = hdr[0];
+        out.stats[7] = hdr[1];
+    }
+}
+
+// ------------------------------------------------------------------ host side
+static int ppo_check_policy(const gca_heli_policy* p) {
+    GCA_CHECK_ARG(p && p->w_local && p->w_coarse && p->b1 && p->w_out && p->b2, "helicopter_policy: null weights");
+    GCA_CHECK_ARG(p->radius >= 0 && p->radius <= 31, "helicopter_policy: radius in [0, 31]");
+    GCA_CHECK_ARG(p->block >= 1 && p->block <= 64 && (p->block & (p->block - 1)) == 0,
+                  "helicopter_policy: block must be a power of two in [1, 64]");
+    GCA_CHECK_ARG(p->hidden >= 32 && p->hidden <= 256 && (p->hidden & (p->hidden - 1)) == 0,
+                  "helicopter_policy: hidden must be a power of two in [32, 256]");
+    return GCA_OK;
+}
+
+extern "C" int64_t gca_helicopter_policy_grad_workspace(const gca_heli_policy* p, int C, int N) {
+    if (!p || p->radius < 0 || p->radius > 31 || p->hidden < 32 || p->hidden > 256 || (p->hidden & (p->hidden - 1)) ||
+        C < 2 || C % 2 || C > 15088 || N < 1) {
+        gca_set_error("argument: %s", "helicopter_policy_grad_workspace: radius in [0, 31], hidden a power of two in "
+                                      "[32, 256], C = 2 Hc Wc at most 15088, N >= 1");
+        return -1;
+    }
+    const int S = 2 * p->radius + 1;
+    return ppo_plan(S * S, C, p->hidden, N).bytes;
+}
+
+static bool ppo_overlap(const void* a, int64_t na, const void* b, int64_t nb) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
+}
+
+template <int HD>
+static void ppo_launch(const PpoBatch& b, const PpoPlan& pl, const gca_heli_policy* p, const PpoLossArgs& la,
+                       const PpoOut& out, char* ws, hipStream_t st) {
+    float* hdr = reinterpret_cast<float*>(ws);
+    float* DA = reinterpret_cast<float*>(ws + pl.off_da);
+    float* H = reinterpret_cast<float*>(ws + pl.off_h);
+    float* DO = reinterpret_cast<float*>(ws + pl.off_do);
+    float* TP = reinterpret_cast<float*>(ws + pl.off_tp);
+    float* part = reinterpret_cast<float*>(ws + pl.off_part);
+    hipLaunchKernelGGL(ppo_adv_kernel, dim3(1), dim3(PPO_ADV_THREADS), 0, st, b, hdr);
+    hipLaunchKernelGGL(ppo_fwd_kernel<HD>, dim3((unsigned)pl.ntiles), dim3(PPO_THREADS), 0, st, b, p->w_local,
+                       p->w_coarse, p->b1, p->w_out, p->b2, la, hdr, DA, H, DO, TP);
+    hipLaunchKernelGGL(ppo_wgrad_kernel<HD>, dim3((unsigned)pl.nb, (unsigned)pl.P), dim3(PPO_THREADS), 0, st, b, pl, DA,
+                       H, DO, part);
+    const int elem_blocks = (int)((pl.GF + PPO_THREADS - 1) / PPO_THREADS);
+    hipLaunchKernelGGL(ppo_reduce_kernel, dim3((unsigned)elem_blocks + 1), dim3(PPO_THREADS), 0, st, pl, la, part, TP,
+                       hdr, out, elem_blocks);
+}
+
+extern "C" int gca_helicopter_policy_grad(const gca_heli_policy* p, int C, const uint8_t* local, const float* coarse,
+                                          const int32_t* action, const float* old_logits, const float* advantage,
+                                          const float* returns, int64_t T, const int32_t* idx, int N, float clip_coef,
+                                          float ent_coef, float vf_coef, int norm_adv, float* g_w_local,
+                                          float* g_w_coarse, float* g_b1, float* g_w_out, float* g_b2, float* stats,
+                                          void* workspace, int64_t workspace_bytes, void* stream) {
+    if (const int st = ppo_check_policy(p)) return st;
+    GCA_CHECK_ARG(local && coarse && action && old_logits && advantage && returns,
+                  "helicopter_policy_grad: null record");
+    GCA_CHECK_ARG(g_w_local && g_w_coarse && g_b1 && g_w_out && g_b2 && stats && workspace,
+                  "helicopter_policy_grad: null output or workspace");
+    GCA_CHECK_ARG(C >= 2 && C % 2 == 0 && C <= 15088, "helicopter_policy_grad: C = 2 Hc Wc, at most 15088");
+    GCA_CHECK_ARG(T >= 1 && T < (1ll << 31), "helicopter_policy_grad: 1 <= T < 2^31");
+    GCA_CHECK_ARG(N >= 1, "helicopter_policy_grad: N >= 1");
+    GCA_CHECK_ARG(idx || N <= T, "helicopter_policy_grad: N <= T without idx");
+    GCA_CHECK_ARG(clip_coef >= 0.0f, "helicopter_policy_grad: clip_coef >= 0");
+    const int S = 2 * p->radius + 1, SS = S * S, Hd = p->hidden;
+    const PpoPlan pl = ppo_plan(SS, C, Hd, N);
+    GCA_CHECK_ARG(workspace_bytes >= pl.bytes,
+                  "helicopter_policy_grad: workspace smaller than gca_helicopter_policy_grad_workspace");
+    const uintptr_t aligned = (uintptr_t)workspace | (uintptr_t)p->w_local | (uintptr_t)p->w_coarse | (uintptr_t)p->b1;
+    GCA_CHECK_ARG((aligned & 15u) == 0,
+                  "helicopter_policy_grad: workspace, w_local, w_coarse and b1 16-B aligned");
+    const void* ptrs[11] = {g_w_local, g_w_coarse, g_b1, g_w_out, g_b2, stats,
+                            p->w_local, p->w_coarse, p->b1, p->w_out, p->b2};
+    const int64_t sizes[11] = {pl.off_wc * 4, (int64_t)C * Hd * 4, Hd * 4ll, Hd * 40ll, 40, 32,
+                               pl.off_wc * 4, (int64_t)C * Hd * 4, Hd * 4ll, Hd * 40ll, 40};
+    for (int i = 0; i < 6; ++i)
+        for (int j = i + 1; j < 11; ++j)
+            GCA_CHECK_ARG(!ppo_overlap(ptrs[i], sizes[i], ptrs[j], sizes[j]),
+                          "helicopter_policy_grad: the outputs may alias neither each other nor the weights");
+    PpoBatch b{local, coarse, action, old_logits, advantage, returns, idx, N, (int)T, SS, C};
+    const PpoLossArgs la{clip_coef, ent_coef, vf_coef, 1.0f / (float)N, norm_adv ? 1 : 0};
+    const PpoOut out{g_w_local, g_w_coarse, g_b1, g_w_out, g_b2, stats};
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = reinterpret_cast<char*>(workspace);
+    switch (Hd) {
+        case 32: ppo_launch<32>(b, pl, p, la, out, ws, st); break;
+        case 64: ppo_launch<64>(b, pl, p, la, out, ws, st); break;
+        case 128: ppo_launch<128>(b, pl, p, la, out, ws, st); break;
+        default: ppo_launch<256>(b, pl, p, la, out, ws, st); break;
+    }
+    GCA_CHECK_LAUNCH("helicopter_policy_grad");
+    return GCA_OK;
+}

@@ -257,6 +257,10 @@ _SIGNATURES = {
     "gca_helicopter_policy_rollout": ([c_int, c_int, c_int, c_int, c_uint64, c_int, POINTER(HeliPolicy), c_uint64,
                                        c_int, c_int, P, P, P, P, P, P, P, P, P, P, P, P, P, P, c_int, c_int, P, P, P, P,
                                        P, c_int, P], c_int),
+    "gca_gae": ([P, P, P, P, c_float, c_float, c_int, c_int, P, P, P], c_int),
+    "gca_helicopter_policy_grad_workspace": ([POINTER(HeliPolicy), c_int, c_int], c_int64),
+    "gca_helicopter_policy_grad": ([POINTER(HeliPolicy), c_int, P, P, P, P, P, P, c_int64, P, c_int, c_float, c_float,
+                                    c_float, c_int, P, P, P, P, P, P, P, c_int64, P], c_int),
     "gca_bench_copy": ([P, P, c_int64, c_int, P], c_int),
     "gca_bench_march_pattern": ([c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P], c_int),
 }
@@ -266,7 +270,8 @@ EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 CPU_SYMBOLS = ("gca_last_error", "gca_version", "gca_philox", "gca_count_cells", "gca_move_modify",
                "gca_ds_count_draws", "gca_ds_step", "gca_helicopter_step", "gca_helicopter_rollout",
                "gca_bulldozer_reset_where", "gca_policy_observation", "gca_helicopter_policy_act",
-               "gca_helicopter_policy_rollout")
+               "gca_helicopter_policy_rollout", "gca_gae", "gca_helicopter_policy_grad_workspace",
+               "gca_helicopter_policy_grad")
 
 _lib = None
 _lib_cpu = None

@@ -669,6 +669,54 @@ int gca_helicopter_policy_rollout(int empty, int tree, int fire, int max_freeze,
                                   uint8_t* buf0, uint8_t* buf1, int H, int W, int32_t* pos, int32_t* counts,
                                   uint8_t* hit, double* reward, int64_t* steps_elapsed, int E, void* stream);
 
+/* ------------------------------------------ PPO update (the learner's half of the reference's main loop:
+ * agents/jax_ppo.py:932-984 compute_gae, :987-1043 ppo_loss and its gradient), on rollout_policy's records
+ * gca_gae: reward f64 (K, E) and value f32 (K, E) as gca_helicopter_policy_rollout records them, next_value f32 (E) the
+ * value of the state after the rollout (gca_helicopter_policy_act gives it without side effects), terminal u8 (K, E),
+ * nullable: terminal[k][e] != 0 means step k ended env e's episode, nothing is bootstrapped across k -> k + 1 (the
+ * reference's dones[1:] with next_done as the last row; NULL = never, the helicopter env never ends). For k = K-1 .. 0,
+ * A = 0.0f before the first iteration, every operation an individually rounded f32 one (no fma) in this order:
+ *   r = (float)reward; nn = terminal ? 0.0f : 1.0f; nv = k == K-1 ? next_value[e] : value[k+1][e];
+ *   delta = (r + (gamma * nv) * nn) - value[k][e];  A = delta + (gamma_lambda * nn) * A;
+ *   advantage[k][e] = A;  returns[k][e] = A + value[k][e].
+ * gamma_lambda is the caller's float(gamma * gae_lambda) computed in double (jax's weak-typed Python scalars). One launch,
+ * a thread per env, no allocation, no sync: capturable. K == 0 is a no-op; argument errors come before any launch. The
+ * device, the host build and tests/_ppo_ref.py agree bit for bit. */
+int gca_gae(const double* reward, const float* value, const float* next_value, const uint8_t* terminal, float gamma,
+            float gamma_lambda, int K, int E, float* advantage, float* returns, void* stream);
+
+/* gca_helicopter_policy_grad: the PPO clipped-surrogate loss (jax_ppo.py:987-1041 with clip_vloss off), its statistics
+ * and d loss / d each of the five policy tensors over a minibatch of recorded samples. The T = K E rows are
+ * rollout_policy's records flattened: local u8 [T][S][S], coarse f32 [T][C], action i32 [T], old_logits f32 [T][9];
+ * advantage / returns f32 [T] are gca_gae's. The minibatch is rows idx[0..N) (NULL: rows 0..N-1, N <= T; repeats
+ * allowed; nothing is gathered into a copy). Per sample, with (l, v) the policy's logits and value on that row (class
+ * & 3, relu'(0) = 0): logp_new = l[a] - logsumexp(l); logp_old the same function of old_logits; ratio = exp(logp_new -
+ * logp_old); A^ the advantage, with norm_adv != 0 (A - mean) / (std + 1e-8) over the minibatch (population std;
+ * constants, not differentiated); pg = max(-A^ ratio, -A^ clip(ratio, 1 - c, 1 + c)); vl = 0.5 (v - R)^2; ent = -sum p_i
+ * log p_i. loss = mean(pg) - ent_coef mean(ent) + vf_coef mean(vl).
+ * stats[8] = {loss, mean pg, mean vl, mean ent, approx_kl = mean((ratio - 1) - logratio), clip fraction = the share of
+ * samples with ratio outside [1 - c, 1 + c], adv mean, adv std}.
+ * The reference's clipped value loss (clip_vloss, :1022-1029) takes the batch mean BEFORE its maximum, a quirk; it is out
+ * of scope here.
+ * Outputs: g_* f32 in the weights' own layouts, every element written (a (cell, class) row no sample selects is exactly
+ * 0.0f), never read, and they may alias neither each other nor the weights. All accumulation is f32 (the scalar loss
+ * chain of ONE sample -- the two logsumexps, the ratio, the entropy -- runs in double and is rounded once), no floating-point
+ * atomics: partial sums go to `workspace` (gca_helicopter_policy_grad_workspace bytes; a smaller one is an argument
+ * error; the workspace, w_local, w_coarse and b1 must be 16-B aligned, which both builds check; the outputs need no
+ * alignment) and are added in a fixed order, so equal arguments give equal bits; the result may depend on N and on
+ * the launch shape derived from (S, C, Hd, N), on nothing else. The forward inside does NOT follow the act kernels'
+ * summation order: logits recomputed with unchanged weights agree with the recorded ones within rounding, not bit for
+ * bit. An action outside [0, 8] is clamped. The host build checks idx against [0, T) (an argument error); the device
+ * cannot without a sync and clamps each index into [0, T). Launches only: capturable, no allocation, no sync. The host
+ * build runs plain loops with the network and the gradient sums in double, rounded once. */
+int64_t gca_helicopter_policy_grad_workspace(const gca_heli_policy* p, int C, int N);
+int gca_helicopter_policy_grad(const gca_heli_policy* p, int C, const uint8_t* local, const float* coarse,
+                               const int32_t* action, const float* old_logits, const float* advantage,
+                               const float* returns, int64_t T, const int32_t* idx, int N, float clip_coef,
+                               float ent_coef, float vf_coef, int norm_adv, float* g_w_local, float* g_w_coarse,
+                               float* g_b1, float* g_w_out, float* g_b2, float* stats, void* workspace,
+                               int64_t workspace_bytes, void* stream);
+
 /* ------------------------------------------ measurement yardsticks (bench.py; no reference counterpart)
  * gca_bench_copy: a 16-B device copy of nbytes (one element per thread, one pass) (a multiple of 16, 16-B aligned), nt != 0 non-temporal
  * loads and stores: the practical HBM ceiling the bench reports beside the 8 TB/s spec.
