@@ -20,6 +20,7 @@
 //                     (gca_heli.hip, gca_heli_policy_dev.h), in gca.h's summation order
 //   gca_gae / gca_helicopter_policy_grad(_workspace)  the PPO update (gca_ppo.hip): the GAE recurrence bit for bit, the
 //                     loss gradient in double as a second yardstick
+//   gca_adam_step(_workspace) / gca_permutation  the optimizer and the minibatch shuffle (gca_opt.hip), bit for bit
 //   gca_philox        Random123 Philox4x32-10 (KAT hook)
 #include <math.h>
 #include <stdarg.h>
@@ -30,6 +31,7 @@
 #include <vector>
 
 #include "../../include/gca.h"
+#include "gca_opt_plan.h"
 #include "gca_ppo_plan.h"
 
 namespace {
@@ -802,5 +804,114 @@ extern "C" int gca_helicopter_policy_grad(const gca_heli_policy* p, int C, const
     stats[5] = (float)(st[4] * inv_n);
     stats[6] = (float)mean;
     stats[7] = (float)sd;
+    return GCA_OK;
+}
+
+// ---------------------------------------------------------------- the optimizer (gca.h "optimizer")
+// gca_adam_step in gca.h's order: the lanes, the chunks and the trees of the device's sum as plain loops, then one
+// rounded f32 operation at a time per element (the file is built with -ffp-contract=off).
+static double adam_tree_host(double* s) {
+    for (int h = ADAM_THREADS / 2; h >= 1; h >>= 1)
+        for (int l = 0; l < h; ++l) s[l] = s[l] + s[l + h];
+    return s[0];
+}
+
+extern "C" int64_t gca_adam_step_workspace(int64_t total_elements) {
+    if (total_elements < 1) {
+        set_error("argument: %s", "adam_step_workspace: total_elements >= 1");
+        return -1;
+    }
+    return adam_workspace_bytes(total_elements);
+}
+
+extern "C" int gca_adam_step(const gca_adam_tensors* t, void* state, float lr0, float b1, float b2, float eps,
+                             float max_norm, int64_t steps_per_iteration, int64_t num_iterations, float* info_out,
+                             void* workspace, int64_t workspace_bytes, void*) {
+    CPU_CHECK_ARG(t && state && workspace, "adam: null tensor table, state or workspace");
+    CPU_CHECK_ARG(t->n >= 1 && t->n <= GCA_ADAM_MAX_TENSORS, "adam: 1 to 8 tensors");
+    int64_t total = 0;
+    uintptr_t low = (uintptr_t)state | (uintptr_t)info_out;
+    for (int i = 0; i < t->n; ++i) {
+        CPU_CHECK_ARG(t->w[i] && t->g[i] && t->m[i] && t->v[i], "adam: null tensor pointer");
+        CPU_CHECK_ARG(t->len[i] >= 1 && t->len[i] < (1ll << 31), "adam: tensor lengths in [1, 2^31)");
+        total += t->len[i];
+        low |= (uintptr_t)t->w[i] | (uintptr_t)t->g[i] | (uintptr_t)t->m[i] | (uintptr_t)t->v[i];
+    }
+    CPU_CHECK_ARG((low & 3u) == 0, "adam: tensors, state and info_out 4-B aligned");
+    CPU_CHECK_ARG(((uintptr_t)workspace & 7u) == 0, "adam: workspace 8-B aligned");
+    CPU_CHECK_ARG(b1 >= 0.0f && b1 < 1.0f && b2 >= 0.0f && b2 < 1.0f, "adam: b1 and b2 in [0, 1)");
+    CPU_CHECK_ARG(eps >= 0.0f, "adam: eps >= 0");
+    CPU_CHECK_ARG((steps_per_iteration == 0 && num_iterations == 0) || (steps_per_iteration >= 1 && num_iterations >= 1),
+                  "adam: steps_per_iteration and num_iterations both 0 (no annealing) or both >= 1");
+    CPU_CHECK_ARG(workspace_bytes >= adam_workspace_bytes(total), "adam: workspace smaller than gca_adam_step_workspace");
+    const int64_t CH = adam_chunk(total);
+    std::vector<double> part;
+    double s[ADAM_THREADS];
+    for (int i = 0; i < t->n; ++i) {
+        for (int64_t base = 0; base < t->len[i]; base += CH) {
+            const int64_t cnt = t->len[i] - base < CH ? t->len[i] - base : CH;
+            for (int l = 0; l < ADAM_THREADS; ++l) s[l] = 0.0;
+            const float* g = t->g[i] + base;
+            for (int64_t e = 0; e < cnt; ++e) {  // increasing e is increasing (k, j) for every lane
+                double& a = s[(e / 4) % ADAM_THREADS];
+                a = a + (double)g[e] * (double)g[e];
+            }
+            part.push_back(adam_tree_host(s));
+        }
+    }
+    for (int l = 0; l < ADAM_THREADS; ++l) s[l] = 0.0;
+    for (size_t p = 0; p < part.size(); ++p) s[p % ADAM_THREADS] = s[p % ADAM_THREADS] + part[p];
+    const float norm = sqrtf((float)adam_tree_host(s));
+    int32_t* sw = reinterpret_cast<int32_t*>(state);
+    float* sf = reinterpret_cast<float*>(state);
+    const int32_t count = sw[ADAM_COUNT];
+    const float b1p = sf[ADAM_B1POW] * b1, b2p = sf[ADAM_B2POW] * b2;
+    const float lr = adam_lr(lr0, count, steps_per_iteration, num_iterations);
+    const float omb1 = 1.0f - b1, omb2 = 1.0f - b2, c1 = 1.0f - b1p, c2 = 1.0f - b2p;
+    const bool clip = max_norm > 0.0f && !(norm < max_norm);
+    for (int i = 0; i < t->n; ++i) {
+        float *w = t->w[i], *m = t->m[i], *v = t->v[i];
+        const float* g = t->g[i];
+        for (int64_t e = 0; e < t->len[i]; ++e) {
+            const float gc = clip ? (g[e] / norm) * max_norm : g[e];
+            m[e] = (b1 * m[e]) + (omb1 * gc);
+            v[e] = (b2 * v[e]) + ((omb2 * gc) * gc);
+            const float mhat = m[e] / c1, vhat = v[e] / c2;
+            w[e] = w[e] - (lr * (mhat / (sqrtf(vhat) + eps)));
+        }
+    }
+    sw[ADAM_COUNT] = sw[ADAM_PENDING + ADAM_COUNT] = count + 1;
+    sf[ADAM_B1POW] = sf[ADAM_PENDING + ADAM_B1POW] = b1p;
+    sf[ADAM_B2POW] = sf[ADAM_PENDING + ADAM_B2POW] = b2p;
+    sf[ADAM_NORM] = norm;
+    sf[ADAM_LR] = sf[ADAM_PENDING + ADAM_LR] = lr;
+    if (info_out) {
+        info_out[0] = norm;
+        info_out[1] = lr;
+    }
+    return GCA_OK;
+}
+
+extern "C" int gca_permutation(uint64_t seed, uint32_t epoch0, const int32_t* counter, int64_t T, int rows,
+                               int32_t* out, void*) {
+    CPU_CHECK_ARG(out, "permutation: null out");
+    CPU_CHECK_ARG(T >= 1 && T < (1ll << 31), "permutation: 1 <= T < 2^31");
+    CPU_CHECK_ARG(rows >= 1 && rows <= 65535, "permutation: 1 <= rows <= 65535");
+    CPU_CHECK_ARG((((uintptr_t)out | (uintptr_t)counter) & 3u) == 0, "permutation: out and counter 4-B aligned");
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    const auto f = [k0, k1](uint32_t right, uint32_t round, uint32_t row_key) {
+        return philox4x32_10(u32x4{right, round, row_key, GCA_TAG_PERM}, k0, k1).x;
+    };
+    const int h = perm_half_bits(T);
+    bool capped = false;
+    for (int r = 0; r < rows; ++r) {
+        const uint32_t row_key = epoch0 + (uint32_t)r + (counter ? (uint32_t)counter[0] : 0u);
+        for (int64_t i = 0; i < T; ++i)
+            out[(size_t)r * T + i] = (int32_t)perm_walk((uint32_t)i, (uint32_t)T, h, row_key, f, &capped);
+    }
+    if (capped) {
+        set_error("internal: %s", "permutation: the walk reached its cap");
+        return GCA_ERR_UNSUPPORTED;
+    }
     return GCA_OK;
 }

@@ -187,6 +187,25 @@ class HeliPolicy(ctypes.Structure):
     ]
 
 
+GCA_ADAM_MAX_TENSORS = 8
+GCA_ADAM_STATE_WORDS = 16
+TAG_PERM = 0x5045524D
+
+
+class AdamTensors(ctypes.Structure):
+    """gca_adam_tensors (include/gca.h): the lengths and the w / g / m / v addresses of the optimizer's tensors."""
+
+    _fields_ = [
+        ("n", c_int32),
+        ("reserved", c_int32),
+        ("len", c_int64 * GCA_ADAM_MAX_TENSORS),
+        ("w", c_void_p * GCA_ADAM_MAX_TENSORS),
+        ("g", c_void_p * GCA_ADAM_MAX_TENSORS),
+        ("m", c_void_p * GCA_ADAM_MAX_TENSORS),
+        ("v", c_void_p * GCA_ADAM_MAX_TENSORS),
+    ]
+
+
 P = c_void_p  # device pointers travel as plain addresses
 _SIGNATURES = {
     "gca_last_error": ([], ctypes.c_char_p),
@@ -261,6 +280,10 @@ _SIGNATURES = {
     "gca_helicopter_policy_grad_workspace": ([POINTER(HeliPolicy), c_int, c_int], c_int64),
     "gca_helicopter_policy_grad": ([POINTER(HeliPolicy), c_int, P, P, P, P, P, P, c_int64, P, c_int, c_float, c_float,
                                     c_float, c_int, P, P, P, P, P, P, P, c_int64, P], c_int),
+    "gca_adam_step_workspace": ([c_int64], c_int64),
+    "gca_adam_step": ([POINTER(AdamTensors), P, c_float, c_float, c_float, c_float, c_float, c_int64, c_int64, P, P,
+                       c_int64, P], c_int),
+    "gca_permutation": ([c_uint64, c_uint32, P, c_int64, c_int, P, P], c_int),
     "gca_bench_copy": ([P, P, c_int64, c_int, P], c_int),
     "gca_bench_march_pattern": ([c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P], c_int),
 }
@@ -271,7 +294,7 @@ CPU_SYMBOLS = ("gca_last_error", "gca_version", "gca_philox", "gca_count_cells",
                "gca_ds_count_draws", "gca_ds_step", "gca_helicopter_step", "gca_helicopter_rollout",
                "gca_bulldozer_reset_where", "gca_policy_observation", "gca_helicopter_policy_act",
                "gca_helicopter_policy_rollout", "gca_gae", "gca_helicopter_policy_grad_workspace",
-               "gca_helicopter_policy_grad")
+               "gca_helicopter_policy_grad", "gca_adam_step_workspace", "gca_adam_step", "gca_permutation")
 
 _lib = None
 _lib_cpu = None

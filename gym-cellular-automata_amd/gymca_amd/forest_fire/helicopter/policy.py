@@ -6,7 +6,8 @@ relu hidden layer of width `hidden`, then ten outputs: nine action logits and th
 on an observation; env.rollout_policy(policy, K) collects K closed-loop steps of every env in one launch, bit for bit
 K x (observe, act, step). forward_torch is the same network in differentiable torch ops. ppo_grad is the learner's step
 on rollout_policy's records: the PPO clipped-surrogate loss, its statistics and its gradient with respect to the five
-tensors in four launches (gca_helicopter_policy_grad), with forest_fire.ppo.gae for the advantages.
+tensors in four launches (gca_helicopter_policy_grad), with forest_fire.ppo.gae for the advantages. ppo_update is the
+whole update: forest_fire.ppo.permutation's shuffles, then ppo_grad and forest_fire.ppo.Adam.step per minibatch.
 """
 import ctypes
 import math
@@ -229,3 +230,57 @@ class HelicopterPolicy:
             object.__setattr__(self, "_ppo_call", pc)
         pc[1](*args, dev.raw_stream(di))
         return grads, stats
+
+    def ppo_update(self, opt, records, advantage, returns, epochs=4, minibatches=4, seed=0, clip_coef=0.2,
+                   ent_coef=0.01, vf_coef=0.5, norm_adv=True, stats_out=None, info_out=None, perm_out=None,
+                   grads_out=None, workspace=None):
+        """A whole PPO update on the device (the reference's update_ppo, agents/jax_ppo.py:1045-1114): ONE
+        forest_fire.ppo.permutation launch draws the `epochs` shuffles of the T recorded samples (keyed by seed, the
+        epoch and opt.count, the optimizer's device-resident step count), then every epoch walks its row in
+        `minibatches` slices of T / minibatches rows: ppo_grad on the slice, opt.step on the gradients. opt: a
+        forest_fire.ppo.Adam over exactly this policy's five tensors. Returns (stats (epochs * minibatches, 8), info
+        (epochs * minibatches, 2)): row i holds the i-th minibatch's ppo_grad statistics and Adam.step's (pre-clip
+        gradient norm, learning rate). stats_out / info_out / perm_out (int32 (epochs, T)) / grads_out / workspace: the
+        caller's buffers, else allocated (the workspace: the policy's own). With all of them given the call allocates
+        nothing and does not sync: it can be captured as one graph, and a replay draws new shuffles because opt.count has
+        moved."""
+        import torch
+
+        from .. import ppo
+        from .._batched import check_tensor
+
+        di = -1 if self.device.type == "cpu" else self.device.index
+        epochs, minibatches = int(epochs), int(minibatches)
+        if epochs < 1 or minibatches < 1:
+            raise ValueError("ppo_update: epochs and minibatches must be positive")
+        if not isinstance(opt, ppo.Adam) or set(opt.names) != set(WEIGHTS):
+            raise ValueError(f"ppo_update: opt must be a forest_fire.ppo.Adam over the policy's tensors {list(WEIGHTS)}")
+        for n in WEIGHTS:
+            if opt.params[n] is not getattr(self, n):
+                raise ValueError(f"ppo_update: opt.params['{n}'] is not policy.{n} (a tensor was reassigned after the "
+                                 "optimizer was built)")
+        action = records.get("action") if isinstance(records, dict) else None
+        if type(action) is not torch.Tensor or action.numel() < 1:
+            raise ValueError("ppo_update: records['action'] must be a tensor")
+        T = action.numel()
+        if T % minibatches:
+            raise ValueError(f"ppo_update: T = {T} samples do not divide into {minibatches} minibatches")
+        N, steps = T // minibatches, epochs * minibatches
+        new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=self.device)
+        stats = (new((steps, 8), torch.float32) if stats_out is None
+                 else check_tensor(stats_out, torch.float32, (steps, 8), di, "ppo_update", "stats_out"))
+        info = (new((steps, 2), torch.float32) if info_out is None
+                else check_tensor(info_out, torch.float32, (steps, 2), di, "ppo_update", "info_out"))
+        perm = (new((epochs, T), torch.int32) if perm_out is None
+                else check_tensor(perm_out, torch.int32, (epochs, T), di, "ppo_update", "perm_out"))
+        grads = ({n: new(s, torch.float32) for n, s in self.weight_shapes().items()} if grads_out is None
+                 else grads_out)
+        ppo.permutation(T, epochs, seed, counter=opt.count, out=perm)
+        for e in range(epochs):
+            for mb in range(minibatches):
+                i = e * minibatches + mb
+                self.ppo_grad(records, advantage, returns, perm[e, mb * N:(mb + 1) * N], clip_coef=clip_coef,
+                              ent_coef=ent_coef, vf_coef=vf_coef, norm_adv=norm_adv, grads_out=grads,
+                              stats_out=stats[i], workspace=workspace)
+                opt.step(grads, info_out=info[i])
+        return stats, info

@@ -1,6 +1,9 @@
 """The learner's side of a PPO loop on the batched envs' records (include/gca.h "PPO update"): gae(), the reference's
-generalised advantage estimate (agents/jax_ppo.py:932-984) in one launch, and the names of the eight statistics that
-HelicopterPolicy.ppo_grad returns beside the gradients."""
+generalised advantage estimate (agents/jax_ppo.py:932-984) in one launch, the names of the eight statistics that
+HelicopterPolicy.ppo_grad returns beside the gradients, Adam (the reference's clipped, annealed optimizer in two
+launches per step, its step count on the device) and permutation (the minibatch shuffle in one launch)."""
+import ctypes
+
 import numpy as np
 
 from .. import _device as dev
@@ -70,3 +73,139 @@ def gae(reward, value, next_value, gamma=0.99, gae_lambda=0.95, terminal=None, a
     else:
         call("gca_gae", *args, dev.raw_stream(di))
     return outs[0], outs[1]
+
+
+def _dev_index(device):
+    return -1 if device.type == "cpu" else device.index
+
+
+class Adam:
+    """optax.chain(clip_by_global_norm(max_grad_norm), adam(lr, b1, b2, eps)) with the reference's linear learning-rate
+    schedule (agents/jax_ppo.py:677-702, :775-783; the defaults are agents/args.py's), as gca_adam_step: two launches of
+    hand-written kernels per step for all tensors together, the step count and the running b1 ** count / b2 ** count in
+    a device-resident state block that the host never reads, so a step can be captured in a graph and replayed.
+
+    params: a dict of 1 to 8 contiguous float32 tensors on one device (a cpu device runs the host build, bit for bit the
+    same numbers); they are updated in place, so calls that bound their addresses stay valid. max_grad_norm <= 0: no
+    clipping (the norm is still computed). anneal: None, or (steps_per_iteration, num_iterations): lr * max(1 - (count
+    // steps_per_iteration) / num_iterations, 0) with the count before the step. The arithmetic and its order are
+    include/gca.h's. The optimizer owns m, v, the state block and the workspace."""
+
+    def __init__(self, params, lr=2.5e-4, b1=0.9, b2=0.999, eps=1e-5, max_grad_norm=0.5, anneal=None):
+        import torch
+
+        from .. import _lib
+
+        if not isinstance(params, dict) or not 1 <= len(params) <= _lib.GCA_ADAM_MAX_TENSORS:
+            raise ValueError(f"Adam: params must be a dict of 1 to {_lib.GCA_ADAM_MAX_TENSORS} tensors")
+        first = next(iter(params.values()))
+        if type(first) is not torch.Tensor:
+            raise ValueError("Adam: params must hold torch tensors")
+        self.device = first.device
+        di = _dev_index(self.device)
+        for n, t in params.items():
+            if not (type(t) is torch.Tensor and t.dtype is torch.float32 and t.get_device() == di and t.is_contiguous()
+                    and t.numel() >= 1):
+                raise ValueError(f"Adam: params['{n}'] must be a non-empty contiguous float32 tensor on {self.device}")
+        if anneal is None:
+            spi, ni = 0, 0
+        else:
+            spi, ni = (int(x) for x in anneal)
+            if spi < 1 or ni < 1:
+                raise ValueError("Adam: anneal = (steps_per_iteration, num_iterations), both >= 1")
+        self.params = dict(params)
+        self.names = tuple(self.params)
+        self.hyper = (float(lr), float(b1), float(b2), float(eps), float(max_grad_norm), spi, ni)
+        self.m = {n: torch.zeros_like(t) for n, t in self.params.items()}
+        self.v = {n: torch.zeros_like(t) for n, t in self.params.items()}
+        self.state = torch.zeros(_lib.GCA_ADAM_STATE_WORDS, dtype=torch.int32, device=self.device)
+        self.state[1:3] = 0x3F800000  # b1_pow = b2_pow = 1.0f before step 1
+        self.count = self.state[0:1]  # the device-resident step count (ppo.permutation's `counter`)
+        total = sum(t.numel() for t in self.params.values())
+        lib = _lib.load_cpu() if di < 0 else _lib.load()
+        need = lib.gca_adam_step_workspace(total)
+        if need < 0:
+            raise _lib.GCAError("gca_adam_step_workspace: " + lib.gca_last_error().decode(errors="replace"))
+        self.workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+        s = self._struct = _lib.AdamTensors()
+        s.n = len(self.names)
+        for i, n in enumerate(self.names):
+            s.len[i] = self.params[n].numel()
+            s.w[i], s.m[i], s.v[i] = self.params[n].data_ptr(), self.m[n].data_ptr(), self.v[n].data_ptr()
+        self._grads, self._grad_tensors = None, ()
+        fixed = (self._struct, self.state.data_ptr()) + self.hyper
+        tail = (self.workspace.data_ptr(), self.workspace.numel())
+        if di < 0:
+            self._call = lambda info, stream: _lib.call_cpu("gca_adam_step", ctypes.byref(self._struct), *fixed[1:],
+                                                            info, *tail, None)
+        else:
+            self._call = _lib.BoundCall("gca_adam_step", *fixed, _lib.SLOT, *tail, _lib.SLOT,
+                                        keep=tuple(self.params.values()))
+
+    def step(self, grads, info_out=None):
+        """One step on `grads`, a dict with the names of `params` (contiguous float32 tensors of the parameters'
+        shapes on their device; read only). Returns a float32 (2,) tensor: the gradients' global norm before clipping
+        and the learning rate used (info_out if given, else a new tensor). No sync; with info_out no allocation."""
+        import torch
+
+        di = _dev_index(self.device)
+        s = self._struct
+        if grads is not self._grads or any(grads[n] is not g for n, g in zip(self.names, self._grad_tensors)):
+            if not isinstance(grads, dict) or any(n not in grads for n in self.names):
+                raise ValueError(f"Adam.step: grads must be a dict with the names {list(self.names)}")
+            for i, n in enumerate(self.names):
+                check_tensor(grads[n], torch.float32, self.params[n].shape, di, "Adam.step", f"grads['{n}']")
+                s.g[i] = grads[n].data_ptr()
+            self._grads, self._grad_tensors = grads, tuple(grads[n] for n in self.names)
+        info = (torch.empty(2, dtype=torch.float32, device=self.device) if info_out is None
+                else check_tensor(info_out, torch.float32, (2,), di, "Adam.step", "info_out"))
+        self._call(info.data_ptr(), None if di < 0 else dev.raw_stream(di))
+        return info
+
+    def state_dict(self):
+        """Copies of m, v and the state block (the count, b1 ** count, b2 ** count, the last norm and learning rate)."""
+        return {"m": {n: t.clone() for n, t in self.m.items()}, "v": {n: t.clone() for n, t in self.v.items()},
+                "state": self.state.clone()}
+
+    def load_state_dict(self, sd):
+        """Take a state_dict()'s values, in place (every bound address stays valid): training resumes with equal bits."""
+        for k in ("m", "v"):
+            for n in self.names:
+                getattr(self, k)[n].copy_(sd[k][n])
+        self.state.copy_(sd["state"])
+        return self
+
+
+def permutation(T, rows, seed, epoch0=0, counter=None, out=None, device=None):
+    """int32 (rows, T): every row a permutation of [0, T), in ONE launch of gca_permutation (a keyed Feistel network
+    walked cyclically, include/gca.h; every element computed on its own). Row r is keyed by (seed, epoch0 + r +
+    counter[0]); counter: an int32 device tensor read at run time (Adam.count: a replayed graph then draws fresh rows),
+    or None. out: a contiguous int32 (rows, T) tensor, else allocated on `device` (default: the counter's, else the
+    current HIP device; "cpu" runs the host build, bit for bit the same rows). No sync; with `out` no allocation."""
+    import torch
+
+    T, rows = int(T), int(rows)
+    if out is not None:
+        device = out.device
+    elif counter is not None:
+        device = counter.device
+    elif device is None or str(device) != "cpu":
+        device = dev.require_device(device)
+    device = torch.device(device)
+    di = _dev_index(device)
+    if out is None:
+        if T < 1 or rows < 1:
+            raise ValueError("permutation: T and rows must be positive")
+        out = torch.empty((rows, T), dtype=torch.int32, device=device)
+    else:
+        check_tensor(out, torch.int32, (rows, T), di, "permutation", "out")
+    if counter is not None and not (type(counter) is torch.Tensor and counter.dtype is torch.int32
+                                    and counter.get_device() == di and counter.numel() >= 1):
+        raise ValueError("permutation: counter must be an int32 tensor on the same device as out")
+    args = (int(seed) & (2 ** 64 - 1), int(epoch0) & 0xFFFFFFFF, None if counter is None else counter.data_ptr(), T, rows,
+            out.data_ptr())
+    if di < 0:
+        call_cpu("gca_permutation", *args, None)
+    else:
+        call("gca_permutation", *args, dev.raw_stream(di))
+    return out

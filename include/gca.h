@@ -717,6 +717,70 @@ int gca_helicopter_policy_grad(const gca_heli_policy* p, int C, const uint8_t* l
                                float* g_b1, float* g_w_out, float* g_b2, float* stats, void* workspace,
                                int64_t workspace_bytes, void* stream);
 
+/* ------------------------------------------ optimizer (the rest of the reference's update_ppo, agents/jax_ppo.py:1045-1114:
+ * optax.chain(clip_by_global_norm(max_norm), adam(lr, b1, b2, eps)) with linear_schedule, :677-702 and :775-783)
+ * gca_adam_step: one optimizer step over n <= GCA_ADAM_MAX_TENSORS parameter tensors in TWO launches, no floating-point
+ * atomics, no allocation, no sync: capturable, and equal inputs give equal bits. Tensor t has len[t] >= 1 elements in
+ * four f32 arrays: the parameters w (updated in place), the gradient g (read only), the moments m and v (updated in
+ * place). Contiguous, 4-byte alignment suffices: a tensor whose four pointers are 16-B aligned takes 16-B accesses,
+ * any other a scalar path with the same results. The table is a host struct read at call time.
+ * state: GCA_ADAM_STATE_WORDS 4-byte words of device memory that the host never reads: [0] count i32, [1] b1_pow f32,
+ * [2] b2_pow f32, [3] the last step's pre-clip gradient norm f32, [4] the last learning rate f32, [5..7] unused,
+ * [8..15] the slot the next scalars wait in between the two launches. Before step 1: count = 0, b1_pow = b2_pow = 1.0f
+ * (the caller writes them once), everything else 0. A replayed capture advances the count like any other step.
+ * Arithmetic: every operation an individually rounded IEEE f32 one (correctly rounded divide and square root, no fma),
+ * in exactly this order, but for the sum under the norm and the learning rate, which run in double:
+ *   count' = count + 1; b1_pow' = b1_pow * b1; b2_pow' = b2_pow * b2
+ *   lr     = lr0 without annealing (steps_per_iteration == 0 and num_iterations == 0); with it (both >= 1), in double
+ *            and rounded to f32 once: frac = 1 - ((count / steps_per_iteration) / num_iterations), the first division
+ *            an integer one on the count BEFORE this step, the second a real one; lr = lr0 * max(frac, 0). That is the
+ *            reference's linear_schedule; the reference never leaves frac >= 0, the clamp at zero is ours.
+ *   norm   CH = 1024 * max(1, ceil(total / 2097152)), total = the sum of the lengths. Tensor t is cut into chunks of CH
+ *            elements (the last one shorter), and the chunks are numbered through the tensors in argument order. In a
+ *            chunk, lane l of 256 adds the squares (each exact in double) of its elements to a double that starts at
+ *            0.0, in increasing k and, inside a k, increasing j: elements 4 (l + 256 k) + j, j = 0..3, of the chunk.
+ *            The 256 lane sums meet in the tree s[l] = s[l] + s[l + h] for l < h, h = 128, 64, .., 1; s[0] is the
+ *            chunk's partial. The partials are summed the same way: lane l adds partials l, l + 256, .. in increasing
+ *            order from 0.0, then the same tree. norm = sqrtf((float)sum).
+ *   clip   clip_by_global_norm's operations: g' = norm < max_norm ? g : (g / norm) * max_norm; max_norm <= 0: g' = g
+ *            (the norm is still computed and recorded).
+ *   m      m' = (b1 * m) + ((1.0f - b1) * g')
+ *   v      v' = (b2 * v) + (((1.0f - b2) * g') * g')
+ *   w      mhat = m' / (1.0f - b1_pow'); vhat = v' / (1.0f - b2_pow'); w' = w - (lr * (mhat / (sqrtf(vhat) + eps)))
+ * info_out (nullable, device f32 [2]) receives {norm, lr}. workspace: gca_adam_step_workspace(total) bytes, 8-B
+ * aligned; a shorter one is an argument error. Argument errors come before any launch, the same in both builds. The
+ * device, the host build and tests/_adam_ref.py follow the order above, so they agree bit for bit. */
+#define GCA_ADAM_MAX_TENSORS 8
+#define GCA_ADAM_STATE_WORDS 16
+typedef struct {
+    int32_t n;                 /* tensors in use, 1 .. GCA_ADAM_MAX_TENSORS */
+    int32_t reserved;          /* 0 */
+    int64_t len[GCA_ADAM_MAX_TENSORS];
+    float* w[GCA_ADAM_MAX_TENSORS];
+    const float* g[GCA_ADAM_MAX_TENSORS];
+    float* m[GCA_ADAM_MAX_TENSORS];
+    float* v[GCA_ADAM_MAX_TENSORS];
+} gca_adam_tensors;
+int64_t gca_adam_step_workspace(int64_t total_elements);
+int gca_adam_step(const gca_adam_tensors* t, void* state, float lr0, float b1, float b2, float eps, float max_norm,
+                  int64_t steps_per_iteration, int64_t num_iterations, float* info_out, void* workspace,
+                  int64_t workspace_bytes, void* stream);
+
+/* gca_permutation: rows permutations of [0, T) in one launch (the minibatch shuffle of update_ppo, jax_ppo.py:1062-1067;
+ * our own Philox stream, not jax's). out i32 [rows][T]; every out[r][i] is computed on its own: no sort, no atomic, no
+ * second pass. Row r is keyed by k_r = epoch0 + r + (counter ? *counter : 0) (mod 2^32; counter a device i32, read
+ * only: a replayed capture draws fresh rows when the counter moves, e.g. the optimizer's count). h = the smallest
+ * integer >= 1 with 2^(2h) >= T. The balanced Feistel network on x = (L, R), L = x >> h, R = x & (2^h - 1), runs four
+ * rounds (L, R) <- (R, L ^ (F & (2^h - 1))), round = 0..3, F = word 0 of Philox4x32-10 over the counter (R, round, k_r,
+ * GCA_TAG_PERM) with the key (seed lo, seed hi); x' = (L << h) | R. Starting from x = i the network is applied until
+ * x < T: a bijection of [0, 2^(2h)) walked cyclically is a permutation of [0, T). The walk is capped at 1024
+ * applications (probability below (3/4)^1024); a thread that reaches the cap writes i, the host build reports
+ * GCA_ERR_UNSUPPORTED ("internal: ..."). 1 <= T < 2^31, 1 <= rows <= 65535. The device, the host build and
+ * tests/_adam_ref.py agree bit for bit. */
+#define GCA_TAG_PERM 0x5045524Du /* 'PERM' : the minibatch permutation's round function */
+int gca_permutation(uint64_t seed, uint32_t epoch0, const int32_t* counter, int64_t T, int rows, int32_t* out,
+                    void* stream);
+
 /* ------------------------------------------ measurement yardsticks (bench.py; no reference counterpart)
  * gca_bench_copy: a 16-B device copy of nbytes (one element per thread, one pass) (a multiple of 16, 16-B aligned), nt != 0 non-temporal
  * loads and stores: the practical HBM ceiling the bench reports beside the 8 TB/s spec.

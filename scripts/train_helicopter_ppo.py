@@ -1,11 +1,14 @@
 #!/usr/bin/env python
 """PPO on the batched helicopter env, the whole loop on the public surface and on the device: env.rollout_policy collects
-K steps of every env in one launch, env.act gives the bootstrap value, forest_fire.ppo.gae the advantages, and each
-minibatch of a device randperm goes through HelicopterPolicy.ppo_grad (loss, statistics and the five gradients in four
-launches); Adam is a dozen lines of torch on the policy's five tensors, updated in place, so no call is bound again.
-The only sync of an update is its print. An example, not a test.
+K steps of every env in one launch, env.act gives the bootstrap value, forest_fire.ppo.gae the advantages, and
+HelicopterPolicy.ppo_update runs the update: one forest_fire.ppo.permutation launch shuffles the samples for all epochs,
+then every minibatch goes through ppo_grad (loss, statistics and the five gradients in four launches) and
+forest_fire.ppo.Adam.step (global-norm clip and Adam in two launches, the step count on the device). The optimizer is
+the reference's: clip_by_global_norm(--max-grad-norm), adam(eps=1e-5), and with --anneal its linear learning-rate
+schedule. With --graph the update is captured once and replayed: sixteen minibatches in one graph launch. The only sync
+of an update is its print. An example, not a test.
 
-    python scripts/train_helicopter_ppo.py --updates 20
+    python scripts/train_helicopter_ppo.py --updates 20 --anneal --graph
 """
 import argparse
 import os
@@ -25,6 +28,9 @@ def main():
     ap.add_argument("--epochs", type=int, default=4)
     ap.add_argument("--minibatches", type=int, default=4)
     ap.add_argument("--lr", type=float, default=2.5e-4)
+    ap.add_argument("--max-grad-norm", type=float, default=0.5, help="global-norm clip; 0 turns it off")
+    ap.add_argument("--anneal", action="store_true", help="the reference's linear schedule over --updates")
+    ap.add_argument("--graph", action="store_true", help="capture one update as a graph and replay it")
     ap.add_argument("--seed", type=int, default=1)
     args = ap.parse_args()
     import torch
@@ -38,37 +44,43 @@ def main():
     device = torch.device("cuda", 0)
     E, K = args.envs, args.steps
     T = E * K
-    N = T // args.minibatches
+    steps = args.epochs * args.minibatches
     env = BatchedForestFireHelicopterEnv(E, 42, 42, device=device, seed=args.seed, materialize_obs=False)
     env.reset()
     pol = HelicopterPolicy(env, radius=5, block=8, hidden=64, seed=args.seed)
-    gen = torch.Generator(device=device).manual_seed(args.seed)
-    # persistent buffers: the loop allocates nothing but the permutation
+    opt = ppo.Adam({n: getattr(pol, n) for n in WEIGHTS}, lr=args.lr, max_grad_norm=args.max_grad_norm,
+                   anneal=(steps, args.updates) if args.anneal else None)
+    # persistent buffers: the update allocates nothing
     adv, ret = torch.empty((K, E), device=device), torch.empty((K, E), device=device)
-    grads = {n: torch.empty_like(getattr(pol, n)) for n in WEIGHTS}
-    stats = torch.empty(8, device=device)
-    m = {n: torch.zeros_like(g) for n, g in grads.items()}
-    v = {n: torch.zeros_like(g) for n, g in grads.items()}
-    b1, b2, eps, step = 0.9, 0.999, 1e-5, 0
+    bufs = dict(stats_out=torch.empty((steps, 8), device=device), info_out=torch.empty((steps, 2), device=device),
+                perm_out=torch.empty((args.epochs, T), dtype=torch.int32, device=device),
+                grads_out={n: torch.empty_like(getattr(pol, n)) for n in WEIGHTS},
+                workspace=torch.empty_like(pol._ppo_workspace(T // args.minibatches, None)))
+    graph = rec0 = None
     for update in range(args.updates):
         rec = env.rollout_policy(pol, K, seed=args.seed + update)
         _, _, next_value = env.act(pol, seed=args.seed + update)
         ppo.gae(rec["reward"], rec["value"], next_value, 0.99, 0.95, adv_out=adv, ret_out=ret)
-        for _ in range(args.epochs):
-            perm = torch.randperm(T, generator=gen, device=device).to(torch.int32)
-            for mb in range(args.minibatches):
-                pol.ppo_grad(rec, adv, ret, perm[mb * N:(mb + 1) * N], clip_coef=0.2, ent_coef=0.01, vf_coef=0.5,
-                             grads_out=grads, stats_out=stats)
-                step += 1
-                for n in WEIGHTS:  # Adam, in place on the policy's own tensors
-                    g = grads[n]
-                    m[n].mul_(b1).add_(g, alpha=1 - b1)
-                    v[n].mul_(b2).addcmul_(g, g, value=1 - b2)
-                    denom = (v[n] / (1 - b2 ** step)).sqrt_().add_(eps)
-                    getattr(pol, n).addcdiv_(m[n], denom, value=-args.lr / (1 - b1 ** step))
-        s = stats.tolist()  # the update's one sync
+        run = lambda r: pol.ppo_update(opt, r, adv, ret, epochs=args.epochs, minibatches=args.minibatches,
+                                       seed=args.seed, **bufs)
+        if not args.graph:
+            run(rec)
+        else:
+            if graph is None:
+                # the graph reads the records at fixed addresses: the first rollout's tensors, refilled every update
+                rec0 = {k: rec[k] for k in ("local", "coarse", "action", "logits")}
+                torch.cuda.synchronize(device)
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph):
+                    run(rec0)
+            else:
+                for k, t in rec0.items():
+                    t.copy_(rec[k])
+            graph.replay()  # opt.count has moved since the last replay: new shuffles, the next learning rate
+        s, info = bufs["stats_out"][-1].tolist(), bufs["info_out"][-1].tolist()  # the update's one sync
         print(f"update {update:3d}  mean reward {rec['reward'].mean().item():+.4f}  loss {s[0]:+.4f}  "
-              f"pg {s[1]:+.5f}  v {s[2]:.4f}  entropy {s[3]:.4f}  kl {s[4]:.2e}  clip {s[5]:.3f}")
+              f"pg {s[1]:+.5f}  v {s[2]:.4f}  entropy {s[3]:.4f}  kl {s[4]:.2e}  clip {s[5]:.3f}  "
+              f"|g| {info[0]:.3f}  lr {info[1]:.2e}")
 
 
 if __name__ == "__main__":
