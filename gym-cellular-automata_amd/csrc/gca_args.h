@@ -1,0 +1,277 @@
+// gca_args.h — the argument contract of the entry points that libgca_hip.so (csrc/*.hip) and libgca_cpu.so
+// (gca_cpu.cpp) both export: one check function per entry point, or per group of checks that several share, holding
+// every refusal that does not depend on the build. Both builds call them first, so both refuse the same arguments
+// with the same words in the same order. What only one build can know (LDS fit, workgroup counts, plane alignment,
+// `scratch`, memset failures on the device; the idx scan and the walk's cap on the host) stays in that build, after
+// the shared call. Plain C++, no device code, like the two plan headers.
+#pragma once
+#include <stdint.h>
+
+#include "../../include/gca.h"
+#include "gca_opt_plan.h"
+#include "gca_ppo_plan.h"
+
+// ----------------------------------------------------------------- errors
+// Each library defines its own (gca_util.hip, gca_cpu.cpp); hidden, so that two libraries loaded into one process can
+// never bind each other's copy and thread-local message.
+__attribute__((visibility("hidden"))) void gca_set_error(const char* fmt, ...);
+
+#define GCA_CHECK_ARG(cond, msg)                 \
+    do {                                         \
+        if (!(cond)) {                           \
+            gca_set_error("argument: %s", msg);  \
+            return GCA_ERR_ARG;                  \
+        }                                        \
+    } while (0)
+
+// a refusal whose message the entry point `who` heads
+static inline int gca_refuse(const char* who, const char* what) {
+    gca_set_error("argument: %s: %s", who, what);
+    return GCA_ERR_ARG;
+}
+
+// ----------------------------------------------------------------- util, Move / Modify, Drossel-Schwabl
+static inline int gca_check_philox(const void* ctr, const void* out, int64_t n) {
+    GCA_CHECK_ARG(ctr && out && n >= 0, "ctr/out required");
+    return GCA_OK;
+}
+
+static inline int gca_check_count_cells(const void* grid, int E, int H, int W, const void* counts) {
+    GCA_CHECK_ARG(grid && counts && E > 0 && H > 0 && W > 0, "grid/counts and positive sizes required");
+    return GCA_OK;
+}
+
+static inline int gca_check_move_modify(const void* p, const void* action, const void* pos, int H, int W, int E) {
+    GCA_CHECK_ARG(p && action && pos && E > 0 && H > 0 && W > 0, "move_modify: bad arguments");
+    return GCA_OK;
+}
+
+static inline int gca_check_ds_count_draws(const void* grid, int E, int H, int W, const void* n_draws) {
+    GCA_CHECK_ARG(grid && n_draws && E > 0 && H > 0 && W > 0, "ds_count_draws: bad arguments");
+    GCA_CHECK_ARG((int64_t)H * W < (1 << 30), "ds_count_draws: grid too large");
+    return GCA_OK;
+}
+
+static inline int gca_check_ds_step(const void* grid_in, const void* grid_out, int E, int H, int W,
+                                    const void* thresholds, const void* uniforms, const void* uniform_offset) {
+    GCA_CHECK_ARG(grid_in && grid_out && thresholds && E > 0 && H > 0 && W > 0, "ds_step: bad arguments");
+    GCA_CHECK_ARG(grid_in != grid_out, "ds_step: in-place update is not supported");
+    GCA_CHECK_ARG(!uniforms || uniform_offset, "ds_step: uniforms need uniform_offset");
+    GCA_CHECK_ARG((int64_t)H * W < (1 << 30), "ds_step: grid too large");
+    return GCA_OK;
+}
+
+// ----------------------------------------------------------------- the helicopter env
+// The env arguments of gca_helicopter_step, gca_helicopter_rollout and gca_helicopter_policy_rollout.
+static inline int gca_check_heli_env(const char* who, int empty, int tree, int fire, int max_freeze,
+                                     const void* thresholds, const void* freeze, const void* rng_step,
+                                     const void* parity, const void* buf0, const void* buf1, int H, int W,
+                                     const void* pos, const void* counts, const void* hit, const void* reward,
+                                     const void* steps_elapsed, int E) {
+    if (!(thresholds && freeze && rng_step && parity && buf0 && buf1 && pos && counts && hit && reward &&
+          steps_elapsed))
+        return gca_refuse(who, "null argument");
+    if (!(E > 0 && H > 0 && W > 0 && max_freeze >= 0)) return gca_refuse(who, "E, H, W > 0 and max_freeze >= 0");
+    if (buf0 == buf1) return gca_refuse(who, "buf0 and buf1 must differ");
+    if ((int64_t)H * W >= (1 << 30)) return gca_refuse(who, "grid too large");
+    if (((empty | tree | fire) & ~0xFF) != 0 || empty == tree || tree == fire || empty == fire)
+        return gca_refuse(who, "three distinct u8 codes");
+    return GCA_OK;
+}
+
+static inline int gca_check_k(const char* who, int K) { return K >= 0 ? GCA_OK : gca_refuse(who, "K >= 0"); }
+
+static inline int gca_check_bulldozer_reset_where(const gca_bulldozer_params* p, int64_t max_steps,
+                                                  int64_t set_episode, const void* cdf, const void* values,
+                                                  const void* done, const void* episode, const void* accu,
+                                                  const void* parity, const void* buf0, const void* buf1, int H,
+                                                  int W, const void* pos, const void* counts, const void* hit,
+                                                  const void* steps_elapsed, int E) {
+    GCA_CHECK_ARG(p && cdf && values && done && episode && accu && parity && buf0 && buf1 && pos && counts && hit &&
+                      steps_elapsed,
+                  "bulldozer_reset_where: null argument");
+    GCA_CHECK_ARG(E > 0 && H > 0 && W > 0, "bulldozer_reset_where: E, H, W must be positive");
+    GCA_CHECK_ARG(H < 32768 && W < 32768, "bulldozer_reset_where: H, W < 32768");
+    GCA_CHECK_ARG(buf0 != buf1, "bulldozer_reset_where: buf0 and buf1 must differ");
+    GCA_CHECK_ARG(max_steps >= 0 && set_episode >= -1 && set_episode <= 0xFFFFFFFFll,
+                  "bulldozer_reset_where: max_steps >= 0 and set_episode in [-1, 2^32)");
+    GCA_CHECK_ARG(p->env_offset >= 0, "bulldozer_reset_where: env_offset >= 0");
+    return GCA_OK;
+}
+
+// ----------------------------------------------------------------- the policy observation
+// the shapes the device's rows form takes; `form` 2 asks for it by name
+static inline bool gca_policy_obs_rows_shape(int H, int W, int block) {
+    return (W == 256 || W == 512) && (block == 8 || block == 16 || block == 32) && H % block == 0;
+}
+
+static inline int gca_check_policy_observation(const void* buf0, const void* buf1, const void* parity,
+                                               const void* pos, int E, int H, int W, int empty, int tree, int fire,
+                                               int radius, int block, int form, const void* local_out,
+                                               const void* coarse_out) {
+    GCA_CHECK_ARG(buf0 && (buf1 || !parity), "policy_observation: buf0 required, and buf1 with parity");
+    GCA_CHECK_ARG(local_out || coarse_out, "policy_observation: local_out or coarse_out required");
+    GCA_CHECK_ARG(pos || !local_out, "policy_observation: local_out needs pos");
+    GCA_CHECK_ARG(E > 0 && H > 0 && W > 0, "policy_observation: E, H, W must be positive");
+    GCA_CHECK_ARG((int64_t)H * W < (1 << 30), "policy_observation: grid too large (H * W < 2^30)");
+    GCA_CHECK_ARG(((empty | tree | fire) & ~0xFF) == 0, "policy_observation: the codes must be u8 values");
+    GCA_CHECK_ARG(radius >= 0 && radius <= 31, "policy_observation: radius in [0, 31]");
+    GCA_CHECK_ARG(block >= 1 && block <= 64 && (block & (block - 1)) == 0,
+                  "policy_observation: block must be a power of two in [1, 64]");
+    GCA_CHECK_ARG(form >= 0 && form <= 2, "policy_observation: form 0 (by shape), 1 (generic) or 2 (rows)");
+    GCA_CHECK_ARG(form != 2 || gca_policy_obs_rows_shape(H, W, block),
+                  "policy_observation: form 2 (rows) needs W = 256 / 512, block = 8 / 16 / 32 and H % block == 0");
+    return GCA_OK;
+}
+
+// ----------------------------------------------------------------- the helicopter policy
+// The largest coarse map (C = 2 Hc Wc floats) of a policy: with the network's other LDS words (gca_heli.hip ties the
+// two together) it fills the 64 KiB of a workgroup. The host build keeps the same limit.
+constexpr int GCA_POLICY_C_MAX = 15088;
+
+static inline int gca_check_policy(const gca_heli_policy* p) {
+    GCA_CHECK_ARG(p && p->w_local && p->w_coarse && p->b1 && p->w_out && p->b2, "helicopter_policy: null weights");
+    GCA_CHECK_ARG(p->radius >= 0 && p->radius <= 31, "helicopter_policy: radius in [0, 31]");
+    GCA_CHECK_ARG(p->block >= 1 && p->block <= 64 && (p->block & (p->block - 1)) == 0,
+                  "helicopter_policy: block must be a power of two in [1, 64]");
+    GCA_CHECK_ARG(p->hidden >= 32 && p->hidden <= 256 && (p->hidden & (p->hidden - 1)) == 0,
+                  "helicopter_policy: hidden must be a power of two in [32, 256]");
+    return GCA_OK;
+}
+
+// the 16-B loads of the device's kernels; of a checked policy
+static inline bool gca_policy_weights_aligned(const gca_heli_policy* p) {
+    return (((uintptr_t)p->w_local | (uintptr_t)p->w_coarse) & 15u) == 0;
+}
+
+static inline int gca_check_policy_c(const char* who, int C) {
+    return (C >= 2 && C % 2 == 0 && C <= GCA_POLICY_C_MAX) ? GCA_OK : gca_refuse(who, "C = 2 Hc Wc, at most 15088");
+}
+
+static inline int gca_check_policy_act(const gca_heli_policy* p, int C, const void* local, const void* coarse,
+                                       const void* rng_step, const void* action, int E) {
+    if (const int st = gca_check_policy(p)) return st;
+    GCA_CHECK_ARG(local && coarse && rng_step && action, "helicopter_policy_act: null argument");
+    GCA_CHECK_ARG(E > 0, "helicopter_policy_act: E > 0");
+    return gca_check_policy_c("helicopter_policy_act", C);
+}
+
+// gca_helicopter_policy_rollout's refusal of a coarse map of C floats: above 2^30 at once, above what a build can
+// take where that build comes to need it
+static inline int gca_check_rollout_coarse(int64_t C, int64_t limit) {
+    GCA_CHECK_ARG(C <= limit, "helicopter_policy_rollout: coarse map too large");
+    return GCA_OK;
+}
+
+static inline int gca_check_policy_rollout(int empty, int tree, int fire, int max_freeze, const gca_heli_policy* p,
+                                           int K, const void* thresholds, const void* freeze, const void* rng_step,
+                                           const void* parity, const void* buf0, const void* buf1, int H, int W,
+                                           const void* pos, const void* counts, const void* hit, const void* reward,
+                                           const void* steps_elapsed, int E) {
+    const char* who = "helicopter_policy_rollout";
+    if (const int st = gca_check_heli_env(who, empty, tree, fire, max_freeze, thresholds, freeze, rng_step, parity, buf0,
+                                          buf1, H, W, pos, counts, hit, reward, steps_elapsed, E))
+        return st;
+    if (const int st = gca_check_k(who, K)) return st;
+    GCA_CHECK_ARG(p && p->block >= 1, "helicopter_policy_rollout: policy required");
+    const int64_t Hc = (H - 1) / p->block + 1, Wc = (W - 1) / p->block + 1;  // the ceilings, for any block >= 1
+    if (const int st = gca_check_rollout_coarse(2 * Hc * Wc, (1 << 30) - 1)) return st;
+    return gca_check_policy(p);
+}
+
+// ----------------------------------------------------------------- the PPO update
+static inline int gca_check_gae(const void* reward, const void* value, const void* next_value, int K, int E,
+                                const void* advantage, const void* returns) {
+    if (const int st = gca_check_k("gae", K)) return st;
+    GCA_CHECK_ARG(E > 0, "gae: E > 0");
+    GCA_CHECK_ARG(reward && value && next_value && advantage && returns, "gae: null argument");
+    return GCA_OK;
+}
+
+// a workspace query answers -1 where this refuses
+static inline int gca_check_policy_grad_workspace(const gca_heli_policy* p, int C, int N) {
+    GCA_CHECK_ARG(p && p->radius >= 0 && p->radius <= 31 && p->hidden >= 32 && p->hidden <= 256 &&
+                      (p->hidden & (p->hidden - 1)) == 0 && C >= 2 && C % 2 == 0 && C <= GCA_POLICY_C_MAX && N >= 1,
+                  "helicopter_policy_grad_workspace: radius in [0, 31], hidden a power of two in [32, 256], "
+                  "C = 2 Hc Wc at most 15088, N >= 1");
+    return GCA_OK;
+}
+
+static inline bool gca_overlap(const void* a, int64_t na, const void* b, int64_t nb) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
+}
+
+// *pl: the plan of the checked call. The alignment is the device's requirement, and the host build keeps it so that
+// a workspace or a policy moves between the builds as it is.
+static inline int gca_check_policy_grad(const gca_heli_policy* p, int C, const void* local, const void* coarse,
+                                        const void* action, const void* old_logits, const void* advantage,
+                                        const void* returns, int64_t T, const void* idx, int N, float clip_coef,
+                                        const void* g_w_local, const void* g_w_coarse, const void* g_b1,
+                                        const void* g_w_out, const void* g_b2, const void* stats,
+                                        const void* workspace, int64_t workspace_bytes, PpoPlan* pl) {
+    if (const int st = gca_check_policy(p)) return st;
+    GCA_CHECK_ARG(local && coarse && action && old_logits && advantage && returns,
+                  "helicopter_policy_grad: null record");
+    GCA_CHECK_ARG(g_w_local && g_w_coarse && g_b1 && g_w_out && g_b2 && stats && workspace,
+                  "helicopter_policy_grad: null output or workspace");
+    if (const int st = gca_check_policy_c("helicopter_policy_grad", C)) return st;
+    GCA_CHECK_ARG(T >= 1 && T < (1ll << 31), "helicopter_policy_grad: 1 <= T < 2^31");
+    GCA_CHECK_ARG(N >= 1, "helicopter_policy_grad: N >= 1");
+    GCA_CHECK_ARG(idx || N <= T, "helicopter_policy_grad: N <= T without idx");
+    GCA_CHECK_ARG(clip_coef >= 0.0f, "helicopter_policy_grad: clip_coef >= 0");
+    const int S = 2 * p->radius + 1, Hd = p->hidden;
+    *pl = ppo_plan(S * S, C, Hd, N);
+    GCA_CHECK_ARG(workspace_bytes >= pl->bytes,
+                  "helicopter_policy_grad: workspace smaller than gca_helicopter_policy_grad_workspace");
+    GCA_CHECK_ARG(gca_policy_weights_aligned(p) && (((uintptr_t)workspace | (uintptr_t)p->b1) & 15u) == 0,
+                  "helicopter_policy_grad: workspace, w_local, w_coarse and b1 16-B aligned");
+    const void* ptrs[11] = {g_w_local, g_w_coarse, g_b1, g_w_out, g_b2, stats,
+                            p->w_local, p->w_coarse, p->b1, p->w_out, p->b2};
+    const int64_t sizes[11] = {pl->off_wc * 4, (int64_t)C * Hd * 4, Hd * 4ll, Hd * 40ll, 40, 32,
+                               pl->off_wc * 4, (int64_t)C * Hd * 4, Hd * 4ll, Hd * 40ll, 40};
+    for (int i = 0; i < 6; ++i)
+        for (int j = i + 1; j < 11; ++j)
+            GCA_CHECK_ARG(!gca_overlap(ptrs[i], sizes[i], ptrs[j], sizes[j]),
+                          "helicopter_policy_grad: the outputs may alias neither each other nor the weights");
+    return GCA_OK;
+}
+
+// ----------------------------------------------------------------- the optimizer
+// a workspace query answers -1 where this refuses
+static inline int gca_check_adam_step_workspace(int64_t total_elements) {
+    GCA_CHECK_ARG(total_elements >= 1, "adam_step_workspace: total_elements >= 1");
+    return GCA_OK;
+}
+
+// *total: the elements of the checked call's tensors
+static inline int gca_check_adam_step(const gca_adam_tensors* t, const void* state, float b1, float b2, float eps,
+                                      int64_t steps_per_iteration, int64_t num_iterations, const void* info_out,
+                                      const void* workspace, int64_t workspace_bytes, int64_t* total) {
+    GCA_CHECK_ARG(t && state && workspace, "adam: null tensor table, state or workspace");
+    GCA_CHECK_ARG(t->n >= 1 && t->n <= GCA_ADAM_MAX_TENSORS, "adam: 1 to 8 tensors");
+    *total = 0;
+    uintptr_t low = (uintptr_t)state | (uintptr_t)info_out;
+    for (int i = 0; i < t->n; ++i) {
+        GCA_CHECK_ARG(t->w[i] && t->g[i] && t->m[i] && t->v[i], "adam: null tensor pointer");
+        GCA_CHECK_ARG(t->len[i] >= 1 && t->len[i] < (1ll << 31), "adam: tensor lengths in [1, 2^31)");
+        *total += t->len[i];
+        low |= (uintptr_t)t->w[i] | (uintptr_t)t->g[i] | (uintptr_t)t->m[i] | (uintptr_t)t->v[i];
+    }
+    GCA_CHECK_ARG((low & 3u) == 0, "adam: tensors, state and info_out 4-B aligned");
+    GCA_CHECK_ARG(((uintptr_t)workspace & 7u) == 0, "adam: workspace 8-B aligned");
+    GCA_CHECK_ARG(b1 >= 0.0f && b1 < 1.0f && b2 >= 0.0f && b2 < 1.0f, "adam: b1 and b2 in [0, 1)");
+    GCA_CHECK_ARG(eps >= 0.0f, "adam: eps >= 0");
+    GCA_CHECK_ARG((steps_per_iteration == 0 && num_iterations == 0) || (steps_per_iteration >= 1 && num_iterations >= 1),
+                  "adam: steps_per_iteration and num_iterations both 0 (no annealing) or both >= 1");
+    GCA_CHECK_ARG(workspace_bytes >= adam_workspace_bytes(*total), "adam: workspace smaller than gca_adam_step_workspace");
+    return GCA_OK;
+}
+
+static inline int gca_check_permutation(const void* counter, int64_t T, int rows, const void* out) {
+    GCA_CHECK_ARG(out, "permutation: null out");
+    GCA_CHECK_ARG(T >= 1 && T < (1ll << 31), "permutation: 1 <= T < 2^31");
+    GCA_CHECK_ARG(rows >= 1 && rows <= 65535, "permutation: 1 <= rows <= 65535");
+    GCA_CHECK_ARG((((uintptr_t)out | (uintptr_t)counter) & 3u) == 0, "permutation: out and counter 4-B aligned");
+    return GCA_OK;
+}

@@ -1,4 +1,5 @@
-// gca_common.h — shared device helpers for the gfx950 forest-fire kernels.
+// gca_common.h — shared device helpers for the gfx950 forest-fire kernels, and through gca_args.h the error setter,
+// GCA_CHECK_ARG and the argument checks that the device build shares with the host build (gca_cpu.cpp).
 // Product code: not shared with oracle/ (the oracle restates these independently).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -6,19 +7,9 @@
 #include <stdio.h>
 #include <string.h>
 
-#include "../../include/gca.h"
+#include "gca_args.h"
 
 // ----------------------------------------------------------------- errors
-void gca_set_error(const char* fmt, ...);
-
-#define GCA_CHECK_ARG(cond, msg)                 \
-    do {                                         \
-        if (!(cond)) {                           \
-            gca_set_error("argument: %s", msg);  \
-            return GCA_ERR_ARG;                  \
-        }                                        \
-    } while (0)
-
 #define GCA_CHECK_LAUNCH(name)                                                      \
     do {                                                                            \
         hipError_t _e = hipGetLastError();                                          \

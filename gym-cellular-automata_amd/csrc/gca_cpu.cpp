@@ -22,6 +22,11 @@
 //                     loss gradient in double as a second yardstick
 //   gca_adam_step(_workspace) / gca_permutation  the optimizer and the minibatch shuffle (gca_opt.hip), bit for bit
 //   gca_philox        Random123 Philox4x32-10 (KAT hook)
+//
+// Arguments: every entry point first calls its check function of gca_args.h, the same one the device build calls, so
+// both builds refuse the same arguments with the same words. The only checks written here are the two that the host
+// alone can make (the idx scan of gca_helicopter_policy_grad, the permutation walk's cap) and the rollout's coarse-map
+// limit, which the host applies for every K; each says so where it stands.
 #include <math.h>
 #include <stdarg.h>
 #include <stdint.h>
@@ -30,28 +35,19 @@
 
 #include <vector>
 
-#include "../../include/gca.h"
-#include "gca_opt_plan.h"
-#include "gca_ppo_plan.h"
+#include "gca_args.h"
 
-namespace {
+static thread_local char g_err[512] = "";
 
-thread_local char g_err[512] = "";
-
-void set_error(const char* fmt, ...) {
+// this library's own copy of the setter that gca_args.h declares (hidden there)
+void gca_set_error(const char* fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
 }
 
-#define CPU_CHECK_ARG(cond, msg)              \
-    do {                                      \
-        if (!(cond)) {                        \
-            set_error("argument: %s", msg);   \
-            return GCA_ERR_ARG;               \
-        }                                     \
-    } while (0)
+namespace {
 
 struct u32x4 {
     uint32_t x, y, z, w;
@@ -103,7 +99,7 @@ extern "C" const char* gca_last_error(void) { return g_err; }
 extern "C" int gca_version(void) { return 1; }
 
 extern "C" int gca_philox(const uint32_t* ctr, uint32_t key0, uint32_t key1, uint32_t* out, int64_t n, void*) {
-    CPU_CHECK_ARG(ctr && out && n >= 0, "ctr/out required");
+    if (const int st = gca_check_philox(ctr, out, n)) return st;
     for (int64_t i = 0; i < n; ++i) {
         const u32x4 x = philox4x32_10(u32x4{ctr[4 * i], ctr[4 * i + 1], ctr[4 * i + 2], ctr[4 * i + 3]}, key0, key1);
         out[4 * i] = x.x;
@@ -116,7 +112,7 @@ extern "C" int gca_philox(const uint32_t* ctr, uint32_t key0, uint32_t key1, uin
 
 extern "C" int gca_count_cells(const uint8_t* grid, int E, int H, int W, int v0, int v1, int v2, int32_t* counts,
                                void*) {
-    CPU_CHECK_ARG(grid && counts && E > 0 && H > 0 && W > 0, "grid/counts and positive sizes required");
+    if (const int st = gca_check_count_cells(grid, E, H, W, counts)) return st;
     const int64_t HW = (int64_t)H * W;
     for (int e = 0; e < E; ++e) {
         int32_t hist[256] = {0};
@@ -131,7 +127,7 @@ extern "C" int gca_count_cells(const uint8_t* grid, int E, int H, int W, int v0,
 
 extern "C" int gca_move_modify(const gca_bulldozer_params* p, const int32_t* action, int32_t* pos, uint8_t* grid, int H,
                                int W, uint8_t* hit, int E, void*) {
-    CPU_CHECK_ARG(p && action && pos && E > 0 && H > 0 && W > 0, "move_modify: bad arguments");
+    if (const int st = gca_check_move_modify(p, action, pos, H, W, E)) return st;
     for (int e = 0; e < E; ++e) {
         int row = pos[2 * e], col = pos[2 * e + 1];
         const int a0 = action[2 * e], a1 = action[2 * e + 1];
@@ -143,7 +139,7 @@ extern "C" int gca_move_modify(const gca_bulldozer_params* p, const int32_t* act
         // own value, never produced by Move) is refused like the device's bounds of the grid buffer
         if (grid && a1) {
             if (row < 0 || row >= H || col < 0 || col >= W) {
-                set_error("move_modify: position (%d, %d) outside the %dx%d grid", row, col, H, W);
+                gca_set_error("move_modify: position (%d, %d) outside the %dx%d grid", row, col, H, W);
                 return GCA_ERR_ARG;
             }
             uint8_t* g = grid + (int64_t)e * H * W + (int64_t)row * W + col;
@@ -160,8 +156,7 @@ extern "C" int gca_move_modify(const gca_bulldozer_params* p, const int32_t* act
 
 extern "C" int gca_ds_count_draws(const uint8_t* grid, int E, int H, int W, int empty, int tree, int fire,
                                   int32_t* n_draws, void*) {
-    CPU_CHECK_ARG(grid && n_draws && E > 0 && H > 0 && W > 0, "ds_count_draws: bad arguments");
-    CPU_CHECK_ARG((int64_t)H * W < (1 << 30), "ds_count_draws: grid too large");
+    if (const int st = gca_check_ds_count_draws(grid, E, H, W, n_draws)) return st;
     const int64_t HW = (int64_t)H * W;
     for (int e = 0; e < E; ++e) {
         const uint8_t* g = grid + e * HW;
@@ -179,10 +174,7 @@ extern "C" int gca_ds_count_draws(const uint8_t* grid, int E, int H, int W, int 
 extern "C" int gca_ds_step(const uint8_t* grid_in, uint8_t* grid_out, int E, int H, int W, int empty, int tree,
                            int fire, const double* thresholds, const double* uniforms, const int64_t* uniform_offset,
                            uint64_t seed, const uint32_t* rng_step, int env_offset, int32_t* counts, void*) {
-    CPU_CHECK_ARG(grid_in && grid_out && thresholds && E > 0 && H > 0 && W > 0, "ds_step: bad arguments");
-    CPU_CHECK_ARG(grid_in != grid_out, "ds_step: in-place update is not supported");
-    CPU_CHECK_ARG(!uniforms || uniform_offset, "ds_step: uniforms need uniform_offset");
-    CPU_CHECK_ARG((int64_t)H * W < (1 << 30), "ds_step: grid too large");
+    if (const int st = gca_check_ds_step(grid_in, grid_out, E, H, W, thresholds, uniforms, uniform_offset)) return st;
     const int64_t HW = (int64_t)H * W;
     const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
     for (int e = 0; e < E; ++e) {
@@ -226,17 +218,6 @@ extern "C" int gca_ds_step(const uint8_t* grid_in, uint8_t* grid_out, int E, int
     }
     return GCA_OK;
 }
-
-// The argument checks shared by gca_helicopter_step and gca_helicopter_rollout (`who` names the entry point).
-#define CPU_CHECK_HELI_ARGS(who)                                                                                       \
-    CPU_CHECK_ARG(thresholds && freeze && rng_step && parity && buf0 && buf1 && pos && counts && hit && reward &&      \
-                      steps_elapsed,                                                                                   \
-                  who ": null argument");                                                                              \
-    CPU_CHECK_ARG(E > 0 && H > 0 && W > 0 && max_freeze >= 0, who ": E, H, W > 0 and max_freeze >= 0");                \
-    CPU_CHECK_ARG(buf0 != buf1, who ": buf0 and buf1 must differ");                                                    \
-    CPU_CHECK_ARG((int64_t)H * W < (1 << 30), who ": grid too large");                                                 \
-    CPU_CHECK_ARG(((empty | tree | fire) & ~0xFF) == 0 && empty != tree && tree != fire && empty != fire,              \
-                  who ": three distinct u8 codes")
 
 // One batched ForestFireHelicopter env step of every env (gca_heli.hip) in plain loops: helicopter.py:220-236 +
 // ca_env.py:27-48. rec_reward / rec_hit (nullable): gca_helicopter_rollout's record rows of this step.
@@ -328,7 +309,9 @@ extern "C" int gca_helicopter_step(int empty, int tree, int fire, int max_freeze
                                    const double* thresholds, int32_t* freeze, uint32_t* rng_step, uint8_t* parity,
                                    uint8_t* buf0, uint8_t* buf1, int H, int W, int32_t* pos, int32_t* counts,
                                    uint8_t* hit, double* reward, int64_t* steps_elapsed, uint64_t*, int E, void*) {
-    CPU_CHECK_HELI_ARGS("helicopter_step");
+    if (const int st = gca_check_heli_env("helicopter_step", empty, tree, fire, max_freeze, thresholds, freeze, rng_step,
+                                          parity, buf0, buf1, H, W, pos, counts, hit, reward, steps_elapsed, E))
+        return st;
     helicopter_step_host(empty, tree, fire, max_freeze, seed, env_offset, action, action_seed, action_out, thresholds,
                          freeze, rng_step, parity, buf0, buf1, H, W, pos, counts, hit, reward, steps_elapsed, E,
                          nullptr, nullptr);
@@ -342,8 +325,10 @@ extern "C" int gca_helicopter_rollout(int empty, int tree, int fire, int max_fre
                                       uint32_t* rng_step, uint8_t* parity, uint8_t* buf0, uint8_t* buf1, int H, int W,
                                       int32_t* pos, int32_t* counts, uint8_t* hit, double* reward,
                                       int64_t* steps_elapsed, int E, void*) {
-    CPU_CHECK_HELI_ARGS("helicopter_rollout");
-    CPU_CHECK_ARG(K >= 0, "helicopter_rollout: K >= 0");
+    if (const int st = gca_check_heli_env("helicopter_rollout", empty, tree, fire, max_freeze, thresholds, freeze,
+                                          rng_step, parity, buf0, buf1, H, W, pos, counts, hit, reward, steps_elapsed, E))
+        return st;
+    if (const int st = gca_check_k("helicopter_rollout", K)) return st;
     for (int k = 0; k < K; ++k) {
         const size_t o = (size_t)k * (size_t)E;
         helicopter_step_host(empty, tree, fire, max_freeze, seed, env_offset, actions ? actions + o : nullptr,
@@ -375,15 +360,9 @@ extern "C" int gca_bulldozer_reset_where(const gca_bulldozer_params* p, uint64_t
                                          double* accu, uint8_t* parity, uint8_t* buf0, uint8_t* buf1, int H, int W,
                                          int32_t* pos, int32_t* counts, uint8_t* hit, int64_t* steps_elapsed, int E,
                                          void*) {
-    CPU_CHECK_ARG(p && cdf && values && done && episode && accu && parity && buf0 && buf1 && pos && counts && hit &&
-                      steps_elapsed,
-                  "bulldozer_reset_where: null argument");
-    CPU_CHECK_ARG(E > 0 && H > 0 && W > 0, "bulldozer_reset_where: E, H, W must be positive");
-    CPU_CHECK_ARG(H < 32768 && W < 32768, "bulldozer_reset_where: H, W < 32768");
-    CPU_CHECK_ARG(buf0 != buf1, "bulldozer_reset_where: buf0 and buf1 must differ");
-    CPU_CHECK_ARG(max_steps >= 0 && set_episode >= -1 && set_episode <= 0xFFFFFFFFll,
-                  "bulldozer_reset_where: max_steps >= 0 and set_episode in [-1, 2^32)");
-    CPU_CHECK_ARG(p->env_offset >= 0, "bulldozer_reset_where: env_offset >= 0");
+    if (const int st = gca_check_bulldozer_reset_where(p, max_steps, set_episode, cdf, values, done, episode, accu,
+                                                       parity, buf0, buf1, H, W, pos, counts, hit, steps_elapsed, E))
+        return st;
     const int64_t HW = (int64_t)H * W;
     const uint32_t k0 = (uint32_t)reset_seed, k1 = (uint32_t)(reset_seed >> 32);
     const uint32_t span_h = (uint32_t)(H / 12 > 1 ? H / 12 : 1), span_w = (uint32_t)(W / 12 > 1 ? W / 12 : 1);
@@ -430,23 +409,14 @@ extern "C" int gca_bulldozer_reset_where(const gca_bulldozer_params* p, uint64_t
     return GCA_OK;
 }
 
-// The policy observation of the batched envs (gca_policy_obs.hip) in plain loops. `form` is validated as the device
-// build validates it (alignment aside) and otherwise ignored.
+// The policy observation of the batched envs (gca_policy_obs.hip) in plain loops. `form` is validated with the other
+// arguments and otherwise ignored.
 extern "C" int gca_policy_observation(const uint8_t* buf0, const uint8_t* buf1, const uint8_t* parity,
                                       const int32_t* pos, int E, int H, int W, int empty, int tree, int fire, int radius,
                                       int block, int form, uint8_t* local_out, float* coarse_out, void*) {
-    CPU_CHECK_ARG(buf0 && (buf1 || !parity), "policy_observation: buf0 required, and buf1 with parity");
-    CPU_CHECK_ARG(local_out || coarse_out, "policy_observation: local_out or coarse_out required");
-    CPU_CHECK_ARG(pos || !local_out, "policy_observation: local_out needs pos");
-    CPU_CHECK_ARG(E > 0 && H > 0 && W > 0, "policy_observation: E, H, W must be positive");
-    CPU_CHECK_ARG((int64_t)H * W < (1 << 30), "policy_observation: grid too large (H * W < 2^30)");
-    CPU_CHECK_ARG(((empty | tree | fire) & ~0xFF) == 0, "policy_observation: the codes must be u8 values");
-    CPU_CHECK_ARG(radius >= 0 && radius <= 31, "policy_observation: radius in [0, 31]");
-    CPU_CHECK_ARG(block >= 1 && block <= 64 && (block & (block - 1)) == 0,
-                  "policy_observation: block must be a power of two in [1, 64]");
-    CPU_CHECK_ARG(form >= 0 && form <= 2, "policy_observation: form 0 (by shape), 1 (generic) or 2 (rows)");
-    CPU_CHECK_ARG(form != 2 || ((W == 256 || W == 512) && (block == 8 || block == 16 || block == 32) && H % block == 0),
-                  "policy_observation: form 2 (rows) needs W = 256 / 512, block = 8 / 16 / 32 and H % block == 0");
+    if (const int st = gca_check_policy_observation(buf0, buf1, parity, pos, E, H, W, empty, tree, fire, radius, block,
+                                                    form, local_out, coarse_out))
+        return st;
     const int64_t HW = (int64_t)H * W;
     const int S = 2 * radius + 1, Hc = (H + block - 1) / block, Wc = (W + block - 1) / block;
     const float inv = 1.0f / (float)(block * block);
@@ -508,16 +478,6 @@ static inline float exp_f32_host(float x) {
     bits += (uint32_t)k << 23;
     memcpy(&p, &bits, 4);
     return p;
-}
-
-static int policy_check_host(const gca_heli_policy* p) {
-    CPU_CHECK_ARG(p && p->w_local && p->w_coarse && p->b1 && p->w_out && p->b2, "helicopter_policy: null weights");
-    CPU_CHECK_ARG(p->radius >= 0 && p->radius <= 31, "helicopter_policy: radius in [0, 31]");
-    CPU_CHECK_ARG(p->block >= 1 && p->block <= 64 && (p->block & (p->block - 1)) == 0,
-                  "helicopter_policy: block must be a power of two in [1, 64]");
-    CPU_CHECK_ARG(p->hidden >= 32 && p->hidden <= 256 && (p->hidden & (p->hidden - 1)) == 0,
-                  "helicopter_policy: hidden must be a power of two in [32, 256]");
-    return GCA_OK;
 }
 
 // One env's outputs and action in gca.h's order. loc [S*S], coarse [C]; out [10] receives the logits and the value.
@@ -585,10 +545,7 @@ static void policy_act_host(const gca_heli_policy* p, int C, const uint8_t* loca
 extern "C" int gca_helicopter_policy_act(const gca_heli_policy* p, int C, const uint8_t* local, const float* coarse,
                                          const uint32_t* rng_step, int env_offset, uint64_t policy_seed, int greedy,
                                          int32_t* action, float* logits, float* value, int E, void*) {
-    if (const int st = policy_check_host(p)) return st;
-    CPU_CHECK_ARG(local && coarse && rng_step && action, "helicopter_policy_act: null argument");
-    CPU_CHECK_ARG(E > 0, "helicopter_policy_act: E > 0");
-    CPU_CHECK_ARG(C >= 2 && C % 2 == 0 && C <= 15088, "helicopter_policy_act: C = 2 Hc Wc, at most 15088");
+    if (const int st = gca_check_policy_act(p, C, local, coarse, rng_step, action, E)) return st;
     policy_act_host(p, C, local, coarse, rng_step, env_offset, policy_seed, greedy, action, logits, value, E);
     return GCA_OK;
 }
@@ -602,12 +559,13 @@ extern "C" int gca_helicopter_policy_rollout(int empty, int tree, int fire, int 
                                              uint32_t* rng_step, uint8_t* parity, uint8_t* buf0, uint8_t* buf1, int H,
                                              int W, int32_t* pos, int32_t* counts, uint8_t* hit, double* reward,
                                              int64_t* steps_elapsed, int E, void*) {
-    CPU_CHECK_HELI_ARGS("helicopter_policy_rollout");
-    CPU_CHECK_ARG(K >= 0, "helicopter_policy_rollout: K >= 0");
-    if (const int st = policy_check_host(p)) return st;
+    if (const int st = gca_check_policy_rollout(empty, tree, fire, max_freeze, p, K, thresholds, freeze, rng_step, parity,
+                                                buf0, buf1, H, W, pos, counts, hit, reward, steps_elapsed, E))
+        return st;
     const int S = 2 * p->radius + 1, Hc = (H + p->block - 1) / p->block, Wc = (W + p->block - 1) / p->block;
-    CPU_CHECK_ARG(2 * (int64_t)Hc * Wc <= 15088, "helicopter_policy_rollout: coarse map too large");
     const int C = 2 * Hc * Wc;
+    // the host build has one path and refuses this for every K; the device build only on its way to a launch
+    if (const int st = gca_check_rollout_coarse(C, GCA_POLICY_C_MAX)) return st;
     const size_t SS = (size_t)S * S;
     std::vector<int32_t> act((size_t)E);
     std::vector<uint8_t> loc((size_t)E * SS);
@@ -633,9 +591,7 @@ extern "C" int gca_helicopter_policy_rollout(int empty, int tree, int fire, int 
 // The recurrence of gca.h, one rounded f32 operation at a time (the file is built with -ffp-contract=off).
 extern "C" int gca_gae(const double* reward, const float* value, const float* next_value, const uint8_t* terminal,
                        float gamma, float gamma_lambda, int K, int E, float* advantage, float* returns, void*) {
-    CPU_CHECK_ARG(K >= 0, "gae: K >= 0");
-    CPU_CHECK_ARG(E > 0, "gae: E > 0");
-    CPU_CHECK_ARG(reward && value && next_value && advantage && returns, "gae: null argument");
+    if (const int st = gca_check_gae(reward, value, next_value, K, E, advantage, returns)) return st;
     for (int e = 0; e < E; ++e) {
         float A = 0.0f, nv = next_value[e];
         for (int k = K - 1; k >= 0; --k) {
@@ -654,12 +610,7 @@ extern "C" int gca_gae(const double* reward, const float* value, const float* ne
 }
 
 extern "C" int64_t gca_helicopter_policy_grad_workspace(const gca_heli_policy* p, int C, int N) {
-    if (!p || p->radius < 0 || p->radius > 31 || p->hidden < 32 || p->hidden > 256 || (p->hidden & (p->hidden - 1)) ||
-        C < 2 || C % 2 || C > 15088 || N < 1) {
-        set_error("argument: %s", "helicopter_policy_grad_workspace: radius in [0, 31], hidden a power of two in "
-                                  "[32, 256], C = 2 Hc Wc at most 15088, N >= 1");
-        return -1;
-    }
+    if (gca_check_policy_grad_workspace(p, C, N)) return -1;
     const int S = 2 * p->radius + 1;
     return ppo_plan(S * S, C, p->hidden, N).bytes;
 }
@@ -672,11 +623,6 @@ static double lse9_host(const double* l) {
     return m + log(s);
 }
 
-static bool ppo_overlap_host(const void* a, int64_t na, const void* b, int64_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
-}
-
 // Plain loops: the network, the loss and every gradient sum in double, rounded to f32 once. The workspace is checked
 // as on the device and not used.
 extern "C" int gca_helicopter_policy_grad(const gca_heli_policy* p, int C, const uint8_t* local, const float* coarse,
@@ -685,34 +631,15 @@ extern "C" int gca_helicopter_policy_grad(const gca_heli_policy* p, int C, const
                                           float ent_coef, float vf_coef, int norm_adv, float* g_w_local,
                                           float* g_w_coarse, float* g_b1, float* g_w_out, float* g_b2, float* stats,
                                           void* workspace, int64_t workspace_bytes, void*) {
-    if (const int st = policy_check_host(p)) return st;
-    CPU_CHECK_ARG(local && coarse && action && old_logits && advantage && returns,
-                  "helicopter_policy_grad: null record");
-    CPU_CHECK_ARG(g_w_local && g_w_coarse && g_b1 && g_w_out && g_b2 && stats && workspace,
-                  "helicopter_policy_grad: null output or workspace");
-    CPU_CHECK_ARG(C >= 2 && C % 2 == 0 && C <= 15088, "helicopter_policy_grad: C = 2 Hc Wc, at most 15088");
-    CPU_CHECK_ARG(T >= 1 && T < (1ll << 31), "helicopter_policy_grad: 1 <= T < 2^31");
-    CPU_CHECK_ARG(N >= 1, "helicopter_policy_grad: N >= 1");
-    CPU_CHECK_ARG(idx || N <= T, "helicopter_policy_grad: N <= T without idx");
-    CPU_CHECK_ARG(clip_coef >= 0.0f, "helicopter_policy_grad: clip_coef >= 0");
+    PpoPlan pl;
+    if (const int st = gca_check_policy_grad(p, C, local, coarse, action, old_logits, advantage, returns, T, idx, N,
+                                             clip_coef, g_w_local, g_w_coarse, g_b1, g_w_out, g_b2, stats, workspace,
+                                             workspace_bytes, &pl))
+        return st;
     const int S = 2 * p->radius + 1, SS = S * S, Hd = p->hidden;
-    const PpoPlan pl = ppo_plan(SS, C, Hd, N);
-    CPU_CHECK_ARG(workspace_bytes >= pl.bytes,
-                  "helicopter_policy_grad: workspace smaller than gca_helicopter_policy_grad_workspace");
-    // the device's requirement, checked here too so that both builds refuse the same arguments
-    const uintptr_t aligned = (uintptr_t)workspace | (uintptr_t)p->w_local | (uintptr_t)p->w_coarse | (uintptr_t)p->b1;
-    CPU_CHECK_ARG((aligned & 15u) == 0,
-                  "helicopter_policy_grad: workspace, w_local, w_coarse and b1 16-B aligned");
-    const void* ptrs[11] = {g_w_local, g_w_coarse, g_b1, g_w_out, g_b2, stats,
-                            p->w_local, p->w_coarse, p->b1, p->w_out, p->b2};
-    const int64_t sizes[11] = {pl.off_wc * 4, (int64_t)C * Hd * 4, Hd * 4ll, Hd * 40ll, 40, 32,
-                               pl.off_wc * 4, (int64_t)C * Hd * 4, Hd * 4ll, Hd * 40ll, 40};
-    for (int i = 0; i < 6; ++i)
-        for (int j = i + 1; j < 11; ++j)
-            CPU_CHECK_ARG(!ppo_overlap_host(ptrs[i], sizes[i], ptrs[j], sizes[j]),
-                          "helicopter_policy_grad: the outputs may alias neither each other nor the weights");
+    // idx is host memory here, so the host build alone can read it before it indexes with it
     if (idx)
-        for (int t = 0; t < N; ++t) CPU_CHECK_ARG(idx[t] >= 0 && idx[t] < T, "helicopter_policy_grad: idx outside [0, T)");
+        for (int t = 0; t < N; ++t) GCA_CHECK_ARG(idx[t] >= 0 && idx[t] < T, "helicopter_policy_grad: idx outside [0, T)");
     auto row_of = [&](int t) { return idx ? (size_t)idx[t] : (size_t)t; };
     double mean = 0.0, var = 0.0;
     for (int t = 0; t < N; ++t) mean += advantage[row_of(t)];
@@ -817,33 +744,17 @@ static double adam_tree_host(double* s) {
 }
 
 extern "C" int64_t gca_adam_step_workspace(int64_t total_elements) {
-    if (total_elements < 1) {
-        set_error("argument: %s", "adam_step_workspace: total_elements >= 1");
-        return -1;
-    }
+    if (gca_check_adam_step_workspace(total_elements)) return -1;
     return adam_workspace_bytes(total_elements);
 }
 
 extern "C" int gca_adam_step(const gca_adam_tensors* t, void* state, float lr0, float b1, float b2, float eps,
                              float max_norm, int64_t steps_per_iteration, int64_t num_iterations, float* info_out,
                              void* workspace, int64_t workspace_bytes, void*) {
-    CPU_CHECK_ARG(t && state && workspace, "adam: null tensor table, state or workspace");
-    CPU_CHECK_ARG(t->n >= 1 && t->n <= GCA_ADAM_MAX_TENSORS, "adam: 1 to 8 tensors");
-    int64_t total = 0;
-    uintptr_t low = (uintptr_t)state | (uintptr_t)info_out;
-    for (int i = 0; i < t->n; ++i) {
-        CPU_CHECK_ARG(t->w[i] && t->g[i] && t->m[i] && t->v[i], "adam: null tensor pointer");
-        CPU_CHECK_ARG(t->len[i] >= 1 && t->len[i] < (1ll << 31), "adam: tensor lengths in [1, 2^31)");
-        total += t->len[i];
-        low |= (uintptr_t)t->w[i] | (uintptr_t)t->g[i] | (uintptr_t)t->m[i] | (uintptr_t)t->v[i];
-    }
-    CPU_CHECK_ARG((low & 3u) == 0, "adam: tensors, state and info_out 4-B aligned");
-    CPU_CHECK_ARG(((uintptr_t)workspace & 7u) == 0, "adam: workspace 8-B aligned");
-    CPU_CHECK_ARG(b1 >= 0.0f && b1 < 1.0f && b2 >= 0.0f && b2 < 1.0f, "adam: b1 and b2 in [0, 1)");
-    CPU_CHECK_ARG(eps >= 0.0f, "adam: eps >= 0");
-    CPU_CHECK_ARG((steps_per_iteration == 0 && num_iterations == 0) || (steps_per_iteration >= 1 && num_iterations >= 1),
-                  "adam: steps_per_iteration and num_iterations both 0 (no annealing) or both >= 1");
-    CPU_CHECK_ARG(workspace_bytes >= adam_workspace_bytes(total), "adam: workspace smaller than gca_adam_step_workspace");
+    int64_t total;
+    if (const int st = gca_check_adam_step(t, state, b1, b2, eps, steps_per_iteration, num_iterations, info_out,
+                                           workspace, workspace_bytes, &total))
+        return st;
     const int64_t CH = adam_chunk(total);
     std::vector<double> part;
     double s[ADAM_THREADS];
@@ -894,10 +805,7 @@ extern "C" int gca_adam_step(const gca_adam_tensors* t, void* state, float lr0, 
 
 extern "C" int gca_permutation(uint64_t seed, uint32_t epoch0, const int32_t* counter, int64_t T, int rows,
                                int32_t* out, void*) {
-    CPU_CHECK_ARG(out, "permutation: null out");
-    CPU_CHECK_ARG(T >= 1 && T < (1ll << 31), "permutation: 1 <= T < 2^31");
-    CPU_CHECK_ARG(rows >= 1 && rows <= 65535, "permutation: 1 <= rows <= 65535");
-    CPU_CHECK_ARG((((uintptr_t)out | (uintptr_t)counter) & 3u) == 0, "permutation: out and counter 4-B aligned");
+    if (const int st = gca_check_permutation(counter, T, rows, out)) return st;
     const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
     const auto f = [k0, k1](uint32_t right, uint32_t round, uint32_t row_key) {
         return philox4x32_10(u32x4{right, round, row_key, GCA_TAG_PERM}, k0, k1).x;
@@ -909,8 +817,9 @@ extern "C" int gca_permutation(uint64_t seed, uint32_t epoch0, const int32_t* co
         for (int64_t i = 0; i < T; ++i)
             out[(size_t)r * T + i] = (int32_t)perm_walk((uint32_t)i, (uint32_t)T, h, row_key, f, &capped);
     }
+    // the host build alone sees its walks: a kernel cannot report one that reached the cap
     if (capped) {
-        set_error("internal: %s", "permutation: the walk reached its cap");
+        gca_set_error("internal: %s", "permutation: the walk reached its cap");
         return GCA_ERR_UNSUPPORTED;
     }
     return GCA_OK;

@@ -127,8 +127,7 @@ __global__ __launch_bounds__(256) void ds_step_kernel(const uint8_t* __restrict_
 
 extern "C" int gca_ds_count_draws(const uint8_t* grid, int E, int H, int W, int empty, int tree, int fire,
                                   int32_t* n_draws, void* stream) {
-    GCA_CHECK_ARG(grid && n_draws && E > 0 && H > 0 && W > 0, "ds_count_draws: bad arguments");
-    GCA_CHECK_ARG((int64_t)H * W < (1 << 30), "ds_count_draws: grid too large");
+    if (const int st = gca_check_ds_count_draws(grid, E, H, W, n_draws)) return st;
     hipLaunchKernelGGL(ds_count_kernel, dim3(E), dim3(256), 0, (hipStream_t)stream, grid, H, W, empty, tree, fire,
                        n_draws);
     GCA_CHECK_LAUNCH("ds_count_draws");
@@ -138,11 +137,9 @@ extern "C" int gca_ds_count_draws(const uint8_t* grid, int E, int H, int W, int 
 extern "C" int gca_ds_step(const uint8_t* grid_in, uint8_t* grid_out, int E, int H, int W, int empty, int tree,
                            int fire, const double* thresholds, const double* uniforms, const int64_t* uniform_offset,
                            uint64_t seed, const uint32_t* rng_step, int env_offset, int32_t* counts, void* stream) {
-    GCA_CHECK_ARG(grid_in && grid_out && thresholds && E > 0 && H > 0 && W > 0, "ds_step: bad arguments");
-    GCA_CHECK_ARG(grid_in != grid_out, "ds_step: in-place update is not supported");
-    GCA_CHECK_ARG(!uniforms || uniform_offset, "ds_step: uniforms need uniform_offset");
-    GCA_CHECK_ARG((int64_t)H * W < (1 << 30), "ds_step: grid too large");
+    if (const int st = gca_check_ds_step(grid_in, grid_out, E, H, W, thresholds, uniforms, uniform_offset)) return st;
     hipStream_t st = (hipStream_t)stream;
+    // the device build alone zeroes the counts with a call that can fail
     if (counts && hipMemsetAsync(counts, 0, sizeof(int32_t) * 3 * (size_t)E, st) != hipSuccess) {
         gca_set_error("ds_step: counts memset failed");
         return GCA_ERR_HIP;

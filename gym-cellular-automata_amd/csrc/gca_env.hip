@@ -283,7 +283,7 @@ __global__ void move_modify_kernel(const int32_t* __restrict__ action, int32_t* 
 
 extern "C" int gca_move_modify(const gca_bulldozer_params* p, const int32_t* action, int32_t* pos, uint8_t* grid, int H,
                                int W, uint8_t* hit, int E, void* stream) {
-    GCA_CHECK_ARG(p && action && pos && E > 0 && H > 0 && W > 0, "move_modify: bad arguments");
+    if (const int st = gca_check_move_modify(p, action, pos, H, W, E)) return st;
     hipLaunchKernelGGL(move_modify_kernel, ENV_GRID(E), 0, (hipStream_t)stream, action, pos, grid, H, W, *p, hit, E);
     GCA_CHECK_LAUNCH("move_modify");
     return GCA_OK;

@@ -745,20 +745,10 @@ __global__ __launch_bounds__(POL_THREADS) void helicopter_policy_act_kernel(
 
 // ---------------------------------------------------------------- host side
 // The entry points that step the envs put their arguments into a HeliArgs `a` first (one workgroup per env, no `meet`);
-// these are their shared argument checks, `who` heading the message.
+// this hands its fields to their shared argument checks, `who` heading the message.
 int heli_check_env(const char* who, const HeliArgs& a, int E) {
-    const char* bad = nullptr;
-    if (!(a.thr && a.freeze && a.rng_step && a.parity && a.buf0 && a.buf1 && a.pos && a.counts && a.hit && a.reward &&
-          a.steps_elapsed))
-        bad = "null argument";
-    else if (!(E > 0 && a.H > 0 && a.W > 0 && a.max_freeze >= 0)) bad = "E, H, W > 0 and max_freeze >= 0";
-    else if (a.buf0 == a.buf1) bad = "buf0 and buf1 must differ";
-    else if ((int64_t)a.H * a.W >= (1 << 30)) bad = "grid too large";
-    else if (((a.empty | a.tree | a.fire) & ~0xFF) != 0 || a.empty == a.tree || a.tree == a.fire || a.empty == a.fire)
-        bad = "three distinct u8 codes";
-    if (!bad) return GCA_OK;
-    gca_set_error("argument: %s: %s", who, bad);
-    return GCA_ERR_ARG;
+    return gca_check_heli_env(who, a.empty, a.tree, a.fire, a.max_freeze, a.thr, a.freeze, a.rng_step, a.parity, a.buf0,
+                              a.buf1, a.H, a.W, a.pos, a.counts, a.hit, a.reward, a.steps_elapsed, E);
 }
 
 bool heli_aligned(const HeliArgs& a) { return (((uintptr_t)a.buf0 | (uintptr_t)a.buf1) & 3u) == 0; }
@@ -810,6 +800,7 @@ extern "C" int gca_helicopter_step(int empty, int tree, int fire, int max_freeze
     int P = 1;
     if (meet && HW + 1 < (1 << 20))
         while (P < 8 && (int64_t)E * P < 1024 && 2 * P <= units) P *= 2;
+    // the launch's 32-bit workgroup count: the host build launches nothing
     GCA_CHECK_ARG((int64_t)E * P < (1ll << 31), "helicopter_step: too many workgroups");
     a.meet = P > 1 ? (unsigned long long*)meet : nullptr;
     a.P = P;
@@ -828,7 +819,7 @@ extern "C" int gca_helicopter_rollout(int empty, int tree, int fire, int max_fre
                freeze, rng_step, parity, buf0,       buf1, H,           W,          pos,     counts,  hit,
                reward, steps_elapsed, nullptr, 1, nullptr, nullptr};
     if (const int st = heli_check_env("helicopter_rollout", a, E)) return st;
-    GCA_CHECK_ARG(K >= 0, "helicopter_rollout: K >= 0");
+    if (const int st = gca_check_k("helicopter_rollout", K)) return st;
     if (K == 0) return GCA_OK;
     const dim3 grid((unsigned)E);
     HeliRollArgs ra;
@@ -855,16 +846,13 @@ extern "C" int gca_helicopter_rollout(int empty, int tree, int fire, int max_fre
 // ---------------------------------------------------------------- the helicopter policy (gca.h "helicopter policy")
 namespace {
 
-// the checks gca_helicopter_policy_act and gca_helicopter_policy_rollout share, and the device's view of the weights
-int heli_policy_check(const gca_heli_policy* p, int C, uint64_t policy_seed, int greedy, HeliPolicyW* w) {
-    GCA_CHECK_ARG(p && p->w_local && p->w_coarse && p->b1 && p->w_out && p->b2, "helicopter_policy: null weights");
-    GCA_CHECK_ARG((((uintptr_t)p->w_local | (uintptr_t)p->w_coarse) & 15u) == 0,
-                  "helicopter_policy: w_local and w_coarse must be 16-B aligned");
-    GCA_CHECK_ARG(p->radius >= 0 && p->radius <= 31, "helicopter_policy: radius in [0, 31]");
-    GCA_CHECK_ARG(p->block >= 1 && p->block <= 64 && (p->block & (p->block - 1)) == 0,
-                  "helicopter_policy: block must be a power of two in [1, 64]");
-    GCA_CHECK_ARG(p->hidden >= 32 && p->hidden <= 256 && (p->hidden & (p->hidden - 1)) == 0,
-                  "helicopter_policy: hidden must be a power of two in [32, 256]");
+// the largest coarse map the shared checks admit is the one whose network words fill a workgroup's 64 KiB of LDS
+static_assert(heli_policy_lds_words(GCA_POLICY_C_MAX) * 4 == 65536, "GCA_POLICY_C_MAX must follow heli_policy_lds_words");
+
+// The device's view of the weights of a checked policy, for gca_helicopter_policy_act and gca_helicopter_policy_rollout.
+int heli_policy_view(const gca_heli_policy* p, int C, uint64_t policy_seed, int greedy, HeliPolicyW* w) {
+    // the kernels' 16-B loads of the weights: the host build's loops take any alignment
+    GCA_CHECK_ARG(gca_policy_weights_aligned(p), "helicopter_policy: w_local and w_coarse must be 16-B aligned");
     w->w_local = p->w_local; w->w_coarse = p->w_coarse; w->b1 = p->b1; w->w_out = p->w_out; w->b2 = p->b2;
     w->S = 2 * p->radius + 1;
     w->SS = w->S * w->S;
@@ -883,12 +871,9 @@ int heli_policy_check(const gca_heli_policy* p, int C, uint64_t policy_seed, int
 extern "C" int gca_helicopter_policy_act(const gca_heli_policy* p, int C, const uint8_t* local, const float* coarse,
                                          const uint32_t* rng_step, int env_offset, uint64_t policy_seed, int greedy,
                                          int32_t* action, float* logits, float* value, int E, void* stream) {
+    if (const int st = gca_check_policy_act(p, C, local, coarse, rng_step, action, E)) return st;
     HeliPolicyW w;
-    if (const int st = heli_policy_check(p, C, policy_seed, greedy, &w)) return st;
-    GCA_CHECK_ARG(local && coarse && rng_step && action, "helicopter_policy_act: null argument");
-    GCA_CHECK_ARG(E > 0, "helicopter_policy_act: E > 0");
-    GCA_CHECK_ARG(C >= 2 && C % 2 == 0 && (size_t)heli_policy_lds_words(C) * 4 <= 65536,
-                  "helicopter_policy_act: C = 2 Hc Wc, at most 15088");
+    if (const int st = heli_policy_view(p, C, policy_seed, greedy, &w)) return st;
     hipLaunchKernelGGL(helicopter_policy_act_kernel, dim3((unsigned)E), dim3(POL_THREADS),
                        (size_t)heli_policy_lds_words(C) * 4, (hipStream_t)stream, w, local, coarse, rng_step,
                        env_offset, action, logits, value);
@@ -907,15 +892,12 @@ extern "C" int gca_helicopter_policy_rollout(int empty, int tree, int fire, int 
     HeliArgs a{empty,  tree,     fire,   max_freeze, seed, 0, env_offset, nullptr, nullptr, thresholds,
                freeze, rng_step, parity, buf0,       buf1, H, W,          pos,     counts,  hit,
                reward, steps_elapsed, nullptr, 1, nullptr, nullptr};
-    if (const int st = heli_check_env("helicopter_policy_rollout", a, E)) return st;
-    GCA_CHECK_ARG(K >= 0, "helicopter_policy_rollout: K >= 0");
-    GCA_CHECK_ARG(p && p->block >= 1, "helicopter_policy_rollout: policy required");
-    const int Hc = (H + p->block - 1) / p->block, Wc = (W + p->block - 1) / p->block;
-    const int64_t C64 = 2 * (int64_t)Hc * Wc;
-    GCA_CHECK_ARG(C64 < (1 << 30), "helicopter_policy_rollout: coarse map too large");
-    const int C = (int)C64;
+    if (const int st = gca_check_policy_rollout(empty, tree, fire, max_freeze, p, K, thresholds, freeze, rng_step, parity,
+                                                buf0, buf1, H, W, pos, counts, hit, reward, steps_elapsed, E))
+        return st;
+    const int Hc = (H + p->block - 1) / p->block, Wc = (W + p->block - 1) / p->block, C = 2 * Hc * Wc;
     HeliPolArgs q;
-    if (const int st = heli_policy_check(p, C, policy_seed, greedy, &q.w)) return st;
+    if (const int st = heli_policy_view(p, C, policy_seed, greedy, &q.w)) return st;
     if (K == 0) return GCA_OK;
     const dim3 grid((unsigned)E);
     HeliRollArgs ra;
@@ -936,9 +918,11 @@ extern "C" int gca_helicopter_policy_rollout(int empty, int tree, int fire, int 
     // The planes and the network's words do not fit in LDS: K x (observation, act, step) launches. A step's action, window
     // and coarse map go to their record rows, or to `scratch` where the caller keeps no such record.
     const size_t SS = (size_t)q.w.SS;
+    // only the device build has this path: the host build keeps its own buffers
     GCA_CHECK_ARG(scratch || (action_out && local_out && coarse_out),
                   "helicopter_policy_rollout: this shape runs K x 3 launches and needs `scratch` for the records not kept");
-    GCA_CHECK_ARG((size_t)heli_policy_lds_words(C) * 4 <= 65536, "helicopter_policy_rollout: coarse map too large");
+    // the act kernel's LDS: met only here, on the way to its launch (K > 0, after the `scratch` test)
+    if (const int st = gca_check_rollout_coarse(C, GCA_POLICY_C_MAX)) return st;
     int32_t* s_act = (int32_t*)scratch;
     float* s_coarse = (float*)scratch + E;
     uint8_t* s_local = (uint8_t*)(s_coarse + (size_t)E * C);

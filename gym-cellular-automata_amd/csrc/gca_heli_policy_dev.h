@@ -34,7 +34,7 @@ struct HeliPolicyW {
 };
 
 // LDS words of one evaluation: the coarse map (rounded up to 4 words), the partials, the hidden vector, the outputs
-__host__ __device__ inline int heli_policy_lds_words(int C) { return ((C + 3) & ~3) + POL_PART + POL_THREADS + 16; }
+__host__ __device__ constexpr int heli_policy_lds_words(int C) { return ((C + 3) & ~3) + POL_PART + POL_THREADS + 16; }
 
 // The action from the nine logits l (gca.h "sampling"). Comparisons only, no fmax: NaN logits give an action in [0, 8].
 // Every wave runs it whole (all 64 lanes active) and every lane gets the same action. The nine exponentials are one

@@ -173,33 +173,17 @@ __global__ __launch_bounds__(ADAM_THREADS) void adam_update_kernel(AdamArgs a, i
 }
 
 extern "C" int64_t gca_adam_step_workspace(int64_t total_elements) {
-    if (total_elements < 1) {
-        gca_set_error("argument: %s", "adam_step_workspace: total_elements >= 1");
-        return -1;
-    }
+    if (gca_check_adam_step_workspace(total_elements)) return -1;
     return adam_workspace_bytes(total_elements);
 }
 
 extern "C" int gca_adam_step(const gca_adam_tensors* t, void* state, float lr0, float b1, float b2, float eps,
                              float max_norm, int64_t steps_per_iteration, int64_t num_iterations, float* info_out,
                              void* workspace, int64_t workspace_bytes, void* stream) {
-    GCA_CHECK_ARG(t && state && workspace, "adam: null tensor table, state or workspace");
-    GCA_CHECK_ARG(t->n >= 1 && t->n <= GCA_ADAM_MAX_TENSORS, "adam: 1 to 8 tensors");
-    int64_t total = 0;
-    uintptr_t low = (uintptr_t)state | (uintptr_t)info_out;
-    for (int i = 0; i < t->n; ++i) {
-        GCA_CHECK_ARG(t->w[i] && t->g[i] && t->m[i] && t->v[i], "adam: null tensor pointer");
-        GCA_CHECK_ARG(t->len[i] >= 1 && t->len[i] < (1ll << 31), "adam: tensor lengths in [1, 2^31)");
-        total += t->len[i];
-        low |= (uintptr_t)t->w[i] | (uintptr_t)t->g[i] | (uintptr_t)t->m[i] | (uintptr_t)t->v[i];
-    }
-    GCA_CHECK_ARG((low & 3u) == 0, "adam: tensors, state and info_out 4-B aligned");
-    GCA_CHECK_ARG(((uintptr_t)workspace & 7u) == 0, "adam: workspace 8-B aligned");
-    GCA_CHECK_ARG(b1 >= 0.0f && b1 < 1.0f && b2 >= 0.0f && b2 < 1.0f, "adam: b1 and b2 in [0, 1)");
-    GCA_CHECK_ARG(eps >= 0.0f, "adam: eps >= 0");
-    GCA_CHECK_ARG((steps_per_iteration == 0 && num_iterations == 0) || (steps_per_iteration >= 1 && num_iterations >= 1),
-                  "adam: steps_per_iteration and num_iterations both 0 (no annealing) or both >= 1");
-    GCA_CHECK_ARG(workspace_bytes >= adam_workspace_bytes(total), "adam: workspace smaller than gca_adam_step_workspace");
+    int64_t total;
+    if (const int st = gca_check_adam_step(t, state, b1, b2, eps, steps_per_iteration, num_iterations, info_out,
+                                           workspace, workspace_bytes, &total))
+        return st;
     AdamArgs a;
     memset(&a, 0, sizeof(a));
     a.CH = adam_chunk(total);
@@ -243,10 +227,7 @@ __global__ __launch_bounds__(256) void permutation_kernel(uint32_t k0, uint32_t 
 
 extern "C" int gca_permutation(uint64_t seed, uint32_t epoch0, const int32_t* counter, int64_t T, int rows,
                                int32_t* out, void* stream) {
-    GCA_CHECK_ARG(out, "permutation: null out");
-    GCA_CHECK_ARG(T >= 1 && T < (1ll << 31), "permutation: 1 <= T < 2^31");
-    GCA_CHECK_ARG(rows >= 1 && rows <= 65535, "permutation: 1 <= rows <= 65535");
-    GCA_CHECK_ARG((((uintptr_t)out | (uintptr_t)counter) & 3u) == 0, "permutation: out and counter 4-B aligned");
+    if (const int st = gca_check_permutation(counter, T, rows, out)) return st;
     hipLaunchKernelGGL(permutation_kernel, dim3((unsigned)((T + 255) / 256), (unsigned)rows), dim3(256), 0,
                        (hipStream_t)stream, (uint32_t)seed, (uint32_t)(seed >> 32), epoch0, counter, (uint32_t)T,
                        perm_half_bits(T), out);

@@ -208,22 +208,13 @@ __global__ __launch_bounds__(POBS_THREADS) void policy_obs_generic_kernel(
 extern "C" int gca_policy_observation(const uint8_t* buf0, const uint8_t* buf1, const uint8_t* parity,
                                       const int32_t* pos, int E, int H, int W, int empty, int tree, int fire, int radius,
                                       int block, int form, uint8_t* local_out, float* coarse_out, void* stream) {
-    GCA_CHECK_ARG(buf0 && (buf1 || !parity), "policy_observation: buf0 required, and buf1 with parity");
-    GCA_CHECK_ARG(local_out || coarse_out, "policy_observation: local_out or coarse_out required");
-    GCA_CHECK_ARG(pos || !local_out, "policy_observation: local_out needs pos");
-    GCA_CHECK_ARG(E > 0 && H > 0 && W > 0, "policy_observation: E, H, W must be positive");
-    GCA_CHECK_ARG((int64_t)H * W < (1 << 30), "policy_observation: grid too large (H * W < 2^30)");
-    GCA_CHECK_ARG(((empty | tree | fire) & ~0xFF) == 0, "policy_observation: the codes must be u8 values");
-    GCA_CHECK_ARG(radius >= 0 && radius <= 31, "policy_observation: radius in [0, 31]");
-    GCA_CHECK_ARG(block >= 1 && block <= 64 && (block & (block - 1)) == 0,
-                  "policy_observation: block must be a power of two in [1, 64]");
-    GCA_CHECK_ARG(form >= 0 && form <= 2, "policy_observation: form 0 (by shape), 1 (generic) or 2 (rows)");
-    const bool rows_shape = (W == 256 || W == 512) && (block == 8 || block == 16 || block == 32) && H % block == 0;
-    GCA_CHECK_ARG(form != 2 || rows_shape,
-                  "policy_observation: form 2 (rows) needs W = 256 / 512, block = 8 / 16 / 32 and H % block == 0");
+    if (const int st = gca_check_policy_observation(buf0, buf1, parity, pos, E, H, W, empty, tree, fire, radius, block,
+                                                    form, local_out, coarse_out))
+        return st;
+    // the rows kernel's 8-B loads: the host build has one form and takes any alignment
     const bool aligned = (((uintptr_t)buf0 | (parity ? (uintptr_t)buf1 : (uintptr_t)0)) & 7u) == 0;
     GCA_CHECK_ARG(form != 2 || aligned, "policy_observation: form 2 (rows) needs 8-B aligned planes");
-    const bool rows = form != 1 && rows_shape && aligned;
+    const bool rows = form != 1 && gca_policy_obs_rows_shape(H, W, block) && aligned;
     const int Hc = (H + block - 1) / block, Wc = (W + block - 1) / block;
     const int64_t tiles = (int64_t)E * Hc * Wc;
     const int strips = (H + POBS_STRIP - 1) / POBS_STRIP;
@@ -231,7 +222,7 @@ extern "C" int gca_policy_observation(const uint8_t* buf0, const uint8_t* buf1, 
     if (coarse_out)
         coarse_wgs = rows ? ((int64_t)E * strips + POBS_WAVES - 1) / POBS_WAVES : (tiles + POBS_THREADS - 1) / POBS_THREADS;
     const int64_t window_wgs = local_out ? ((int64_t)E + POBS_WAVES - 1) / POBS_WAVES : 0;
-    // the kernels' 32-bit wave / workgroup indices
+    // the kernels' 32-bit wave / workgroup indices: the host build launches nothing
     GCA_CHECK_ARG(coarse_wgs + window_wgs < (1ll << 29), "policy_observation: too many envs for one launch");
     const dim3 grid((unsigned)(coarse_wgs + window_wgs)), wg(POBS_THREADS);
     const float inv = 1.0f / (float)(block * block);

@@ -50,9 +50,7 @@ __global__ __launch_bounds__(PPO_THREADS) void gae_kernel(const double* __restri
 
 extern "C" int gca_gae(const double* reward, const float* value, const float* next_value, const uint8_t* terminal,
                        float gamma, float gamma_lambda, int K, int E, float* advantage, float* returns, void* stream) {
-    GCA_CHECK_ARG(K >= 0, "gae: K >= 0");
-    GCA_CHECK_ARG(E > 0, "gae: E > 0");
-    GCA_CHECK_ARG(reward && value && next_value && advantage && returns, "gae: null argument");
+    if (const int st = gca_check_gae(reward, value, next_value, K, E, advantage, returns)) return st;
     if (K == 0) return GCA_OK;
     hipLaunchKernelGGL(gae_kernel, dim3((unsigned)((E + PPO_THREADS - 1) / PPO_THREADS)), dim3(PPO_THREADS), 0,
                        (hipStream_t)stream, reward, value, next_value, terminal, gamma, gamma_lambda, K, E, advantage,
@@ -521,30 +519,10 @@ __global__ __launch_bounds__(PPO_THREADS) void ppo_reduce_kernel(PpoPlan pl, Ppo
 }
 
 // ------------------------------------------------------------------ host side
-static int ppo_check_policy(const gca_heli_policy* p) {
-    GCA_CHECK_ARG(p && p->w_local && p->w_coarse && p->b1 && p->w_out && p->b2, "helicopter_policy: null weights");
-    GCA_CHECK_ARG(p->radius >= 0 && p->radius <= 31, "helicopter_policy: radius in [0, 31]");
-    GCA_CHECK_ARG(p->block >= 1 && p->block <= 64 && (p->block & (p->block - 1)) == 0,
-                  "helicopter_policy: block must be a power of two in [1, 64]");
-    GCA_CHECK_ARG(p->hidden >= 32 && p->hidden <= 256 && (p->hidden & (p->hidden - 1)) == 0,
-                  "helicopter_policy: hidden must be a power of two in [32, 256]");
-    return GCA_OK;
-}
-
 extern "C" int64_t gca_helicopter_policy_grad_workspace(const gca_heli_policy* p, int C, int N) {
-    if (!p || p->radius < 0 || p->radius > 31 || p->hidden < 32 || p->hidden > 256 || (p->hidden & (p->hidden - 1)) ||
-        C < 2 || C % 2 || C > 15088 || N < 1) {
-        gca_set_error("argument: %s", "helicopter_policy_grad_workspace: radius in [0, 31], hidden a power of two in "
-                                      "[32, 256], C = 2 Hc Wc at most 15088, N >= 1");
-        return -1;
-    }
+    if (gca_check_policy_grad_workspace(p, C, N)) return -1;
     const int S = 2 * p->radius + 1;
     return ppo_plan(S * S, C, p->hidden, N).bytes;
-}
-
-static bool ppo_overlap(const void* a, int64_t na, const void* b, int64_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
 }
 
 template <int HD>
@@ -572,31 +550,12 @@ extern "C" int gca_helicopter_policy_grad(const gca_heli_policy* p, int C, const
                                           float ent_coef, float vf_coef, int norm_adv, float* g_w_local,
                                           float* g_w_coarse, float* g_b1, float* g_w_out, float* g_b2, float* stats,
                                           void* workspace, int64_t workspace_bytes, void* stream) {
-    if (const int st = ppo_check_policy(p)) return st;
-    GCA_CHECK_ARG(local && coarse && action && old_logits && advantage && returns,
-                  "helicopter_policy_grad: null record");
-    GCA_CHECK_ARG(g_w_local && g_w_coarse && g_b1 && g_w_out && g_b2 && stats && workspace,
-                  "helicopter_policy_grad: null output or workspace");
-    GCA_CHECK_ARG(C >= 2 && C % 2 == 0 && C <= 15088, "helicopter_policy_grad: C = 2 Hc Wc, at most 15088");
-    GCA_CHECK_ARG(T >= 1 && T < (1ll << 31), "helicopter_policy_grad: 1 <= T < 2^31");
-    GCA_CHECK_ARG(N >= 1, "helicopter_policy_grad: N >= 1");
-    GCA_CHECK_ARG(idx || N <= T, "helicopter_policy_grad: N <= T without idx");
-    GCA_CHECK_ARG(clip_coef >= 0.0f, "helicopter_policy_grad: clip_coef >= 0");
+    PpoPlan pl;
+    if (const int st = gca_check_policy_grad(p, C, local, coarse, action, old_logits, advantage, returns, T, idx, N,
+                                             clip_coef, g_w_local, g_w_coarse, g_b1, g_w_out, g_b2, stats, workspace,
+                                             workspace_bytes, &pl))
+        return st;
     const int S = 2 * p->radius + 1, SS = S * S, Hd = p->hidden;
-    const PpoPlan pl = ppo_plan(SS, C, Hd, N);
-    GCA_CHECK_ARG(workspace_bytes >= pl.bytes,
-                  "helicopter_policy_grad: workspace smaller than gca_helicopter_policy_grad_workspace");
-    const uintptr_t aligned = (uintptr_t)workspace | (uintptr_t)p->w_local | (uintptr_t)p->w_coarse | (uintptr_t)p->b1;
-    GCA_CHECK_ARG((aligned & 15u) == 0,
-                  "helicopter_policy_grad: workspace, w_local, w_coarse and b1 16-B aligned");
-    const void* ptrs[11] = {g_w_local, g_w_coarse, g_b1, g_w_out, g_b2, stats,
-                            p->w_local, p->w_coarse, p->b1, p->w_out, p->b2};
-    const int64_t sizes[11] = {pl.off_wc * 4, (int64_t)C * Hd * 4, Hd * 4ll, Hd * 40ll, 40, 32,
-                               pl.off_wc * 4, (int64_t)C * Hd * 4, Hd * 4ll, Hd * 40ll, 40};
-    for (int i = 0; i < 6; ++i)
-        for (int j = i + 1; j < 11; ++j)
-            GCA_CHECK_ARG(!ppo_overlap(ptrs[i], sizes[i], ptrs[j], sizes[j]),
-                          "helicopter_policy_grad: the outputs may alias neither each other nor the weights");
     PpoBatch b{local, coarse, action, old_logits, advantage, returns, idx, N, (int)T, SS, C};
     const PpoLossArgs la{clip_coef, ent_coef, vf_coef, 1.0f / (float)N, norm_adv ? 1 : 0};
     const PpoOut out{g_w_local, g_w_coarse, g_b1, g_w_out, g_b2, stats};

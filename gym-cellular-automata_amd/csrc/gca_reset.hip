@@ -80,15 +80,9 @@ extern "C" int gca_bulldozer_reset_where(const gca_bulldozer_params* p, uint64_t
                                          double* accu, uint8_t* parity, uint8_t* buf0, uint8_t* buf1, int H, int W,
                                          int32_t* pos, int32_t* counts, uint8_t* hit, int64_t* steps_elapsed, int E,
                                          void* stream) {
-    GCA_CHECK_ARG(p && cdf && values && done && episode && accu && parity && buf0 && buf1 && pos && counts && hit &&
-                      steps_elapsed,
-                  "bulldozer_reset_where: null argument");
-    GCA_CHECK_ARG(E > 0 && H > 0 && W > 0, "bulldozer_reset_where: E, H, W must be positive");
-    GCA_CHECK_ARG(H < 32768 && W < 32768, "bulldozer_reset_where: H, W < 32768");
-    GCA_CHECK_ARG(buf0 != buf1, "bulldozer_reset_where: buf0 and buf1 must differ");
-    GCA_CHECK_ARG(max_steps >= 0 && set_episode >= -1 && set_episode <= 0xFFFFFFFFll,
-                  "bulldozer_reset_where: max_steps >= 0 and set_episode in [-1, 2^32)");
-    GCA_CHECK_ARG(p->env_offset >= 0, "bulldozer_reset_where: env_offset >= 0");
+    if (const int st = gca_check_bulldozer_reset_where(p, max_steps, set_episode, cdf, values, done, episode, accu,
+                                                       parity, buf0, buf1, H, W, pos, counts, hit, steps_elapsed, E))
+        return st;
     // a workgroup per env, a thread per quad of cells up to 1024 (whole waves); larger grids loop
     const int64_t quads = ((int64_t)H * W + 3) / 4;
     const int threads = (int)min((int64_t)RESET_MAX_THREADS, (quads + 63) / 64 * 64);

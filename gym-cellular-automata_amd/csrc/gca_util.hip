@@ -29,7 +29,7 @@ __global__ void philox_kernel(const uint32_t* __restrict__ ctr, uint32_t k0, uin
 }
 
 extern "C" int gca_philox(const uint32_t* ctr, uint32_t key0, uint32_t key1, uint32_t* out, int64_t n, void* stream) {
-    GCA_CHECK_ARG(ctr && out && n >= 0, "ctr/out required");
+    if (const int st = gca_check_philox(ctr, out, n)) return st;
     if (n == 0) return GCA_OK;
     hipLaunchKernelGGL(philox_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ctr, key0,
                        key1, out, n);
@@ -81,8 +81,9 @@ __global__ __launch_bounds__(256) void count_kernel(const uint8_t* __restrict__ 
 
 extern "C" int gca_count_cells(const uint8_t* grid, int E, int H, int W, int v0, int v1, int v2, int32_t* counts,
                                void* stream) {
-    GCA_CHECK_ARG(grid && counts && E > 0 && H > 0 && W > 0, "grid/counts and positive sizes required");
+    if (const int st = gca_check_count_cells(grid, E, H, W, counts)) return st;
     hipStream_t st = (hipStream_t)stream;
+    // the device build alone zeroes the counts with a call that can fail
     if (hipMemsetAsync(counts, 0, sizeof(int32_t) * 3 * (size_t)E, st) != hipSuccess) {
         gca_set_error("count_cells: memset failed");
         return GCA_ERR_HIP;
