@@ -179,6 +179,39 @@ static inline int gca_check_policy_rollout(int empty, int tree, int fire, int ma
     return gca_check_policy(p);
 }
 
+// ----------------------------------------------------------------- the bulldozer policy
+// Every refusal names its argument. The dims are the helicopter policy's; the act kernel's LDS gives the same C limit.
+static inline int gca_check_bdz_policy(const char* who, const gca_bulldozer_policy* p) {
+    if (!p) return gca_refuse(who, "policy is null");
+    if (!p->w_local) return gca_refuse(who, "policy.w_local is null");
+    if (!p->w_coarse) return gca_refuse(who, "policy.w_coarse is null");
+    if (!p->b1) return gca_refuse(who, "policy.b1 is null");
+    if (!p->w_out) return gca_refuse(who, "policy.w_out is null");
+    if (!p->b2) return gca_refuse(who, "policy.b2 is null");
+    if (!(p->radius >= 0 && p->radius <= 31)) return gca_refuse(who, "policy.radius in [0, 31]");
+    if (!(p->block >= 1 && p->block <= 64 && (p->block & (p->block - 1)) == 0))
+        return gca_refuse(who, "policy.block must be a power of two in [1, 64]");
+    if (!(p->hidden >= 32 && p->hidden <= 256 && (p->hidden & (p->hidden - 1)) == 0))
+        return gca_refuse(who, "policy.hidden must be a power of two in [32, 256]");
+    return GCA_OK;
+}
+
+static inline bool gca_bdz_policy_weights_aligned(const gca_bulldozer_policy* p) {
+    return (((uintptr_t)p->w_local | (uintptr_t)p->w_coarse) & 15u) == 0;
+}
+
+static inline int gca_check_bdz_policy_act(const gca_bulldozer_policy* p, int C, const void* local, const void* coarse,
+                                           const void* steps_elapsed, const void* action, int E) {
+    const char* who = "bulldozer_policy_act";
+    if (const int st = gca_check_bdz_policy(who, p)) return st;
+    if (!local) return gca_refuse(who, "local is null");
+    if (!coarse) return gca_refuse(who, "coarse is null");
+    if (!steps_elapsed) return gca_refuse(who, "steps_elapsed is null");
+    if (!action) return gca_refuse(who, "action is null");
+    if (!(E > 0)) return gca_refuse(who, "E > 0");
+    return gca_check_policy_c(who, C);
+}
+
 // ----------------------------------------------------------------- the PPO update
 static inline int gca_check_gae(const void* reward, const void* value, const void* next_value, int K, int E,
                                 const void* advantage, const void* returns) {

@@ -18,6 +18,8 @@
 //   gca_policy_observation  the batched envs' policy observation (gca_policy_obs.hip), pinned by tests/_policy_obs_ref.py
 //   gca_helicopter_policy_act / gca_helicopter_policy_rollout  the policy network and the closed-loop rollout
 //                     (gca_heli.hip, gca_heli_policy_dev.h), in gca.h's summation order
+//   gca_bulldozer_policy_act  the bulldozer policy network alone (gca_bdz_policy_dev.h), in gca.h's summation order;
+//                     gca_bulldozer_policy_rollout needs the Windy CA and is in the device build only
 //   gca_gae / gca_helicopter_policy_grad(_workspace)  the PPO update (gca_ppo.hip): the GAE recurrence bit for bit, the
 //                     loss gradient in double as a second yardstick
 //   gca_adam_step(_workspace) / gca_permutation  the optimizer and the minibatch shuffle (gca_opt.hip), bit for bit
@@ -583,6 +585,83 @@ extern "C" int gca_helicopter_policy_rollout(int empty, int tree, int fire, int 
         helicopter_step_host(empty, tree, fire, max_freeze, seed, env_offset, act_k, 0, nullptr, thresholds, freeze,
                              rng_step, parity, buf0, buf1, H, W, pos, counts, hit, reward, steps_elapsed, E,
                              reward_out ? reward_out + o : nullptr, hit_out ? hit_out + o : nullptr);
+    }
+    return GCA_OK;
+}
+
+// ---------------------------------------------------------------- the bulldozer policy (gca.h "bulldozer policy")
+// One env's twelve outputs and its (move, shoot) in gca.h's order: the helicopter network with 12 outputs, two heads.
+static void bdz_policy_eval_host(const gca_bulldozer_policy* p, int C, const uint8_t* loc, const float* coarse,
+                                 uint32_t step, uint32_t env_id, uint32_t ep, uint64_t policy_seed, int greedy,
+                                 float* out, int32_t* act) {
+    const int S = 2 * p->radius + 1, SS = S * S, N = SS + C, Hd = p->hidden, G = 1024 / Hd;
+    float h[256];
+    for (int j = 0; j < Hd; ++j) {
+        float hj = p->b1[j];
+        for (int g = 0; g < G; ++g) {
+            float acc = 0.0f;
+            for (int n = g; n < N; n += G) {
+                if (n < SS) acc = acc + p->w_local[((size_t)n * 4 + (loc[n] & 3)) * Hd + j];
+                else acc = acc + p->w_coarse[(size_t)(n - SS) * Hd + j] * coarse[n - SS];
+            }
+            hj = hj + acc;
+        }
+        h[j] = hj > 0.0f ? hj : 0.0f;
+    }
+    for (int o = 0; o < 12; ++o) {
+        float q[16];
+        for (int r = 0; r < 16; ++r) {
+            float acc = 0.0f;
+            for (int j = r; j < Hd; j += 16) acc = acc + p->w_out[j * 12 + o] * h[j];
+            q[r] = acc;
+        }
+        for (int half = 8; half >= 1; half >>= 1)
+            for (int r = 0; r < half; ++r) q[r] = q[r] + q[r + half];
+        out[o] = p->b2[o] + q[0];
+    }
+    float m = out[0];
+    int32_t first = 0;
+    for (int i = 1; i < 9; ++i)
+        if (out[i] > m) {
+            m = out[i];
+            first = i;
+        }
+    const float s0 = out[9], s1 = out[10];
+    if (greedy) {
+        act[0] = first;
+        act[1] = s1 > s0 ? 1 : 0;
+        return;
+    }
+    float c[9], s = 0.0f;
+    for (int i = 0; i < 9; ++i) {
+        s = s + exp_f32_host(out[i] - m);
+        c[i] = s;
+    }
+    const u32x4 x = philox4x32_10(u32x4{step, env_id, ep, GCA_TAG_BPOLICY}, (uint32_t)policy_seed,
+                                  (uint32_t)(policy_seed >> 32));
+    const float t = ((float)(x.x >> 8) * 0x1.0p-24f) * c[8];
+    int32_t mv = 8;
+    for (int i = 7; i >= 0; --i)
+        if (t < c[i]) mv = i;
+    act[0] = mv;
+    const float ms = s1 > s0 ? s1 : s0;
+    const float c0 = exp_f32_host(s0 - ms), c1 = c0 + exp_f32_host(s1 - ms);
+    act[1] = ((float)(x.y >> 8) * 0x1.0p-24f) * c1 < c0 ? 0 : 1;
+}
+
+extern "C" int gca_bulldozer_policy_act(const gca_bulldozer_policy* p, int C, const uint8_t* local, const float* coarse,
+                                        const int64_t* steps_elapsed, const uint32_t* episode, int env_offset,
+                                        uint64_t policy_seed, int greedy, int32_t* action, float* logits, float* value,
+                                        int E, void*) {
+    if (const int st = gca_check_bdz_policy_act(p, C, local, coarse, steps_elapsed, action, E)) return st;
+    const size_t SS = (size_t)(2 * p->radius + 1) * (2 * p->radius + 1);
+    for (int e = 0; e < E; ++e) {
+        float out[12];
+        bdz_policy_eval_host(p, C, local + e * SS, coarse + (size_t)e * C, (uint32_t)steps_elapsed[e],
+                             (uint32_t)(env_offset + e), episode ? episode[e] : 0u, policy_seed, greedy, out,
+                             action + 2 * (size_t)e);
+        if (logits) memcpy(logits + (size_t)e * 11, out, 11 * sizeof(float));
+        if (value) value[e] = out[11];
     }
     return GCA_OK;
 }

@@ -16,11 +16,10 @@
 //   generic  any H, W, block: a thread per tile with byte loads (the helicopter's 42 x 42).
 // Device pointers only, no allocation, no memset, no atomics, no LDS, no host synchronisation: capturable.
 #include "gca_common.h"
+#include "gca_policy_obs_dev.h"  // the rows form's strip of one wave, shared with the bulldozer policy rollout
 
 #define POBS_THREADS 256
 #define POBS_WAVES (POBS_THREADS / GCA_WAVE)
-constexpr int POBS_STRIP = 32;  // rows of one wave of the rows form: the largest block, so a strip is whole block-rows
-constexpr int POBS_RD = 8;      // rows per group of loads (the smallest block: every block-row is whole groups)
 
 // ------------------------------------------------------------------ the window part (both kernels)
 // One wave per env, lane j the window's column j (S <= 63), its S rows in groups of POBS_WIN with the group's loads in
@@ -72,38 +71,8 @@ __device__ __forceinline__ void policy_window_group(const uint8_t* __restrict__ 
 }
 
 // ------------------------------------------------------------------ rows form (W = 256 NW, NW = 1, 2)
-template <int NW>
-struct ObsRow {
-    uint32_t w[NW];
-};
-
-// S: the env's wave-uniform base, lofs: the lane's column offset, R wave-uniform and inside the grid (the caller's loop
-// bounds): one global_load_dword / dwordx2 with a scalar base
-template <int NW>
-__device__ __forceinline__ ObsRow<NW> load_obsrow(const uint8_t* __restrict__ S, uint32_t lofs, int R) {
-    constexpr int W = 256 * NW;
-    const uint8_t* p = S + (uint32_t)R * (uint32_t)W + lofs;
-    ObsRow<NW> x;
-    if (NW == 1) {
-        x.w[0] = *reinterpret_cast<const uint32_t*>(p);
-    } else {
-        const uint2 v = *reinterpret_cast<const uint2*>(p);
-        x.w[0] = v.x; x.w[1 % NW] = v.y;
-    }
-    return x;
-}
-
-template <int CTRL>
-__device__ __forceinline__ uint32_t obs_dpp(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, true);
-}
-
-// A wave takes a strip of POBS_STRIP rows of one env = 32 / B block-rows (H % B == 0, so every block-row is whole and
-// inside the grid). Per block-row: TREE and FIRE flags as 0x01 bytes by SWAR equality (bytes_eq01), added per byte over
-// its B rows (<= 32 per byte); then the lane's bytes summed by v_sad_u8 against 0, TREE in the low half and FIRE in the
-// high half of one dword (<= 1024 each), and the G = B / (4 NW) lanes of a tile added by DPP (quad_perm xor 1, xor 2,
-// row_half_mirror: every lane of the group ends with the tile's sum; G = 1, W = 512 with B = 8, needs none). The
-// group's first lane stores the two f32.
+// A wave takes a strip of POBS_STRIP rows of one env (policy_obs_rows_strip, gca_policy_obs_dev.h); the first lane of
+// every tile stores the tile's two f32.
 template <int NW>
 __global__ __launch_bounds__(POBS_THREADS) void policy_obs_rows_kernel(
     const uint8_t* __restrict__ buf0, const uint8_t* __restrict__ buf1, const uint8_t* __restrict__ parity,
@@ -120,58 +89,14 @@ __global__ __launch_bounds__(POBS_THREADS) void policy_obs_rows_kernel(
     const int env = unit / strips;
     if (env >= E) return;
     const int strip = unit - env * strips;
-    const int B = 1 << lgB;
-    const int lgG = lgB - (NW == 1 ? 2 : 3);  // lanes per tile: G = B / (4 NW) = 1, 2, 4, 8
     const int Hc = H >> lgB, Wc = W >> lgB;
     const uint8_t* __restrict__ S = ((parity && parity[env]) ? buf1 : buf0) + (int64_t)env * H * W;
     float* __restrict__ C = coarse_out + (int64_t)env * 2 * Hc * Wc;
-    const uint32_t lofs = 4 * NW * (uint32_t)lane;
-    const uint32_t Tp = rep4(tree), Fp = rep4(fire);
-    const int row_end = min(H, strip * POBS_STRIP + POBS_STRIP);
-    uint32_t aT[NW], aF[NW];
-#pragma unroll
-    for (int j = 0; j < NW; ++j) aT[j] = aF[j] = 0u;
-    // the strip's rows in groups of POBS_RD, unrolled over the strip's four groups with two register sets: the next
-    // group's loads are issued before the current group is classified (two groups in flight, across block-row boundaries
-    // too); a block-row ends where (r + POBS_RD) % B == 0
-    ObsRow<NW> x[2][POBS_RD];
-    const int base = strip * POBS_STRIP;
-#pragma unroll
-    for (int k = 0; k < POBS_RD; ++k) x[0][k] = load_obsrow<NW>(S, lofs, base + k);
-#pragma unroll
-    for (int g = 0; g < POBS_STRIP / POBS_RD; ++g) {
-        const int r = base + g * POBS_RD;
-        if (r >= row_end) break;  // wave-uniform: a strip cut short by the grid's last row
-        if (g + 1 < POBS_STRIP / POBS_RD && r + POBS_RD < row_end) {
-#pragma unroll
-            for (int k = 0; k < POBS_RD; ++k) x[(g + 1) & 1][k] = load_obsrow<NW>(S, lofs, r + POBS_RD + k);
-        }
-#pragma unroll
-        for (int k = 0; k < POBS_RD; ++k) {
-#pragma unroll
-            for (int j = 0; j < NW; ++j) {
-                aT[j] += bytes_eq01(x[g & 1][k].w[j], Tp);
-                aF[j] += bytes_eq01(x[g & 1][k].w[j], Fp);
-            }
-        }
-        if (((r + POBS_RD) & (B - 1)) != 0) continue;
-        uint32_t sT = 0u, sF = 0u;
-#pragma unroll
-        for (int j = 0; j < NW; ++j) {
-            sT = __builtin_amdgcn_sad_u8(aT[j], 0u, sT);
-            sF = __builtin_amdgcn_sad_u8(aF[j], 0u, sF);
-            aT[j] = aF[j] = 0u;
-        }
-        uint32_t s = sT | (sF << 16);
-        if (lgG >= 1) s += obs_dpp<0xB1>(s);   // quad_perm [1, 0, 3, 2]
-        if (lgG >= 2) s += obs_dpp<0x4E>(s);   // quad_perm [2, 3, 0, 1]
-        if (lgG >= 3) s += obs_dpp<0x141>(s);  // row_half_mirror: the other quad of the lane's eight
-        if ((lane & ((1 << lgG) - 1)) == 0) {
-            const int o = (r >> lgB) * Wc + (lane >> lgG);
-            C[o] = (float)(s & 0xFFFFu) * inv;
-            C[Hc * Wc + o] = (float)(s >> 16) * inv;
-        }
-    }
+    policy_obs_rows_strip<NW>(S, 4 * NW * (uint32_t)lane, lane, strip, H, lgB, rep4(tree), rep4(fire),
+                              [&](int o, uint32_t nT, uint32_t nF) {
+                                  C[o] = (float)nT * inv;
+                                  C[Hc * Wc + o] = (float)nF * inv;
+                              });
 }
 
 // ------------------------------------------------------------------ generic form (any H, W, block)

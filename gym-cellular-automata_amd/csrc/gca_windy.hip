@@ -20,6 +20,8 @@
 //    Reward/done counts of the new grid are fused (wave reduction + 3 atomics).
 #include "gca_common.h"
 #include "gca_reset_dev.h"  // the in-launch reset of the rollout kernel, wave_sum3
+#include "gca_bdz_policy_dev.h"  // the bulldozer policy network (the act kernel and the policy rollout)
+#include "gca_policy_obs_dev.h"  // the coarse map's rows-form strip (the policy rollout's recount)
 
 // windy_fast_kernel: row chunks in flight ahead of the one being computed (r01o: 2 / 4 / 8 measured slower than 1)
 constexpr int WINDY_AHEAD = 1;
@@ -1285,4 +1287,503 @@ extern "C" int gca_bulldozer_rollout(const gca_bulldozer_params* p, const int32_
     return bulldozer_rollout_impl(who, true, autoreset, p, action_seed, K, action_out, reward_out, terminated_out, ext,
                                   accu, steps, done, wind, wind_stride, rng_step, parity, buf0, buf1, H, W, pos, counts,
                                   hit, reward, steps_elapsed, E, stream);
+}
+
+// ------------------------------------------------------------------ the bulldozer policy (gca.h "bulldozer policy")
+// gca_bulldozer_policy_act: the network alone, one 256-thread workgroup per env on the observation the caller hands over.
+// A class above 3 (never written by gca_policy_observation) is taken modulo 4, so no weight row outside w_local is read.
+__global__ __launch_bounds__(BPOL_VT) void bulldozer_policy_act_kernel(
+    BdzPolicyW w, const uint8_t* __restrict__ local, const float* __restrict__ coarse,
+    const int64_t* __restrict__ steps_elapsed, const uint32_t* __restrict__ episode, int env_offset,
+    int32_t* __restrict__ action, float* __restrict__ logits, float* __restrict__ value) {
+    extern __shared__ __attribute__((aligned(16))) float bpol_lds[];
+    const int e = blockIdx.x, tid = threadIdx.x;
+    float* cs = bpol_lds;
+    float* part = cs + ((w.C + 3) & ~3);
+    float* hs = part + BPOL_PART;
+    float* outs = hs + BPOL_VT;
+    for (int c = tid; c < w.C; c += BPOL_VT) cs[c] = coarse[(size_t)e * (size_t)w.C + c];
+    const uint8_t* __restrict__ loc = local + (size_t)e * (size_t)w.SS;
+    int32_t move, shoot;
+    bdz_policy_eval(
+        w, cs, part, hs, outs, tid, BPOL_VT, (uint32_t)steps_elapsed[e], (uint32_t)(env_offset + e),
+        episode ? episode[e] : 0u, logits ? logits + (size_t)e * 11 : nullptr, value ? value + e : nullptr,
+        [&](int n, int, int) -> uint32_t { return (uint32_t)loc[n] & 3u; }, [] {}, move, shoot);
+    if (tid == 0) {
+        action[2 * (size_t)e] = move;
+        action[2 * (size_t)e + 1] = shoot;
+    }
+}
+
+// gca_bulldozer_policy_rollout's resident form: bulldozer_rollout_random_kernel's march (the env's state in registers,
+// a wave per strip of the grid, the Windy CA by every wave when a step takes a pass, Move / Modify by thread 0, the
+// in-launch reset) with the agent inside: every step the workgroup evaluates the policy network on that step's
+// observation (gca_bdz_policy_dev.h) and takes the sampled (move, shoot). Its own kernel, so the existing rollout
+// instantiations compile to what they were. Autoreset is a run-time, workgroup-uniform branch here (three instantiations
+// per width instead of six).
+//
+// The observation. The window is read from the env's current plane in global memory around the position before the
+// move (class 3 outside the grid, policy_window_wave's unsigned tests). The coarse map lives in LDS (cs) for the whole
+// launch. INVARIANT: at barrier A of every step, cs equals gca_policy_observation's coarse map of the current plane. It
+// is established by a recount (policy_obs_rows_strip, the observation kernel's own strip code, a wave per 32 rows) on
+// entry, in the step after a CA pass and in the step after an in-launch reset -- `recount`, workgroup-uniform since every
+// thread carries the env's state -- and kept in between by thread 0, whose Modify adjusts the one block it changed by
+// -+ 1 / block^2. Every value is a multiple of 1 / block^2 = 2^-(2 lg block) that is at most 1: the adjustment is exact
+// and equals a recount.
+//
+// Which barrier orders what (all of them outside every non-uniform condition: K, `recount`, n > 0 and "resets" are
+// workgroup-uniform, "is thread 0" never guards a barrier):
+//   R  (only in a recounting step, before the recount) thread 0's Modify byte of the step before, written after the CA
+//      pass's closing barrier (SOLO has none after Modify), before other waves count that row. The CA pass's and the
+//      refill's own stores are already behind their closing barriers.
+//   A  (the evaluation's first) the recount's LDS stores of every wave; thread 0's Modify byte in global memory and its
+//      adjustment of cs from the step before (a SOLO step without a CA pass has no other barrier) -- before every wave's
+//      window gather and partial sums. The gather also reads cells other waves wrote in a CA pass or a refill: those are
+//      behind that pass's / refill's closing barrier, which precedes A.
+//   B  the end of this step's reads of cs and of the window: thread 0's Modify (after D) cannot touch what a slower
+//      wave still reads. The records of the observation (local_out, coarse_out) are stored between A and B for the same
+//      reason.
+//   C, D  the network's (gca_bdz_policy_dev.h, with the reuse argument for part / hs / outs).
+// wave_cnt and bc are double-buffered exactly as in bulldozer_rollout_random_kernel; the barriers added here only
+// tighten that argument.
+struct BdzPolArgs {
+    BdzPolicyW w;
+    int radius, lgB, HcWc, Wc;
+    float inv;  // 1 / block^2
+    int autoreset;
+    float* logits_out;   // (K, E, 11) or NULL
+    float* value_out;    // (K, E) or NULL
+    uint8_t* local_out;  // (K, E, S, S) or NULL
+    float* coarse_out;   // (K, E, C) or NULL
+};
+template <int NW, bool STD, bool SOLO>
+__global__ __launch_bounds__(1024) void bulldozer_policy_rollout_kernel(
+    gca_bulldozer_params p, int K, int32_t* __restrict__ action_out, double* __restrict__ reward_out,
+    uint8_t* __restrict__ done_out, double* __restrict__ accu, int32_t* __restrict__ steps, uint8_t* __restrict__ done,
+    const double* __restrict__ wind, int64_t wind_stride, uint32_t* __restrict__ rng_step, uint8_t* __restrict__ parity,
+    uint8_t* buf0, uint8_t* buf1, int H, int32_t* __restrict__ pos, int32_t* __restrict__ counts,
+    uint8_t* __restrict__ hit, double* __restrict__ reward, int64_t* __restrict__ steps_elapsed, int E, RolloutExt ext,
+    BdzPolArgs q) {
+    constexpr int W = 256 * NW;
+    extern __shared__ __attribute__((aligned(16))) float bpol_lds[];
+    __shared__ int32_t wave_cnt[2][16][3];
+    __shared__ int32_t bc[2][4];
+    float* cs = bpol_lds;
+    float* part = cs + ((q.w.C + 3) & ~3);
+    float* hs = part + BPOL_PART;
+    float* outs = hs + BPOL_VT;
+    const int e = blockIdx.x;
+    const int tid = threadIdx.x, nt = (int)blockDim.x;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, nw = nt >> 6;
+    const uint32_t env_id = (uint32_t)(p.env_offset + e);
+    const bool RESET = q.autoreset != 0;
+    bool was_done = done[e] != 0;
+    uint32_t rs = rng_step[e];
+    double acc = accu[e];
+    bool odd = parity[e] != 0;
+    int32_t row = pos[2 * e], col = pos[2 * e + 1];
+    int32_t cE = counts[3 * e + 0], cT = counts[3 * e + 1], cF = counts[3 * e + 2];
+    int64_t se = steps_elapsed[e];
+    uint8_t h = hit[e];
+    double rew = reward[e];
+    uint32_t ep = ext.episode ? ext.episode[e] : 0u;
+    int last_n = 0, ca = 0;
+    double wl[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) wl[k] = wind[(int64_t)e * wind_stride + k];
+    const int64_t HW = (int64_t)H * W;
+    const uint32_t lofs = 4 * NW * (uint32_t)lane;
+    const uint32_t Tp = rep4((uint32_t)p.tree), Fp = rep4((uint32_t)p.fire);
+    const int obs_strips = (H + POBS_STRIP - 1) / POBS_STRIP;
+    const size_t SS = (size_t)q.w.SS, C = (size_t)q.w.C;
+    bool term = false, trunc_f = false;
+    bool recount = true;
+    if (!RESET && ext.truncated_out)
+        for (int k = tid; k < K; k += nt) ext.truncated_out[(size_t)k * E + e] = 0;
+    for (int k = 0; k < K; ++k) {
+        const size_t ke = (size_t)k * E + e;
+        uint8_t* grid = (odd ? buf1 : buf0) + e * HW;
+        if (recount) {  // workgroup-uniform
+            __syncthreads();  // R
+            for (int s = wave; s < obs_strips; s += nw)
+                policy_obs_rows_strip<NW>(grid, lofs, lane, s, H, q.lgB, Tp, Fp, [&](int o, uint32_t nT, uint32_t nF) {
+                    cs[o] = (float)nT * q.inv;
+                    cs[q.HcWc + o] = (float)nF * q.inv;
+                });
+            recount = false;
+        }
+        // ---- the agent: this step's observation, the network, the draw
+        const uint32_t wr0 = (uint32_t)row - (uint32_t)q.radius, wc0 = (uint32_t)col - (uint32_t)q.radius;
+        auto class_at = [&](int, int i, int j) -> uint32_t {
+            const uint32_t r = wr0 + (uint32_t)i, c = wc0 + (uint32_t)j;
+            const bool in = r < (uint32_t)H && c < (uint32_t)W;
+            const uint32_t v = grid[in ? r * (uint32_t)W + c : 0u];  // < H * W < 2^30
+            return !in ? 3u : (v == (uint32_t)p.tree ? 1u : (v == (uint32_t)p.fire ? 2u : 0u));
+        };
+        auto record = [&]() {
+            if (q.local_out) {
+                uint8_t* lo = q.local_out + ke * SS;
+                const int S = q.w.S;
+                for (int n = tid; n < (int)SS; n += nt) {
+                    const int i = n / S;
+                    lo[n] = (uint8_t)class_at(n, i, n - i * S);
+                }
+            }
+            if (q.coarse_out) {
+                float* co = q.coarse_out + ke * C;
+                for (int c = tid; c < (int)C; c += nt) co[c] = cs[c];
+            }
+        };
+        int32_t act0, act1;
+        bdz_policy_eval(q.w, cs, part, hs, outs, tid, nt, (uint32_t)se, env_id, ep,
+                        q.logits_out ? q.logits_out + ke * 11 : nullptr, q.value_out ? q.value_out + ke : nullptr,
+                        class_at, record, act0, act1);
+        // every thread sampled the same pair: as wave-uniform values they index t_move / t_shoot by scalar loads, as
+        // the caller's actions do in bulldozer_rollout_random_kernel
+        act0 = __builtin_amdgcn_readfirstlane(act0);
+        act1 = __builtin_amdgcn_readfirstlane(act1);
+        if (action_out && tid == 0) {
+            action_out[2 * ke] = act0;
+            action_out[2 * ke + 1] = act1;
+        }
+        // ---- the env step, as bulldozer_rollout_random_kernel takes it
+        const int a0 = clampi_dev(act0, 0, 8), a1s = clampi_dev(act1, 0, 1);
+        const double x = acc + ((p.t_move[a0] + p.t_shoot[a1s]) + p.t_any);
+        const double reps = trunc(x);
+        const int n = was_done ? -1 : (int)reps;
+        last_n = n;
+        if (n < 0) {  // finished: a graceful no-op step, nothing but the reward changes
+            rew = 0.0;
+            if (tid == 0) {
+                if (reward_out) reward_out[ke] = 0.0;
+                if (!RESET && done_out) done_out[ke] = 1;
+            }
+            if (!RESET) continue;
+        }
+        if (n >= 0) {
+            int nrow = row, ncol = col;
+            move_pos(a0, nrow, ncol, H, W, p.up_mask, p.down_mask, p.left_mask, p.right_mask);
+            if (n > 0) {
+                if constexpr (SOLO) __syncthreads();  // thread 0's Modify writes since the last barrier, before the CA reads
+                auto get_mask = [&]() -> uint32_t { return wave_windy_mask(p, wl, e, rs, lane); };
+                const uint8_t* S = grid;
+                uint8_t* Dst = (odd ? buf0 : buf1) + e * HW;
+                int32_t cntT = 0, cntF = 0, cntV = 0;
+                for (int s0 = wave * FUSED_SH<NW>; s0 < H; s0 += nw * FUSED_SH<NW>)
+                    windy_rows_strip_f<NW, FUSED_SH<NW>, FUSED_RD<NW>, STD>(S, Dst, s0, H, get_mask, lofs, rep4(p.empty),
+                                                                           rep4(p.tree), rep4(p.fire), cntT, cntF, cntV);
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) {
+                    cntT += __shfl_xor(cntT, off);
+                    cntF += __shfl_xor(cntF, off);
+                    cntV += __shfl_xor(cntV, off);
+                }
+                int32_t (*WC)[3] = wave_cnt[ca & 1];
+                ++ca;
+                if (lane == 0) {
+                    WC[wave][0] = cntV - cntT - cntF;
+                    WC[wave][1] = cntT;
+                    WC[wave][2] = cntF;
+                }
+                __syncthreads();  // the new grid (every wave's stores) and the counts are complete
+                grid = Dst;
+                odd = !odd;
+                cE = cT = cF = 0;
+                for (int w = 0; w < nw; ++w) {
+                    cE += WC[w][0];
+                    cT += WC[w][1];
+                    cF += WC[w][2];
+                }
+                recount = true;  // the next step counts the new plane (after thread 0's Modify below: barrier R)
+            }
+            acc = x - reps;
+            row = nrow;
+            col = ncol;
+            // MoveModify: Modify at the new position, on the post-CA grid; thread 0 also keeps the coarse map
+            auto modify = [&](int32_t& mE, int32_t& mT, int32_t& mF) -> uint8_t {
+                uint8_t hh = 0;
+                if (act1 && row >= 0 && row < H && col >= 0 && col < W) {
+                    const int v = grid[(int64_t)row * W + col];
+                    const int nv = p.effect[v];
+                    if (nv >= 0) {
+                        grid[(int64_t)row * W + col] = (uint8_t)nv;
+                        hh = 1;
+                        const int c_old = cell_category(v, p.empty, p.tree, p.fire);
+                        const int c_new = cell_category(nv, p.empty, p.tree, p.fire);
+                        // (as sums of compares: the chain of branches of the other kernels made the compiler index the
+                        // three counts in scratch memory)
+                        mE += (c_new == 0) - (c_old == 0);
+                        mT += (c_new == 1) - (c_old == 1);
+                        mF += (c_new == 2) - (c_old == 2);
+                        // every other thread is past barrier B of this step: nobody reads cs before the next A
+                        const int o = (row >> q.lgB) * q.Wc + (col >> q.lgB);
+                        if (c_old == 1) cs[o] = cs[o] - q.inv; else if (c_old == 2) cs[q.HcWc + o] = cs[q.HcWc + o] - q.inv;
+                        if (c_new == 1) cs[o] = cs[o] + q.inv; else if (c_new == 2) cs[q.HcWc + o] = cs[q.HcWc + o] + q.inv;
+                    }
+                }
+                return hh;
+            };
+            if constexpr (SOLO) {
+                if (tid == 0) h = modify(cE, cT, cF);
+            } else {
+                int32_t* B = bc[k & 1];
+                if (tid == 0) {
+                    const uint8_t hh = modify(cE, cT, cF);
+                    B[0] = cE;
+                    B[1] = cT;
+                    B[2] = cF;
+                    B[3] = hh;
+                }
+                __syncthreads();  // the Modify write and its counts, for every wave's next step
+                cE = B[0];
+                cT = B[1];
+                cF = B[2];
+                h = (uint8_t)B[3];
+            }
+            rew = bdz_reward(cT, cF);
+            was_done = cF == 0;
+            rs += (uint32_t)n;
+            se += 1;
+            if (tid == 0) {
+                if (reward_out) reward_out[ke] = rew;
+                if (!RESET && done_out) done_out[ke] = was_done ? 1 : 0;
+            }
+        }
+        if (RESET) {
+            // gca_bulldozer_reset_where(mask = NULL, set_episode = -1) after this step: the flags it saw, for every env
+            const bool by_limit = ext.max_steps > 0 && se >= ext.max_steps;
+            term = was_done;
+            trunc_f = by_limit && !was_done;
+            if (tid == 0) {
+                if (done_out) done_out[ke] = term ? 1 : 0;
+                if (ext.truncated_out) ext.truncated_out[ke] = trunc_f ? 1 : 0;
+            }
+            if (was_done || by_limit) {  // workgroup-uniform
+                const ResetDist dist = reset_dist(ext.cdf, ext.values);
+                ep += 1u;
+                const int64_t fire_cell = reset_fire_cell(ext.reset_seed, (uint64_t)env_id, ep, H, W);
+                // thread 0's Modify write since the last barrier must land before another wave's refill of the same byte
+                if constexpr (SOLO) __syncthreads();
+                int32_t rE = 0, rT = 0, rF = 0;
+                reset_fill_grid<true>(buf0 + e * HW, HW, tid, nt, ext.reset_seed, (uint64_t)env_id, ep, dist, fire_cell,
+                                      (uint32_t)p.empty, (uint32_t)p.tree, (uint32_t)p.fire, rE, rT, rF);
+                wave_sum3(rE, rT, rF);
+                int32_t (*WC)[3] = wave_cnt[ca & 1];
+                ++ca;
+                if (lane == 0) {
+                    WC[wave][0] = rE;
+                    WC[wave][1] = rT;
+                    WC[wave][2] = rF;
+                }
+                __syncthreads();  // the new grid (every wave's stores) and the counts are complete
+                cE = cT = cF = 0;
+                for (int w = 0; w < nw; ++w) {
+                    cE += WC[w][0];
+                    cT += WC[w][1];
+                    cF += WC[w][2];
+                }
+                reset_position(ext.reset_seed, (uint64_t)env_id, ep, H, W, row, col);
+                if (tid == 0) {
+                    if (ext.last_length) ext.last_length[e] = se;
+                    ext.episode[e] = ep;
+                }
+                odd = false;
+                acc = 0.0;
+                was_done = false;
+                h = 0;
+                se = 0;
+                recount = true;  // the next step counts the new episode's plane
+            }
+        }
+    }
+    if (tid != 0 || K == 0) return;
+    if (RESET) {
+        if (ext.terminated) ext.terminated[e] = term ? 1 : 0;
+        if (ext.truncated) ext.truncated[e] = trunc_f ? 1 : 0;
+    }
+    steps[e] = last_n;
+    reward[e] = rew;
+    accu[e] = acc;
+    parity[e] = odd ? 1 : 0;
+    pos[2 * e] = row;
+    pos[2 * e + 1] = col;
+    counts[3 * e + 0] = cE;
+    counts[3 * e + 1] = cT;
+    counts[3 * e + 2] = cF;
+    hit[e] = h;
+    done[e] = was_done ? 1 : 0;
+    rng_step[e] = rs;
+    steps_elapsed[e] = se;
+}
+
+// The launch path's record rows of one step (a thread per env), after the step and its reset: the reward, and the
+// flags as gca_bulldozer_rollout records them -- under autoreset what the reset launch saw (it wrote them to flag_t /
+// flag_u: the record rows themselves, or the caller's (E) arrays, from which the rows are then copied), otherwise `done`
+// and zeros.
+__global__ __launch_bounds__(256) void bulldozer_policy_record_kernel(
+    int E, int autoreset, const double* __restrict__ reward, const uint8_t* __restrict__ done,
+    const uint8_t* __restrict__ flag_t, const uint8_t* __restrict__ flag_u, double* __restrict__ reward_row,
+    uint8_t* __restrict__ term_row, uint8_t* __restrict__ trunc_row) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E) return;
+    if (reward_row) reward_row[e] = reward[e];
+    if (autoreset) {
+        if (term_row && flag_t != term_row) term_row[e] = flag_t[e];
+        if (trunc_row && flag_u != trunc_row) trunc_row[e] = flag_u[e];
+    } else {
+        if (term_row) term_row[e] = done[e];
+        if (trunc_row) trunc_row[e] = 0;
+    }
+}
+
+namespace {
+
+// the largest coarse map the shared checks admit is the one whose network words fill a workgroup's 64 KiB of LDS
+static_assert(bdz_policy_lds_words(GCA_POLICY_C_MAX) * 4 == 65536, "GCA_POLICY_C_MAX must follow bdz_policy_lds_words");
+constexpr size_t BPOL_STATIC_LDS = 512;  // bulldozer_policy_rollout_kernel's own words (wave_cnt, bc), rounded up
+
+// The device's view of the weights of a checked policy.
+int bdz_policy_view(const char* who, const gca_bulldozer_policy* p, int C, uint64_t policy_seed, int greedy,
+                    BdzPolicyW* w) {
+    // the kernels' 16-B loads of the weights: the host build's loops take any alignment
+    if (!gca_bdz_policy_weights_aligned(p))
+        return gca_refuse(who, "policy.w_local and policy.w_coarse must be 16-B aligned");
+    w->w_local = p->w_local; w->w_coarse = p->w_coarse; w->b1 = p->b1; w->w_out = p->w_out; w->b2 = p->b2;
+    w->S = 2 * p->radius + 1;
+    w->SS = w->S * w->S;
+    w->C = C;
+    w->Hd = p->hidden;
+    w->lgHd = 5;
+    while ((1 << w->lgHd) < p->hidden) ++w->lgHd;
+    w->greedy = greedy != 0;
+    w->k0 = (uint32_t)policy_seed;
+    w->k1 = (uint32_t)(policy_seed >> 32);
+    return GCA_OK;
+}
+
+}  // namespace
+
+extern "C" int gca_bulldozer_policy_act(const gca_bulldozer_policy* p, int C, const uint8_t* local, const float* coarse,
+                                        const int64_t* steps_elapsed, const uint32_t* episode, int env_offset,
+                                        uint64_t policy_seed, int greedy, int32_t* action, float* logits, float* value,
+                                        int E, void* stream) {
+    if (const int st = gca_check_bdz_policy_act(p, C, local, coarse, steps_elapsed, action, E)) return st;
+    BdzPolicyW w;
+    if (const int st = bdz_policy_view("bulldozer_policy_act", p, C, policy_seed, greedy, &w)) return st;
+    hipLaunchKernelGGL(bulldozer_policy_act_kernel, dim3((unsigned)E), dim3(BPOL_VT),
+                       (size_t)bdz_policy_lds_words(C) * 4, (hipStream_t)stream, w, local, coarse, steps_elapsed,
+                       episode, env_offset, action, logits, value);
+    GCA_CHECK_LAUNCH("bulldozer_policy_act");
+    return GCA_OK;
+}
+
+extern "C" int gca_bulldozer_policy_rollout(const gca_bulldozer_params* p, const gca_bulldozer_policy* policy,
+                                            uint64_t policy_seed, int greedy, int K, int32_t* action_out,
+                                            float* logits_out, float* value_out, double* reward_out,
+                                            uint8_t* terminated_out, uint8_t* truncated_out, uint8_t* local_out,
+                                            float* coarse_out, void* scratch, int autoreset, uint64_t reset_seed,
+                                            int64_t max_steps, const float* cdf, const uint8_t* values,
+                                            uint32_t* episode, int64_t* last_length, uint8_t* terminated,
+                                            uint8_t* truncated, double* accu, int32_t* steps, uint8_t* done,
+                                            const double* wind, int64_t wind_stride, uint32_t* rng_step,
+                                            uint8_t* parity, uint8_t* buf0, uint8_t* buf1, int H, int W, int32_t* pos,
+                                            int32_t* counts, uint8_t* hit, double* reward, int64_t* steps_elapsed,
+                                            int E, void* stream) {
+    const char* who = "bulldozer_policy_rollout";
+    const bool have =
+        p && accu && steps && done && wind && rng_step && parity && buf0 && buf1 && pos && counts && hit && reward;
+    if (const int status = bdz_check_fused(who, have, p, E, H, W, buf0, buf1, wind_stride, &K)) return status;
+    if (!steps_elapsed) return gca_refuse(who, "steps_elapsed is null");
+    // gca_bulldozer_reset_where's checks (the reset's inputs and state are read only under autoreset)
+    if (buf0 == buf1) return gca_refuse(who, "buf0 and buf1 must differ");
+    if (!(H < 32768)) return gca_refuse(who, "H < 32768");
+    if (!(max_steps >= 0)) return gca_refuse(who, "max_steps >= 0");
+    if (autoreset) {
+        if (!(cdf && values && episode)) return gca_refuse(who, "autoreset needs cdf, values and episode");
+        if (!(p->env_offset >= 0)) return gca_refuse(who, "env_offset >= 0");
+    }
+    if (const int st = gca_check_bdz_policy(who, policy)) return st;
+    const int B = policy->block, Hc = (H + B - 1) / B, Wc = (W + B - 1) / B, C = 2 * Hc * Wc;
+    // the act kernel's and the resident kernel's LDS: both paths hold the coarse map in a workgroup
+    if (const int st = gca_check_policy_c(who, C)) return st;
+    BdzPolArgs q;
+    if (const int st = bdz_policy_view(who, policy, C, policy_seed, greedy, &q.w)) return st;
+    const size_t lds_bytes = (size_t)bdz_policy_lds_words(C) * 4;
+    const bool resident = gca_policy_obs_rows_shape(H, W, B) && lds_bytes + BPOL_STATIC_LDS <= 65536;
+    if (!resident && !(scratch || (action_out && local_out && coarse_out)))
+        return gca_refuse(who, "this shape runs K x 3 launches and needs `scratch` for the records not kept");
+    if (((uintptr_t)scratch & 3u) != 0) return gca_refuse(who, "scratch 4-B aligned");
+    if (K == 0) return GCA_OK;
+    hipStream_t st = (hipStream_t)stream;
+    if (resident) {
+        q.radius = policy->radius;
+        q.lgB = 3;
+        while ((1 << q.lgB) < B) ++q.lgB;
+        q.HcWc = Hc * Wc;
+        q.Wc = Wc;
+        q.inv = 1.0f / (float)(B * B);
+        q.autoreset = autoreset != 0;
+        q.logits_out = logits_out; q.value_out = value_out; q.local_out = local_out; q.coarse_out = coarse_out;
+        const RolloutExt ext{nullptr, truncated_out, reset_seed, max_steps, cdf, values, episode, last_length,
+                             terminated, truncated};
+        const int threads = bdz_threads(H, W);
+        const bool std_codes = p->empty == 0 && p->tree == 3 && p->fire == 25;
+        const bool solo = bdz_modify_keeps_fire(*p);
+#define GCA_BPOL_LAUNCH(NWV, STDV, SOLOV)                                                                           \
+    hipLaunchKernelGGL((bulldozer_policy_rollout_kernel<NWV, STDV, SOLOV>), dim3((unsigned)E), dim3(threads),       \
+                       lds_bytes, st, *p, K, action_out, reward_out, terminated_out, accu, steps, done, wind,       \
+                       wind_stride, rng_step, parity, buf0, buf1, H, pos, counts, hit, reward, steps_elapsed, E, ext, \
+                       q)
+#define GCA_BPOL_PICK(NWV)                                      \
+    do {                                                        \
+        if (std_codes && solo) GCA_BPOL_LAUNCH(NWV, true, true); \
+        else if (solo) GCA_BPOL_LAUNCH(NWV, false, true);        \
+        else GCA_BPOL_LAUNCH(NWV, false, false);                 \
+    } while (0)
+        if (W == 256) GCA_BPOL_PICK(1); else GCA_BPOL_PICK(2);
+#undef GCA_BPOL_PICK
+#undef GCA_BPOL_LAUNCH
+        GCA_CHECK_LAUNCH(who);
+        return GCA_OK;
+    }
+    // K x (observation, act, step [, reset], record rows). A step's action, window and coarse map go to their record
+    // rows, or to `scratch` where the caller keeps no such record.
+    const size_t SS = (size_t)q.w.SS;
+    int32_t* s_act = (int32_t*)scratch;
+    float* s_coarse = (float*)scratch + 2 * (size_t)E;
+    uint8_t* s_local = (uint8_t*)(s_coarse + (size_t)E * C);
+    const bool rows = reward_out || terminated_out || truncated_out;
+    for (int k = 0; k < K; ++k) {
+        const size_t o = (size_t)k * (size_t)E;
+        int32_t* act_k = action_out ? action_out + 2 * o : s_act;
+        uint8_t* loc_k = local_out ? local_out + o * SS : s_local;
+        float* coa_k = coarse_out ? coarse_out + o * (size_t)C : s_coarse;
+        if (const int status = gca_policy_observation(buf0, buf1, parity, pos, E, H, W, p->empty, p->tree, p->fire,
+                                                      policy->radius, B, 0, loc_k, coa_k, stream))
+            return status;
+        hipLaunchKernelGGL(bulldozer_policy_act_kernel, dim3((unsigned)E), dim3(BPOL_VT), lds_bytes, st, q.w, loc_k,
+                           coa_k, steps_elapsed, episode, (int)p->env_offset, act_k,
+                           logits_out ? logits_out + o * 11 : nullptr, value_out ? value_out + o : nullptr);
+        GCA_CHECK_LAUNCH(who);
+        if (const int status = gca_bulldozer_step_fused(p, act_k, accu, steps, done, wind, wind_stride, rng_step, parity,
+                                                        buf0, buf1, H, W, pos, counts, hit, reward, steps_elapsed,
+                                                        nullptr, E, stream))
+            return status;
+        uint8_t* term_k = terminated_out ? terminated_out + o : nullptr;
+        uint8_t* trunc_k = truncated_out ? truncated_out + o : nullptr;
+        uint8_t* flag_t = terminated ? terminated : term_k;
+        uint8_t* flag_u = truncated ? truncated : trunc_k;
+        if (autoreset)
+            if (const int status = gca_bulldozer_reset_where(p, reset_seed, nullptr, max_steps, -1, cdf, values, done,
+                                                             flag_t, flag_u, episode, last_length, accu, parity, buf0,
+                                                             buf1, H, W, pos, counts, hit, steps_elapsed, E, stream))
+                return status;
+        if (rows) {
+            hipLaunchKernelGGL(bulldozer_policy_record_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, st, E,
+                               autoreset != 0, reward, done, flag_t, flag_u, reward_out ? reward_out + o : nullptr,
+                               term_k, trunc_k);
+            GCA_CHECK_LAUNCH(who);
+        }
+    }
+    return GCA_OK;
 }

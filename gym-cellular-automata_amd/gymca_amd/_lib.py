@@ -187,6 +187,16 @@ class HeliPolicy(ctypes.Structure):
     ]
 
 
+TAG_BPOLICY = 0x42504F4C
+
+
+class BulldozerPolicyStruct(ctypes.Structure):
+    """gca_bulldozer_policy (include/gca.h): the dims and the five weight arrays' device (host build: host) addresses;
+    w_out is [hidden][12], b2 [12]."""
+
+    _fields_ = list(HeliPolicy._fields_)
+
+
 GCA_ADAM_MAX_TENSORS = 8
 GCA_ADAM_STATE_WORDS = 16
 TAG_PERM = 0x5045524D
@@ -276,6 +286,11 @@ _SIGNATURES = {
     "gca_helicopter_policy_rollout": ([c_int, c_int, c_int, c_int, c_uint64, c_int, POINTER(HeliPolicy), c_uint64,
                                        c_int, c_int, P, P, P, P, P, P, P, P, P, P, P, P, P, P, c_int, c_int, P, P, P, P,
                                        P, c_int, P], c_int),
+    "gca_bulldozer_policy_act": ([POINTER(BulldozerPolicyStruct), c_int, P, P, P, P, c_int, c_uint64, c_int, P, P, P,
+                                  c_int, P], c_int),
+    "gca_bulldozer_policy_rollout": ([POINTER(BulldozerParams), POINTER(BulldozerPolicyStruct), c_uint64, c_int, c_int,
+                                      P, P, P, P, P, P, P, P, P, c_int, c_uint64, c_int64, P, P, P, P, P, P, P, P, P,
+                                      P, c_int64, P, P, P, P, c_int, c_int, P, P, P, P, P, c_int, P], c_int),
     "gca_gae": ([P, P, P, P, c_float, c_float, c_int, c_int, P, P, P], c_int),
     "gca_helicopter_policy_grad_workspace": ([POINTER(HeliPolicy), c_int, c_int], c_int64),
     "gca_helicopter_policy_grad": ([POINTER(HeliPolicy), c_int, P, P, P, P, P, P, c_int64, P, c_int, c_float, c_float,
@@ -295,6 +310,8 @@ CPU_SYMBOLS = ("gca_last_error", "gca_version", "gca_philox", "gca_count_cells",
                "gca_bulldozer_reset_where", "gca_policy_observation", "gca_helicopter_policy_act",
                "gca_helicopter_policy_rollout", "gca_gae", "gca_helicopter_policy_grad_workspace",
                "gca_helicopter_policy_grad", "gca_adam_step_workspace", "gca_adam_step", "gca_permutation")
+# the bulldozer policy's network on host arrays (the closed-loop rollout needs the Windy CA: device build only)
+CPU_BULLDOZER_POLICY_SYMBOLS = ("gca_bulldozer_policy_act",)
 
 _lib = None
 _lib_cpu = None
@@ -329,7 +346,7 @@ def load_cpu():
     if not os.path.exists(CPU_LIB_PATH):
         raise GCAError(f"{CPU_LIB_PATH} not found: build it with `make -C gym-cellular-automata_amd/csrc`")
     lib = ctypes.CDLL(CPU_LIB_PATH, mode=ctypes.RTLD_LOCAL)
-    for name in CPU_SYMBOLS:
+    for name in CPU_SYMBOLS + CPU_BULLDOZER_POLICY_SYMBOLS:
         fn = getattr(lib, name)
         fn.argtypes, fn.restype = _SIGNATURES[name]
     _lib_cpu = lib

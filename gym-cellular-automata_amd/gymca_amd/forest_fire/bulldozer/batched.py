@@ -129,6 +129,7 @@ class BatchedForestFireBulldozerEnv(BatchedEnvBase):
         self._reset_call = None
         self._rollout_call = None
         self._observe_calls = {}
+        self._policy_calls = {}
 
     # ------------------------------------------------------------------ state
     def reset(self, seed=None, grids=None, positions=None):
@@ -187,6 +188,7 @@ class BatchedForestFireBulldozerEnv(BatchedEnvBase):
         self._reset_call = None
         self._rollout_call = None
         self._observe_calls = {}
+        self._policy_calls = {}
         self._views()
 
     def _views(self):
@@ -394,6 +396,174 @@ class BatchedForestFireBulldozerEnv(BatchedEnvBase):
            truncated_out.data_ptr(), 1 if self.autoreset else 0, self._reset_seed,
            (self.max_episode_steps or 0) if self.autoreset else 0, dev.raw_stream(self._dev_index))
         return reward_out, terminated_out, truncated_out
+
+    # ------------------------------------------------------------------ the policy inside the env's launches
+    def _check_policy(self, policy, who):
+        from .policy import BulldozerPolicy
+
+        if not isinstance(policy, BulldozerPolicy):
+            raise ValueError(f"{who}: policy must be a BulldozerPolicy")
+        if policy.shape != (self.nrows, self.ncols):
+            raise ValueError(f"{who}: the policy was built for a {policy.shape} grid, the env is "
+                             f"{(self.nrows, self.ncols)}")
+        if policy.device != self.device:
+            raise ValueError(f"{who}: the policy lives on {policy.device}, the env on {self.device}")
+        return policy
+
+    def _policy_call(self, kind, policy, make):
+        """The pre-bound call of `kind` for this policy; bound again when a policy tensor was replaced (its version
+        moved) or the env rebound. The entry keeps the policy, its tensors of that version and the call's scratch alive,
+        so the cache is bounded: beyond _POLICY_CALLS_MAX entries the one bound longest ago is dropped (a trainer that
+        builds policy after policy against one env does not keep them all; a dropped policy is simply bound again). A
+        graph captured from a call replays that entry's addresses: whoever holds such a graph keeps the number of
+        policies in use on this env within the bound, or captures again."""
+        key = (kind, id(policy))
+        calls = self._policy_calls
+        pc = calls.get(key)
+        if pc is None or pc[0] != policy.version or pc[1] is not policy:
+            calls.pop(key, None)
+            while len(calls) >= self._POLICY_CALLS_MAX:
+                del calls[next(iter(calls))]
+            pc = (policy.version, policy) + tuple(make())
+        else:
+            del calls[key]  # least recently used first: a hit moves the entry to the end
+        calls[key] = pc
+        return pc
+
+    _POLICY_CALLS_MAX = 8
+
+    def act(self, policy, local=None, coarse=None, seed=0, greedy=False, action_out=None, logits_out=None,
+            value_out=None):
+        """The policy's (move, shoot) for every env: observe(policy.radius, policy.block) unless both `local` and
+        `coarse` are given (tensors of observe's dtypes and shapes), then ONE launch of the network
+        (gca_bulldozer_policy_act). Returns (action int32 (E, 2), logits float32 (E, 11): nine move logits then two shoot
+        logits, value float32 (E,)), written into the given outputs or allocated. The draw is keyed by (seed, global env
+        id, the env's steps_elapsed and episode); greedy=True takes the first maximum of each head instead. No env state
+        changes, so the value of the state after a rollout (the bootstrap) is free of side effects. No sync."""
+        import torch
+
+        from .. import policy_obs
+
+        policy = self._check_policy(policy, "act")
+        E = self.num_envs
+        ls, cs = policy_obs.output_shapes(self, policy.radius, policy.block)
+        if (local is None) != (coarse is None):
+            raise ValueError("act: give both local and coarse, or neither")
+        if local is None:
+            local, coarse = self.observe(policy.radius, policy.block)
+        else:
+            check_tensor(local, torch.uint8, ls, self._dev_index, "act", "local")
+            check_tensor(coarse, torch.float32, cs, self._dev_index, "act", "coarse")
+        action_out = self._out(action_out, torch.int32, (E, 2), "act", "action_out")
+        logits_out = self._out(logits_out, torch.float32, (E, 11), "act", "logits_out")
+        value_out = self._out(value_out, torch.float32, (E,), "act", "value_out")
+        pc = self._policy_call("act", policy, lambda: (BoundCall(
+            "gca_bulldozer_policy_act", policy.struct, policy.C, SLOT, SLOT, dev.ptr(self.steps_elapsed),
+            dev.ptr(self.episode), self.env_offset, SLOT, SLOT, SLOT, SLOT, SLOT, E, SLOT,
+            keep=(self.steps_elapsed, self.episode) + policy.tensors()),))
+        pc[2](local.data_ptr(), coarse.data_ptr(), seed64(seed), 1 if greedy else 0, action_out.data_ptr(),
+              logits_out.data_ptr(), value_out.data_ptr(), dev.raw_stream(self._dev_index))
+        return action_out, logits_out, value_out
+
+    _POLICY_RECORDS = ("action", "logits", "value", "reward", "terminated", "truncated", "local", "coarse")
+
+    def rollout_policy(self, policy, K, seed=0, greedy=False, record=_POLICY_RECORDS, action_out=None,
+                       logits_out=None, value_out=None, reward_out=None, terminated_out=None, truncated_out=None,
+                       local_out=None, coarse_out=None):
+        """K closed-loop env steps of every env in one call: bit for bit K x (observe(policy.radius, policy.block),
+        act(policy, seed=seed, greedy=greedy), step(action)) under the env's own `autoreset` / `max_episode_steps` -- a
+        PPO collection loop's on-policy experience, episode ends included. Returns a dict of the records named in
+        `record` (and of every record whose output tensor is given), row k what step k saw and did: action int32
+        (K, E, 2), logits float32 (K, E, 11), value float32 (K, E), reward float64 (K, E), terminated / truncated uint8
+        (K, E) as rollout() defines them, local uint8 (K, E, S, S), coarse float32 (K, E, 2, Hc, Wc); step k's observation
+        is of the state before step k, so under autoreset row k + 1 after an episode's end is the new episode's. An env
+        that is done without autoreset keeps observing, acting and recording its no-op step. Given outputs must be
+        contiguous tensors of that dtype and shape on the env's device. Afterwards the env is in the state the K steps
+        leave, so step / rollout / rollout_policy interleave freely. With the fused step, block 8 / 16 / 32 dividing H
+        and a coarse map that fits in LDS everything is ONE launch (gca_bulldozer_policy_rollout); other fused shapes run
+        the K x 3 (+ reset) launches inside that call, a non-fused env K x (observe, act, step) from here with device
+        copies into the records. No sync, and with every record given no allocation: capturable."""
+        import torch
+
+        from .. import policy_obs
+
+        policy = self._check_policy(policy, "rollout_policy")
+        K = int(K)
+        if K < 0:
+            raise ValueError("rollout_policy: K >= 0")
+        E = self.num_envs
+        ls, cs = policy_obs.output_shapes(self, policy.radius, policy.block)
+        spec = {"action": (torch.int32, (K, E, 2)), "logits": (torch.float32, (K, E, 11)),
+                "value": (torch.float32, (K, E)), "reward": (torch.float64, (K, E)),
+                "terminated": (torch.uint8, (K, E)), "truncated": (torch.uint8, (K, E)),
+                "local": (torch.uint8, (K,) + ls), "coarse": (torch.float32, (K,) + cs)}
+        unknown = [r for r in record if r not in spec]
+        if unknown:
+            raise ValueError(f"rollout_policy: unknown records {unknown}; choose from {self._POLICY_RECORDS}")
+        given = {"action": action_out, "logits": logits_out, "value": value_out, "reward": reward_out,
+                 "terminated": terminated_out, "truncated": truncated_out, "local": local_out, "coarse": coarse_out}
+        recs = {}
+        for name in self._POLICY_RECORDS:
+            dtype, shape = spec[name]
+            if given[name] is not None or name in record:
+                recs[name] = self._out(given[name], dtype, shape, "rollout_policy", f"{name}_out")
+        if K == 0:
+            return recs
+        if not self.fused:
+            return self._rollout_policy_steps(policy, K, seed, greedy, recs)
+
+        def make():
+            H, W = self.nrows, self.ncols
+            # the K x 3 launch path keeps a step's action / window / coarse map here when the caller keeps no record
+            scratch = torch.empty(E * (8 + 4 * policy.C + policy.S * policy.S), dtype=torch.uint8, device=self.device)
+            return BoundCall(
+                "gca_bulldozer_policy_rollout", self.params, policy.struct, SLOT, SLOT, SLOT, SLOT, SLOT, SLOT, SLOT,
+                SLOT, SLOT, SLOT, SLOT, dev.ptr(scratch), SLOT, SLOT, SLOT, dev.ptr(self._reset_cdf),
+                dev.ptr(self._reset_vals), dev.ptr(self.episode), dev.ptr(self.last_episode_length),
+                dev.ptr(self._terminated), dev.ptr(self._truncated_u8), dev.ptr(self.accu), dev.ptr(self.steps),
+                dev.ptr(self.done), dev.ptr(self.wind), 9, dev.ptr(self.rng_step), dev.ptr(self.parity),
+                dev.ptr(self.buf[0]), dev.ptr(self.buf[1]), H, W, dev.ptr(self.pos), dev.ptr(self.counts),
+                dev.ptr(self.hit), dev.ptr(self.reward), dev.ptr(self.steps_elapsed), E, SLOT,
+                keep=self._bound_tensors() + policy.tensors() + (
+                    scratch, self._reset_cdf, self._reset_vals, self._terminated, self._truncated_u8, self.episode,
+                    self.last_episode_length)),
+
+        pc = self._policy_call("rollout", policy, make)
+        p = lambda name: recs[name].data_ptr() if name in recs else None
+        pc[2](seed64(seed), 1 if greedy else 0, K, p("action"), p("logits"), p("value"), p("reward"), p("terminated"),
+              p("truncated"), p("local"), p("coarse"), 1 if self.autoreset else 0, self._reset_seed,
+              (self.max_episode_steps or 0) if self.autoreset else 0, dev.raw_stream(self._dev_index))
+        return recs
+
+    def _rollout_policy_steps(self, policy, K, seed, greedy, recs):
+        """rollout_policy of a non-fused env: K x (observe, act, step), each step's results copied into the records on
+        the device. The observation and the network's outputs go straight into their record rows where those exist."""
+        import torch
+
+        from .. import policy_obs
+
+        E = self.num_envs
+        ls, cs = policy_obs.output_shapes(self, policy.radius, policy.block)
+        tmp = {"local": torch.empty(ls, dtype=torch.uint8, device=self.device),
+               "coarse": torch.empty(cs, dtype=torch.float32, device=self.device),
+               "action": torch.empty((E, 2), dtype=torch.int32, device=self.device),
+               "logits": torch.empty((E, 11), dtype=torch.float32, device=self.device),
+               "value": torch.empty(E, dtype=torch.float32, device=self.device)}
+        row = lambda name, k: recs[name][k] if name in recs else tmp[name]
+        for k in range(K):
+            lo, co = self.observe(policy.radius, policy.block, row("local", k), row("coarse", k))
+            a, _, _ = self.act(policy, lo, co, seed, greedy, row("action", k), row("logits", k), row("value", k))
+            self.step(a)
+            if "reward" in recs:
+                recs["reward"][k].copy_(self.reward)
+            if "terminated" in recs:
+                recs["terminated"][k].copy_(self._terminated if self.autoreset else self.done)
+            if "truncated" in recs:
+                if self.autoreset:
+                    recs["truncated"][k].copy_(self._truncated_u8)
+                else:
+                    recs["truncated"][k].zero_()
+        return recs
 
     def sample_actions(self, out=None, tag=9):
         """Uniform random actions for every env on the device -- the batched `action_space.sample()` (move in [0, 9),

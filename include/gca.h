@@ -669,6 +669,82 @@ int gca_helicopter_policy_rollout(int empty, int tree, int fire, int max_freeze,
                                   uint8_t* buf0, uint8_t* buf1, int H, int W, int32_t* pos, int32_t* counts,
                                   uint8_t* hit, double* reward, int64_t* steps_elapsed, int E, void* stream);
 
+/* ------------------------------------------ bulldozer policy (the two-headed agent of the reference's PPO collection
+ * loop on the bulldozer env: Actor(action_dims=[9, 2]), agents/jax_ppo.py:305-356, 866-899)
+ * The helicopter policy's network with TWELVE outputs. Inputs, hidden layer and summation order are exactly those of
+ * "helicopter policy" above: the G = 1024 / Hd groups, a group's terms in increasing n from 0.0f, the relu, and per
+ * output the 16 partial sums q_r (j = r, r + 16, ... left to right from 0.0f) that meet in the 8-4-2-1 tree;
+ * out_o = b2[o] + d for o = 0..11. out[0..8] are the move logits l_i, out[9..10] the shoot logits s_0, s_1, out[11] the
+ * value. All f32, every multiply and add rounded on its own (no fma).
+ *   draw     x = Philox((uint32)steps_elapsed[e], env_offset + e, episode ? episode[e] : 0, GCA_TAG_BPOLICY) under
+ *            policy_seed. Not keyed by rng_step: in this env it counts CA passes, not env steps, and would repeat one
+ *            uniform over several steps.
+ *   move     the helicopter rule on l_0..l_8 with u = u01_f32(x.x): m the first maximum, p_i = exp_f32(l_i - m),
+ *            c_i = c_{i-1} + p_i, the first i with u * c_8 < c_i, else 8.
+ *   shoot    m the first maximum of (s_0, s_1) (m = s_0; if s_1 > m then m = s_1), p_i = exp_f32(s_i - m), c_0 = p_0,
+ *            c_1 = c_0 + p_1, u = u01_f32(x.y): shoot = 0 if u * c_1 < c_0, else 1.
+ *   greedy   != 0: the index of the first maximum of each head, nothing drawn.
+ * Non-finite weights still give a move in [0, 8] and a shoot in {0, 1}; nothing else is promised for them.
+ * The order depends on (S, C, Hd) only: never on E, K, the number of waves of the launch or the path that runs. The
+ * device (the helicopter layout's 256 float4 "virtual threads" looped over the workgroup's real threads, so any wave
+ * count gives the same sums), the host build and tests/_bulldozer_policy_ref.py follow it and agree bit for bit.
+ * Layouts: w_local f32 [S*S][4][Hd] and w_coarse f32 [C][Hd] (16-B aligned on the device), b1 f32 [Hd], w_out f32
+ * [Hd][12], b2 f32 [12] (device arrays; the struct itself is a host struct read at call time). */
+#define GCA_TAG_BPOLICY 0x42504F4Cu /* 'BPOL' : the bulldozer policy's draw (word 0 move, word 1 shoot) */
+typedef struct {
+    int32_t radius, block;     /* gca_policy_observation's: radius in [0, 31], block a power of two in [1, 64] */
+    int32_t hidden;            /* Hd, a power of two in [32, 256]                                               */
+    int32_t reserved;          /* 0                                                                             */
+    const float* w_local;
+    const float* w_coarse;
+    const float* b1;
+    const float* w_out;
+    const float* b2;
+} gca_bulldozer_policy;
+
+/* The policy's action for E envs on a given observation, ONE launch (a workgroup per env), no allocation, no sync:
+ * capturable. local u8 [E][S][S] and coarse f32 [E][C] as gca_policy_observation writes them (C = 2 Hc Wc even, at most
+ * 15088; p->block is not read). steps_elapsed i64 [E] and episode u32 [E] (nullable: 0) key the draw and are the only
+ * env state read; nothing is changed, so the value of the state after a rollout (the bootstrap) is free of side
+ * effects. Writes action i32 [E][2] (move, shoot), logits f32 [E][11] (nullable: the nine move logits, then the two
+ * shoot logits) and value f32 [E] (nullable). The host build runs plain loops in the same order. */
+int gca_bulldozer_policy_act(const gca_bulldozer_policy* p, int C, const uint8_t* local, const float* coarse,
+                             const int64_t* steps_elapsed, const uint32_t* episode, int env_offset,
+                             uint64_t policy_seed, int greedy, int32_t* action, float* logits, float* value, int E,
+                             void* stream);
+
+/* K closed-loop env steps of E bulldozer envs: bit for bit K x (gca_policy_observation(p->radius, p->block) of the state
+ * before the step, gca_bulldozer_policy_act on it, gca_bulldozer_step_fused (meet = NULL) with that action, and then,
+ * when autoreset != 0, gca_bulldozer_reset_where(mask = NULL, max_steps, set_episode = -1)). The arguments are
+ * gca_bulldozer_rollout's with actions / action_seed replaced by the policy. An env that is done without autoreset still
+ * observes, acts and records every step; its step is the no-op (reward 0, steps_elapsed unchanged, so a fixed seed
+ * repeats its action). Records, each nullable, row k = what step k saw and did: action_out i32 (K, E, 2), logits_out
+ * f32 (K, E, 11), value_out f32 (K, E), reward_out f64 (K, E), terminated_out / truncated_out u8 (K, E) as
+ * gca_bulldozer_rollout defines them, local_out u8 (K, E, S, S), coarse_out f32 (K, E, 2, Hc, Wc). steps_elapsed is
+ * required; episode only under autoreset (NULL keys the draw with 0).
+ * ONE launch, one workgroup per env with the env's state in registers, where the observation's rows form applies
+ * (block 8 / 16 / 32, H % block == 0) and the coarse map plus the network's words fit in a workgroup's 64 KiB of LDS
+ * (4 * (C rounded up to 4) + 5184 bytes, plus 512 of the kernel's own: C = 8192 for 512 x 512 at block 8 fits). The
+ * coarse map then lives in LDS for the whole launch: counted from the current plane on entry, after every CA pass and
+ * after every in-launch reset, and adjusted by -+ 1 / block^2 where Modify changes a cell in between (every value is a
+ * multiple of 1 / block^2 that is at most 1, so the adjusted map equals a recount exactly). Every other shape runs the
+ * K x 3 (+ reset, + one small launch that writes the reward / flag rows) launches on the stream with the same results;
+ * they keep a step's action, window and coarse map in the record rows, or, for a record the caller does not keep, in
+ * `scratch`: E * (8 + 4 C + S*S) bytes of device memory, 4-byte aligned (nullable when action_out, local_out and
+ * coarse_out are given or the shape is resident; pass it always to be shape-agnostic). Launches only: capturable.
+ * K == 0 is a no-op; K < 0 and every other argument error is reported before any launch. Device build only (the host
+ * build has no Windy CA for these sizes). */
+int gca_bulldozer_policy_rollout(const gca_bulldozer_params* p, const gca_bulldozer_policy* policy,
+                                 uint64_t policy_seed, int greedy, int K, int32_t* action_out, float* logits_out,
+                                 float* value_out, double* reward_out, uint8_t* terminated_out, uint8_t* truncated_out,
+                                 uint8_t* local_out, float* coarse_out, void* scratch, int autoreset,
+                                 uint64_t reset_seed, int64_t max_steps, const float* cdf, const uint8_t* values,
+                                 uint32_t* episode, int64_t* last_length, uint8_t* terminated, uint8_t* truncated,
+                                 double* accu, int32_t* steps, uint8_t* done, const double* wind, int64_t wind_stride,
+                                 uint32_t* rng_step, uint8_t* parity, uint8_t* buf0, uint8_t* buf1, int H, int W,
+                                 int32_t* pos, int32_t* counts, uint8_t* hit, double* reward, int64_t* steps_elapsed,
+                                 int E, void* stream);
+
 /* ------------------------------------------ PPO update (the learner's half of the reference's main loop:
  * agents/jax_ppo.py:932-984 compute_gae, :987-1043 ppo_loss and its gradient), on rollout_policy's records
  * gca_gae: reward f64 (K, E) and value f32 (K, E) as gca_helicopter_policy_rollout records them, next_value f32 (E) the
