@@ -125,10 +125,11 @@ static inline int gca_check_policy_observation(const void* buf0, const void* buf
 }
 
 // ----------------------------------------------------------------- the helicopter policy
-// The largest coarse map (C = 2 Hc Wc floats) of a policy: with the network's other LDS words (gca_heli.hip ties the
-// two together) it fills the 64 KiB of a workgroup. The host build keeps the same limit.
+// The largest coarse map (C = 2 Hc Wc floats) of a policy: with the network's other LDS words (gca_policy_dev.h ties
+// the two together) it fills the 64 KiB of a workgroup. The host build keeps the same limit.
 constexpr int GCA_POLICY_C_MAX = 15088;
 
+// two functions with gca_check_bdz_policy (below) only because the refusal texts differ: test_abi_refusals.py pins both
 static inline int gca_check_policy(const gca_heli_policy* p) {
     GCA_CHECK_ARG(p && p->w_local && p->w_coarse && p->b1 && p->w_out && p->b2, "helicopter_policy: null weights");
     GCA_CHECK_ARG(p->radius >= 0 && p->radius <= 31, "helicopter_policy: radius in [0, 31]");
@@ -139,8 +140,8 @@ static inline int gca_check_policy(const gca_heli_policy* p) {
     return GCA_OK;
 }
 
-// the 16-B loads of the device's kernels; of a checked policy
-static inline bool gca_policy_weights_aligned(const gca_heli_policy* p) {
+// the 16-B loads of the device's kernels; of a checked policy of either agent
+static inline bool gca_policy_weights_aligned(const gca_policy* p) {
     return (((uintptr_t)p->w_local | (uintptr_t)p->w_coarse) & 15u) == 0;
 }
 
@@ -194,10 +195,6 @@ static inline int gca_check_bdz_policy(const char* who, const gca_bulldozer_poli
     if (!(p->hidden >= 32 && p->hidden <= 256 && (p->hidden & (p->hidden - 1)) == 0))
         return gca_refuse(who, "policy.hidden must be a power of two in [32, 256]");
     return GCA_OK;
-}
-
-static inline bool gca_bdz_policy_weights_aligned(const gca_bulldozer_policy* p) {
-    return (((uintptr_t)p->w_local | (uintptr_t)p->w_coarse) & 15u) == 0;
 }
 
 static inline int gca_check_bdz_policy_act(const gca_bulldozer_policy* p, int C, const void* local, const void* coarse,

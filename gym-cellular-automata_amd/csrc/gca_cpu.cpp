@@ -17,8 +17,8 @@
 //   gca_bulldozer_reset_where  bulldozer.py:221-275 + ca_env.py:64-81 (gca_reset.hip), the per-env reset's twin
 //   gca_policy_observation  the batched envs' policy observation (gca_policy_obs.hip), pinned by tests/_policy_obs_ref.py
 //   gca_helicopter_policy_act / gca_helicopter_policy_rollout  the policy network and the closed-loop rollout
-//                     (gca_heli.hip, gca_heli_policy_dev.h), in gca.h's summation order
-//   gca_bulldozer_policy_act  the bulldozer policy network alone (gca_bdz_policy_dev.h), in gca.h's summation order;
+//                     (gca_heli.hip, gca_policy_dev.h), in gca.h's summation order
+//   gca_bulldozer_policy_act  the bulldozer policy network alone (gca_policy_dev.h), in gca.h's summation order;
 //                     gca_bulldozer_policy_rollout needs the Windy CA and is in the device build only
 //   gca_gae / gca_helicopter_policy_grad(_workspace)  the PPO update (gca_ppo.hip): the GAE recurrence bit for bit, the
 //                     loss gradient in double as a second yardstick
@@ -482,9 +482,10 @@ static inline float exp_f32_host(float x) {
     return p;
 }
 
-// One env's outputs and action in gca.h's order. loc [S*S], coarse [C]; out [10] receives the logits and the value.
-static int32_t policy_eval_host(const gca_heli_policy* p, int C, const uint8_t* loc, const float* coarse,
-                                uint32_t env_id, uint32_t rs, uint64_t policy_seed, int greedy, float* out) {
+// One env's NOUT outputs in gca.h's order, for both agents (10: the helicopter, 12: the bulldozer): the hidden layer
+// and the heads. loc [S*S], coarse [C]; out [NOUT].
+static void policy_outputs_host(const gca_policy* p, int NOUT, int C, const uint8_t* loc, const float* coarse,
+                                float* out) {
     const int S = 2 * p->radius + 1, SS = S * S, N = SS + C, Hd = p->hidden, G = 1024 / Hd;
     float h[256];
     for (int j = 0; j < Hd; ++j) {
@@ -499,36 +500,50 @@ static int32_t policy_eval_host(const gca_heli_policy* p, int C, const uint8_t* 
         }
         h[j] = hj > 0.0f ? hj : 0.0f;
     }
-    for (int o = 0; o < 10; ++o) {
+    for (int o = 0; o < NOUT; ++o) {
         float q[16];
         for (int r = 0; r < 16; ++r) {
             float acc = 0.0f;
-            for (int j = r; j < Hd; j += 16) acc = acc + p->w_out[j * 10 + o] * h[j];
+            for (int j = r; j < Hd; j += 16) acc = acc + p->w_out[j * NOUT + o] * h[j];
             q[r] = acc;
         }
         for (int half = 8; half >= 1; half >>= 1)
             for (int r = 0; r < half; ++r) q[r] = q[r] + q[r + half];
         out[o] = p->b2[o] + q[0];
     }
-    float m = out[0];
+}
+
+static inline float u01_f32_host(uint32_t x) { return (float)(x >> 8) * 0x1.0p-24f; }
+
+// The move rule both agents use on the nine logits l (gca.h "sampling"): the first maximum when greedy, else the
+// first i with t < c_i under the uniform of the Philox word x.
+static int32_t policy_move_host(const float* l, int greedy, uint32_t x) {
+    float m = l[0];
     int32_t first = 0;
     for (int i = 1; i < 9; ++i)
-        if (out[i] > m) {
-            m = out[i];
+        if (l[i] > m) {
+            m = l[i];
             first = i;
         }
     if (greedy) return first;
     float c[9], s = 0.0f;
     for (int i = 0; i < 9; ++i) {
-        s = s + exp_f32_host(out[i] - m);
+        s = s + exp_f32_host(l[i] - m);
         c[i] = s;
     }
-    const u32x4 x = philox4x32_10(u32x4{0u, env_id, rs, GCA_TAG_POLICY}, (uint32_t)policy_seed,
-                                  (uint32_t)(policy_seed >> 32));
-    const float t = ((float)(x.x >> 8) * 0x1.0p-24f) * c[8];
+    const float t = u01_f32_host(x) * c[8];
     for (int i = 0; i < 8; ++i)
         if (t < c[i]) return i;
     return 8;
+}
+
+// One env's outputs (out [10]: the logits and the value) and action: outputs, draw, sample.
+static int32_t policy_eval_host(const gca_heli_policy* p, int C, const uint8_t* loc, const float* coarse,
+                                uint32_t env_id, uint32_t rs, uint64_t policy_seed, int greedy, float* out) {
+    policy_outputs_host(p, 10, C, loc, coarse, out);
+    const u32x4 x = philox4x32_10(u32x4{0u, env_id, rs, GCA_TAG_POLICY}, (uint32_t)policy_seed,
+                                  (uint32_t)(policy_seed >> 32));
+    return policy_move_host(out, greedy, x.x);
 }
 
 static void policy_act_host(const gca_heli_policy* p, int C, const uint8_t* local, const float* coarse,
@@ -590,63 +605,23 @@ extern "C" int gca_helicopter_policy_rollout(int empty, int tree, int fire, int 
 }
 
 // ---------------------------------------------------------------- the bulldozer policy (gca.h "bulldozer policy")
-// One env's twelve outputs and its (move, shoot) in gca.h's order: the helicopter network with 12 outputs, two heads.
+// One env's twelve outputs and its (move, shoot): outputs, draw, sample -- the helicopter's move rule, then the shoot
+// head.
 static void bdz_policy_eval_host(const gca_bulldozer_policy* p, int C, const uint8_t* loc, const float* coarse,
                                  uint32_t step, uint32_t env_id, uint32_t ep, uint64_t policy_seed, int greedy,
                                  float* out, int32_t* act) {
-    const int S = 2 * p->radius + 1, SS = S * S, N = SS + C, Hd = p->hidden, G = 1024 / Hd;
-    float h[256];
-    for (int j = 0; j < Hd; ++j) {
-        float hj = p->b1[j];
-        for (int g = 0; g < G; ++g) {
-            float acc = 0.0f;
-            for (int n = g; n < N; n += G) {
-                if (n < SS) acc = acc + p->w_local[((size_t)n * 4 + (loc[n] & 3)) * Hd + j];
-                else acc = acc + p->w_coarse[(size_t)(n - SS) * Hd + j] * coarse[n - SS];
-            }
-            hj = hj + acc;
-        }
-        h[j] = hj > 0.0f ? hj : 0.0f;
-    }
-    for (int o = 0; o < 12; ++o) {
-        float q[16];
-        for (int r = 0; r < 16; ++r) {
-            float acc = 0.0f;
-            for (int j = r; j < Hd; j += 16) acc = acc + p->w_out[j * 12 + o] * h[j];
-            q[r] = acc;
-        }
-        for (int half = 8; half >= 1; half >>= 1)
-            for (int r = 0; r < half; ++r) q[r] = q[r] + q[r + half];
-        out[o] = p->b2[o] + q[0];
-    }
-    float m = out[0];
-    int32_t first = 0;
-    for (int i = 1; i < 9; ++i)
-        if (out[i] > m) {
-            m = out[i];
-            first = i;
-        }
+    policy_outputs_host(p, 12, C, loc, coarse, out);
+    const u32x4 x = philox4x32_10(u32x4{step, env_id, ep, GCA_TAG_BPOLICY}, (uint32_t)policy_seed,
+                                  (uint32_t)(policy_seed >> 32));
+    act[0] = policy_move_host(out, greedy, x.x);
     const float s0 = out[9], s1 = out[10];
     if (greedy) {
-        act[0] = first;
         act[1] = s1 > s0 ? 1 : 0;
         return;
     }
-    float c[9], s = 0.0f;
-    for (int i = 0; i < 9; ++i) {
-        s = s + exp_f32_host(out[i] - m);
-        c[i] = s;
-    }
-    const u32x4 x = philox4x32_10(u32x4{step, env_id, ep, GCA_TAG_BPOLICY}, (uint32_t)policy_seed,
-                                  (uint32_t)(policy_seed >> 32));
-    const float t = ((float)(x.x >> 8) * 0x1.0p-24f) * c[8];
-    int32_t mv = 8;
-    for (int i = 7; i >= 0; --i)
-        if (t < c[i]) mv = i;
-    act[0] = mv;
     const float ms = s1 > s0 ? s1 : s0;
     const float c0 = exp_f32_host(s0 - ms), c1 = c0 + exp_f32_host(s1 - ms);
-    act[1] = ((float)(x.y >> 8) * 0x1.0p-24f) * c1 < c0 ? 0 : 1;
+    act[1] = u01_f32_host(x.y) * c1 < c0 ? 0 : 1;
 }
 
 extern "C" int gca_bulldozer_policy_act(const gca_bulldozer_policy* p, int C, const uint8_t* local, const float* coarse,

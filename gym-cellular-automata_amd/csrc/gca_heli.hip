@@ -24,10 +24,10 @@
 // per step, no atomics, no `meet`. Grids whose planes do not fit in 64 KiB run K launches of the step kernel instead.
 //
 // gca_helicopter_policy_rollout: the same resident rollout with the agent inside (heli_rollout_body<true>): every step
-// takes its action from a small policy network evaluated on that step's observation (gca_heli_policy_dev.h), four more
+// takes its action from a small policy network evaluated on that step's observation (gca_policy_dev.h), four more
 // barriers per step; gca_helicopter_policy_act is that network alone, one workgroup per env, on a given observation.
 #include "gca_common.h"
-#include "gca_heli_policy_dev.h"
+#include "gca_policy_dev.h"
 
 namespace {
 
@@ -425,7 +425,7 @@ __device__ __forceinline__ void heli_r2g(uint8_t* __restrict__ g, int r, int d, 
 
 // ---- the policy of gca_helicopter_policy_rollout: the network and the (K, E, ...) records only that rollout has
 struct HeliPolArgs {
-    HeliPolicyW w;
+    PolicyW w;
     int radius, lgB, Hc, Wc;
     float inv;  // 1 / block^2
     float* logits_out;
@@ -435,7 +435,7 @@ struct HeliPolArgs {
 };
 
 // Step k's action of env e in the resident rollout: gca_policy_observation's window and coarse map taken from the
-// current LDS plane at the position BEFORE the move, then the network (heli_policy_eval, three barriers). The window's
+// current LDS plane at the position BEFORE the move, then the network (policy_outputs, three barriers). The window's
 // classes are read where they are needed and never staged; the coarse map goes to LDS (it is shared by all hidden
 // units). Rows -1 / H, the dword after a row and the columns >= W hold EMPTY, which is neither TREE nor FIRE, but the
 // loops below stay inside the grid's own rows and dwords anyway. Every thread returns the same action.
@@ -449,7 +449,7 @@ __device__ __forceinline__ int32_t heli_rollout_policy_act(const HeliRollArgs& a
     float* cs = reinterpret_cast<float*>(heli_lds + 2 * NP + 16);
     float* part = cs + ((q.w.C + 3) & ~3);
     float* hs = part + POL_PART;
-    float* outs = hs + POL_THREADS;
+    float* outs = hs + POL_VT;
     const size_t rec = (size_t)k * (size_t)a.E + (size_t)e;
     const uint32_t tree = Tp & 0xFFu, fire = Fp & 0xFFu;
     const int B = 1 << q.lgB, tiles = q.Hc * q.Wc;
@@ -497,10 +497,12 @@ __device__ __forceinline__ int32_t heli_rollout_policy_act(const HeliRollArgs& a
             o[n] = (uint8_t)class_at(n, wi, n - wi * q.w.S);
         }
     }
-    const int32_t act = heli_policy_eval(q.w, cs, part, hs, outs, tid, env_id, rs,
-                                         q.logits_out ? q.logits_out + rec * 9 : nullptr,
-                                         q.value_out ? q.value_out + rec : nullptr, class_at);
-    return __builtin_amdgcn_readfirstlane(act);
+    float o[HELI_POL_NOUT];
+    policy_outputs<HELI_POL_NOUT, POL_VT>(q.w, cs, part, hs, outs, tid, POL_VT,
+                                          q.logits_out ? q.logits_out + rec * 9 : nullptr,
+                                          q.value_out ? q.value_out + rec : nullptr, class_at, [] {}, o);
+    // lane i < 9 also holds l_i on its own
+    return __builtin_amdgcn_readfirstlane(heli_policy_sample(o, outs[min(tid & 63, 8)], q.w, env_id, rs));
 }
 
 // One workgroup (4 waves) per env, K steps. LDS: two planes of PD = D + 1 dwords per row, rows -1 .. H, one leading
@@ -718,15 +720,15 @@ __global__ __launch_bounds__(HELI_THREADS) void helicopter_rollout_kernel(HeliRo
     heli_rollout_body<false>(a, nullptr);
 }
 // gca_helicopter_policy_rollout's: the same steps, the action of each from the policy network (a.actions is not read).
-// LDS after the planes and the waves' words: heli_policy_lds_words(C) words of the network.
+// LDS after the planes and the waves' words: policy_lds_words(C) words of the network.
 __global__ __launch_bounds__(HELI_THREADS) void helicopter_policy_rollout_kernel(HeliRollArgs a, HeliPolArgs pa) {
     heli_rollout_body<true>(a, &pa);
 }
 
 // gca_helicopter_policy_act: one workgroup per env on the observation the caller hands over. A class above 3 (never
 // written by gca_policy_observation) is taken modulo 4, so no weight row outside w_local is ever read.
-__global__ __launch_bounds__(POL_THREADS) void helicopter_policy_act_kernel(
-    HeliPolicyW w, const uint8_t* __restrict__ local, const float* __restrict__ coarse,
+__global__ __launch_bounds__(POL_VT) void helicopter_policy_act_kernel(
+    PolicyW w, const uint8_t* __restrict__ local, const float* __restrict__ coarse,
     const uint32_t* __restrict__ rng_step, int env_offset, int32_t* __restrict__ action, float* __restrict__ logits,
     float* __restrict__ value) {
     extern __shared__ __attribute__((aligned(16))) uint32_t heli_lds[];
@@ -734,12 +736,15 @@ __global__ __launch_bounds__(POL_THREADS) void helicopter_policy_act_kernel(
     float* cs = reinterpret_cast<float*>(heli_lds);
     float* part = cs + ((w.C + 3) & ~3);
     float* hs = part + POL_PART;
-    float* outs = hs + POL_THREADS;
-    for (int c = tid; c < w.C; c += POL_THREADS) cs[c] = coarse[(size_t)e * (size_t)w.C + c];
+    float* outs = hs + POL_VT;
+    for (int c = tid; c < w.C; c += POL_VT) cs[c] = coarse[(size_t)e * (size_t)w.C + c];
     const uint8_t* __restrict__ loc = local + (size_t)e * (size_t)w.SS;
-    const int32_t act = heli_policy_eval(w, cs, part, hs, outs, tid, (uint32_t)(env_offset + e), rng_step[e],
-                                         logits ? logits + (size_t)e * 9 : nullptr, value ? value + e : nullptr,
-                                         [&](int n, int, int) -> uint32_t { return (uint32_t)loc[n] & 3u; });
+    float o[HELI_POL_NOUT];
+    policy_outputs<HELI_POL_NOUT, POL_VT>(
+        w, cs, part, hs, outs, tid, POL_VT, logits ? logits + (size_t)e * 9 : nullptr, value ? value + e : nullptr,
+        [&](int n, int, int) -> uint32_t { return (uint32_t)loc[n] & 3u; }, [] {}, o);
+    // lane i < 9 also holds l_i on its own
+    const int32_t act = heli_policy_sample(o, outs[min(tid & 63, 8)], w, (uint32_t)(env_offset + e), rng_step[e]);
     if (tid == 0) action[e] = act;
 }
 
@@ -844,38 +849,15 @@ extern "C" int gca_helicopter_rollout(int empty, int tree, int fire, int max_fre
 }
 
 // ---------------------------------------------------------------- the helicopter policy (gca.h "helicopter policy")
-namespace {
-
-// the largest coarse map the shared checks admit is the one whose network words fill a workgroup's 64 KiB of LDS
-static_assert(heli_policy_lds_words(GCA_POLICY_C_MAX) * 4 == 65536, "GCA_POLICY_C_MAX must follow heli_policy_lds_words");
-
-// The device's view of the weights of a checked policy, for gca_helicopter_policy_act and gca_helicopter_policy_rollout.
-int heli_policy_view(const gca_heli_policy* p, int C, uint64_t policy_seed, int greedy, HeliPolicyW* w) {
-    // the kernels' 16-B loads of the weights: the host build's loops take any alignment
-    GCA_CHECK_ARG(gca_policy_weights_aligned(p), "helicopter_policy: w_local and w_coarse must be 16-B aligned");
-    w->w_local = p->w_local; w->w_coarse = p->w_coarse; w->b1 = p->b1; w->w_out = p->w_out; w->b2 = p->b2;
-    w->S = 2 * p->radius + 1;
-    w->SS = w->S * w->S;
-    w->C = C;
-    w->Hd = p->hidden;
-    w->lgHd = 5;
-    while ((1 << w->lgHd) < p->hidden) ++w->lgHd;
-    w->greedy = greedy != 0;
-    w->k0 = (uint32_t)policy_seed;
-    w->k1 = (uint32_t)(policy_seed >> 32);
-    return GCA_OK;
-}
-
-}  // namespace
-
+// The network, its LDS words and the device's view of the weights are gca_policy_dev.h's.
 extern "C" int gca_helicopter_policy_act(const gca_heli_policy* p, int C, const uint8_t* local, const float* coarse,
                                          const uint32_t* rng_step, int env_offset, uint64_t policy_seed, int greedy,
                                          int32_t* action, float* logits, float* value, int E, void* stream) {
     if (const int st = gca_check_policy_act(p, C, local, coarse, rng_step, action, E)) return st;
-    HeliPolicyW w;
-    if (const int st = heli_policy_view(p, C, policy_seed, greedy, &w)) return st;
-    hipLaunchKernelGGL(helicopter_policy_act_kernel, dim3((unsigned)E), dim3(POL_THREADS),
-                       (size_t)heli_policy_lds_words(C) * 4, (hipStream_t)stream, w, local, coarse, rng_step,
+    PolicyW w;
+    if (const int st = policy_view(nullptr, p, C, policy_seed, greedy, &w)) return st;
+    hipLaunchKernelGGL(helicopter_policy_act_kernel, dim3((unsigned)E), dim3(POL_VT),
+                       (size_t)policy_lds_words(C) * 4, (hipStream_t)stream, w, local, coarse, rng_step,
                        env_offset, action, logits, value);
     GCA_CHECK_LAUNCH("helicopter_policy_act");
     return GCA_OK;
@@ -897,13 +879,13 @@ extern "C" int gca_helicopter_policy_rollout(int empty, int tree, int fire, int 
         return st;
     const int Hc = (H + p->block - 1) / p->block, Wc = (W + p->block - 1) / p->block, C = 2 * Hc * Wc;
     HeliPolArgs q;
-    if (const int st = heli_policy_view(p, C, policy_seed, greedy, &q.w)) return st;
+    if (const int st = policy_view(nullptr, p, C, policy_seed, greedy, &q.w)) return st;
     if (K == 0) return GCA_OK;
     const dim3 grid((unsigned)E);
     HeliRollArgs ra;
     size_t lds_bytes = 0;
     if (heli_roll_args(a, K, E, nullptr, action_out, reward_out, hit_out, &ra, &lds_bytes) &&
-        lds_bytes + (size_t)heli_policy_lds_words(C) * 4 <= 65536) {
+        lds_bytes + (size_t)policy_lds_words(C) * 4 <= 65536) {
         q.radius = p->radius;
         q.lgB = 0;
         while ((1 << q.lgB) < p->block) ++q.lgB;
@@ -911,7 +893,7 @@ extern "C" int gca_helicopter_policy_rollout(int empty, int tree, int fire, int 
         q.inv = 1.0f / (float)(p->block * p->block);
         q.logits_out = logits_out; q.value_out = value_out; q.local_out = local_out; q.coarse_out = coarse_out;
         hipLaunchKernelGGL(helicopter_policy_rollout_kernel, grid, dim3(HELI_THREADS),
-                           lds_bytes + (size_t)heli_policy_lds_words(C) * 4, (hipStream_t)stream, ra, q);
+                           lds_bytes + (size_t)policy_lds_words(C) * 4, (hipStream_t)stream, ra, q);
         GCA_CHECK_LAUNCH("helicopter_policy_rollout");
         return GCA_OK;
     }
@@ -935,7 +917,7 @@ extern "C" int gca_helicopter_policy_rollout(int empty, int tree, int fire, int 
         if (const int st = gca_policy_observation(buf0, buf1, parity, pos, E, H, W, empty, tree, fire, p->radius,
                                                   p->block, 0, loc_k, coa_k, stream))
             return st;
-        hipLaunchKernelGGL(helicopter_policy_act_kernel, grid, dim3(POL_THREADS), (size_t)heli_policy_lds_words(C) * 4,
+        hipLaunchKernelGGL(helicopter_policy_act_kernel, grid, dim3(POL_VT), (size_t)policy_lds_words(C) * 4,
                            (hipStream_t)stream, q.w, loc_k, coa_k, rng_step, env_offset, act_k,
                            logits_out ? logits_out + o * 9 : nullptr, value_out ? value_out + o : nullptr);
         GCA_CHECK_LAUNCH("helicopter_policy_rollout");

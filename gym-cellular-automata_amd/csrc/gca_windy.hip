@@ -20,7 +20,7 @@
 //    Reward/done counts of the new grid are fused (wave reduction + 3 atomics).
 #include "gca_common.h"
 #include "gca_reset_dev.h"  // the in-launch reset of the rollout kernel, wave_sum3
-#include "gca_bdz_policy_dev.h"  // the bulldozer policy network (the act kernel and the policy rollout)
+#include "gca_policy_dev.h"      // the policy network (the act kernel and the policy rollout)
 #include "gca_policy_obs_dev.h"  // the coarse map's rows-form strip (the policy rollout's recount)
 
 // windy_fast_kernel: row chunks in flight ahead of the one being computed (r01o: 2 / 4 / 8 measured slower than 1)
@@ -1292,23 +1292,25 @@ extern "C" int gca_bulldozer_rollout(const gca_bulldozer_params* p, const int32_
 // ------------------------------------------------------------------ the bulldozer policy (gca.h "bulldozer policy")
 // gca_bulldozer_policy_act: the network alone, one 256-thread workgroup per env on the observation the caller hands over.
 // A class above 3 (never written by gca_policy_observation) is taken modulo 4, so no weight row outside w_local is read.
-__global__ __launch_bounds__(BPOL_VT) void bulldozer_policy_act_kernel(
-    BdzPolicyW w, const uint8_t* __restrict__ local, const float* __restrict__ coarse,
+__global__ __launch_bounds__(POL_VT) void bulldozer_policy_act_kernel(
+    PolicyW w, const uint8_t* __restrict__ local, const float* __restrict__ coarse,
     const int64_t* __restrict__ steps_elapsed, const uint32_t* __restrict__ episode, int env_offset,
     int32_t* __restrict__ action, float* __restrict__ logits, float* __restrict__ value) {
     extern __shared__ __attribute__((aligned(16))) float bpol_lds[];
     const int e = blockIdx.x, tid = threadIdx.x;
     float* cs = bpol_lds;
     float* part = cs + ((w.C + 3) & ~3);
-    float* hs = part + BPOL_PART;
-    float* outs = hs + BPOL_VT;
-    for (int c = tid; c < w.C; c += BPOL_VT) cs[c] = coarse[(size_t)e * (size_t)w.C + c];
+    float* hs = part + POL_PART;
+    float* outs = hs + POL_VT;
+    for (int c = tid; c < w.C; c += POL_VT) cs[c] = coarse[(size_t)e * (size_t)w.C + c];
     const uint8_t* __restrict__ loc = local + (size_t)e * (size_t)w.SS;
+    float o[BDZ_POL_NOUT];
+    policy_outputs<BDZ_POL_NOUT, POL_VT>(
+        w, cs, part, hs, outs, tid, POL_VT, logits ? logits + (size_t)e * 11 : nullptr, value ? value + e : nullptr,
+        [&](int n, int, int) -> uint32_t { return (uint32_t)loc[n] & 3u; }, [] {}, o);
     int32_t move, shoot;
-    bdz_policy_eval(
-        w, cs, part, hs, outs, tid, BPOL_VT, (uint32_t)steps_elapsed[e], (uint32_t)(env_offset + e),
-        episode ? episode[e] : 0u, logits ? logits + (size_t)e * 11 : nullptr, value ? value + e : nullptr,
-        [&](int n, int, int) -> uint32_t { return (uint32_t)loc[n] & 3u; }, [] {}, move, shoot);
+    bdz_policy_sample(o, w, (uint32_t)steps_elapsed[e], (uint32_t)(env_offset + e), episode ? episode[e] : 0u, move,
+                      shoot);
     if (tid == 0) {
         action[2 * (size_t)e] = move;
         action[2 * (size_t)e + 1] = shoot;
@@ -1318,7 +1320,7 @@ __global__ __launch_bounds__(BPOL_VT) void bulldozer_policy_act_kernel(
 // gca_bulldozer_policy_rollout's resident form: bulldozer_rollout_random_kernel's march (the env's state in registers,
 // a wave per strip of the grid, the Windy CA by every wave when a step takes a pass, Move / Modify by thread 0, the
 // in-launch reset) with the agent inside: every step the workgroup evaluates the policy network on that step's
-// observation (gca_bdz_policy_dev.h) and takes the sampled (move, shoot). Its own kernel, so the existing rollout
+// observation (gca_policy_dev.h) and takes the sampled (move, shoot). Its own kernel, so the existing rollout
 // instantiations compile to what they were. Autoreset is a run-time, workgroup-uniform branch here (three instantiations
 // per width instead of six).
 //
@@ -1343,11 +1345,11 @@ __global__ __launch_bounds__(BPOL_VT) void bulldozer_policy_act_kernel(
 //   B  the end of this step's reads of cs and of the window: thread 0's Modify (after D) cannot touch what a slower
 //      wave still reads. The records of the observation (local_out, coarse_out) are stored between A and B for the same
 //      reason.
-//   C, D  the network's (gca_bdz_policy_dev.h, with the reuse argument for part / hs / outs).
+//   C, D  the network's (gca_policy_dev.h, with the reuse argument for part / hs / outs).
 // wave_cnt and bc are double-buffered exactly as in bulldozer_rollout_random_kernel; the barriers added here only
 // tighten that argument.
 struct BdzPolArgs {
-    BdzPolicyW w;
+    PolicyW w;
     int radius, lgB, HcWc, Wc;
     float inv;  // 1 / block^2
     int autoreset;
@@ -1370,8 +1372,8 @@ __global__ __launch_bounds__(1024) void bulldozer_policy_rollout_kernel(
     __shared__ int32_t bc[2][4];
     float* cs = bpol_lds;
     float* part = cs + ((q.w.C + 3) & ~3);
-    float* hs = part + BPOL_PART;
-    float* outs = hs + BPOL_VT;
+    float* hs = part + POL_PART;
+    float* outs = hs + POL_VT;
     const int e = blockIdx.x;
     const int tid = threadIdx.x, nt = (int)blockDim.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, nw = nt >> 6;
@@ -1434,10 +1436,12 @@ __global__ __launch_bounds__(1024) void bulldozer_policy_rollout_kernel(
                 for (int c = tid; c < (int)C; c += nt) co[c] = cs[c];
             }
         };
+        float o[BDZ_POL_NOUT];
+        policy_outputs<BDZ_POL_NOUT, 0>(q.w, cs, part, hs, outs, tid, nt,
+                                        q.logits_out ? q.logits_out + ke * 11 : nullptr,
+                                        q.value_out ? q.value_out + ke : nullptr, class_at, record, o);
         int32_t act0, act1;
-        bdz_policy_eval(q.w, cs, part, hs, outs, tid, nt, (uint32_t)se, env_id, ep,
-                        q.logits_out ? q.logits_out + ke * 11 : nullptr, q.value_out ? q.value_out + ke : nullptr,
-                        class_at, record, act0, act1);
+        bdz_policy_sample(o, q.w, (uint32_t)se, env_id, ep, act0, act1);
         // every thread sampled the same pair: as wave-uniform values they index t_move / t_shoot by scalar loads, as
         // the caller's actions do in bulldozer_rollout_random_kernel
         act0 = __builtin_amdgcn_readfirstlane(act0);
@@ -1636,42 +1640,17 @@ __global__ __launch_bounds__(256) void bulldozer_policy_record_kernel(
     }
 }
 
-namespace {
-
-// the largest coarse map the shared checks admit is the one whose network words fill a workgroup's 64 KiB of LDS
-static_assert(bdz_policy_lds_words(GCA_POLICY_C_MAX) * 4 == 65536, "GCA_POLICY_C_MAX must follow bdz_policy_lds_words");
 constexpr size_t BPOL_STATIC_LDS = 512;  // bulldozer_policy_rollout_kernel's own words (wave_cnt, bc), rounded up
-
-// The device's view of the weights of a checked policy.
-int bdz_policy_view(const char* who, const gca_bulldozer_policy* p, int C, uint64_t policy_seed, int greedy,
-                    BdzPolicyW* w) {
-    // the kernels' 16-B loads of the weights: the host build's loops take any alignment
-    if (!gca_bdz_policy_weights_aligned(p))
-        return gca_refuse(who, "policy.w_local and policy.w_coarse must be 16-B aligned");
-    w->w_local = p->w_local; w->w_coarse = p->w_coarse; w->b1 = p->b1; w->w_out = p->w_out; w->b2 = p->b2;
-    w->S = 2 * p->radius + 1;
-    w->SS = w->S * w->S;
-    w->C = C;
-    w->Hd = p->hidden;
-    w->lgHd = 5;
-    while ((1 << w->lgHd) < p->hidden) ++w->lgHd;
-    w->greedy = greedy != 0;
-    w->k0 = (uint32_t)policy_seed;
-    w->k1 = (uint32_t)(policy_seed >> 32);
-    return GCA_OK;
-}
-
-}  // namespace
 
 extern "C" int gca_bulldozer_policy_act(const gca_bulldozer_policy* p, int C, const uint8_t* local, const float* coarse,
                                         const int64_t* steps_elapsed, const uint32_t* episode, int env_offset,
                                         uint64_t policy_seed, int greedy, int32_t* action, float* logits, float* value,
                                         int E, void* stream) {
     if (const int st = gca_check_bdz_policy_act(p, C, local, coarse, steps_elapsed, action, E)) return st;
-    BdzPolicyW w;
-    if (const int st = bdz_policy_view("bulldozer_policy_act", p, C, policy_seed, greedy, &w)) return st;
-    hipLaunchKernelGGL(bulldozer_policy_act_kernel, dim3((unsigned)E), dim3(BPOL_VT),
-                       (size_t)bdz_policy_lds_words(C) * 4, (hipStream_t)stream, w, local, coarse, steps_elapsed,
+    PolicyW w;
+    if (const int st = policy_view("bulldozer_policy_act", p, C, policy_seed, greedy, &w)) return st;
+    hipLaunchKernelGGL(bulldozer_policy_act_kernel, dim3((unsigned)E), dim3(POL_VT),
+                       (size_t)policy_lds_words(C) * 4, (hipStream_t)stream, w, local, coarse, steps_elapsed,
                        episode, env_offset, action, logits, value);
     GCA_CHECK_LAUNCH("bulldozer_policy_act");
     return GCA_OK;
@@ -1707,8 +1686,8 @@ extern "C" int gca_bulldozer_policy_rollout(const gca_bulldozer_params* p, const
     // the act kernel's and the resident kernel's LDS: both paths hold the coarse map in a workgroup
     if (const int st = gca_check_policy_c(who, C)) return st;
     BdzPolArgs q;
-    if (const int st = bdz_policy_view(who, policy, C, policy_seed, greedy, &q.w)) return st;
-    const size_t lds_bytes = (size_t)bdz_policy_lds_words(C) * 4;
+    if (const int st = policy_view(who, policy, C, policy_seed, greedy, &q.w)) return st;
+    const size_t lds_bytes = (size_t)policy_lds_words(C) * 4;
     const bool resident = gca_policy_obs_rows_shape(H, W, B) && lds_bytes + BPOL_STATIC_LDS <= 65536;
     if (!resident && !(scratch || (action_out && local_out && coarse_out)))
         return gca_refuse(who, "this shape runs K x 3 launches and needs `scratch` for the records not kept");
@@ -1761,7 +1740,7 @@ extern "C" int gca_bulldozer_policy_rollout(const gca_bulldozer_params* p, const
         if (const int status = gca_policy_observation(buf0, buf1, parity, pos, E, H, W, p->empty, p->tree, p->fire,
                                                       policy->radius, B, 0, loc_k, coa_k, stream))
             return status;
-        hipLaunchKernelGGL(bulldozer_policy_act_kernel, dim3((unsigned)E), dim3(BPOL_VT), lds_bytes, st, q.w, loc_k,
+        hipLaunchKernelGGL(bulldozer_policy_act_kernel, dim3((unsigned)E), dim3(POL_VT), lds_bytes, st, q.w, loc_k,
                            coa_k, steps_elapsed, episode, (int)p->env_offset, act_k,
                            logits_out ? logits_out + o * 11 : nullptr, value_out ? value_out + o : nullptr);
         GCA_CHECK_LAUNCH(who);

@@ -171,8 +171,10 @@ class ObsParams(ctypes.Structure):
     ]
 
 
-class HeliPolicy(ctypes.Structure):
-    """gca_heli_policy (include/gca.h): the dims and the five weight arrays' device (host build: host) addresses."""
+class Policy(ctypes.Structure):
+    """gca_policy (include/gca.h), the struct of both agents' networks: the dims and the five weight arrays' device
+    (host build: host) addresses. w_out is [hidden][10] and b2 [10] for the helicopter, [hidden][12] and [12] for the
+    bulldozer."""
 
     _fields_ = [
         ("radius", c_int32),
@@ -187,14 +189,8 @@ class HeliPolicy(ctypes.Structure):
     ]
 
 
+HeliPolicy = BulldozerPolicyStruct = Policy  # gca_heli_policy and gca_bulldozer_policy are typedefs of gca_policy
 TAG_BPOLICY = 0x42504F4C
-
-
-class BulldozerPolicyStruct(ctypes.Structure):
-    """gca_bulldozer_policy (include/gca.h): the dims and the five weight arrays' device (host build: host) addresses;
-    w_out is [hidden][12], b2 [12]."""
-
-    _fields_ = list(HeliPolicy._fields_)
 
 
 GCA_ADAM_MAX_TENSORS = 8

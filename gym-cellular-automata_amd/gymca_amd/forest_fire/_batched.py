@@ -134,6 +134,86 @@ class BatchedEnvBase:
             return torch.empty(shape, dtype=dtype, device=self.device)
         return check_tensor(t, dtype, shape, self._dev_index, who, what)
 
+    # ------------------------------------------------------------------ the policy inside the env's launches
+    # A subclass names its policy class in `_POLICY_CLASS` and its records in `_POLICY_RECORDS` / _policy_spec(), and
+    # keeps the dict `_policy_calls`, emptied by rebind().
+    _POLICY_CLASS = None
+    _POLICY_RECORDS = ()
+    _POLICY_CALLS_MAX = 8
+
+    def _check_policy(self, policy, who):
+        if not isinstance(policy, self._POLICY_CLASS):
+            raise ValueError(f"{who}: policy must be a {self._POLICY_CLASS.__name__}")
+        if policy.shape != (self.nrows, self.ncols):
+            raise ValueError(f"{who}: the policy was built for a {policy.shape} grid, the env is "
+                             f"{(self.nrows, self.ncols)}")
+        if policy.device != self.device:
+            raise ValueError(f"{who}: the policy lives on {policy.device}, the env on {self.device}")
+        return policy
+
+    def _policy_call(self, kind, policy, make):
+        """The pre-bound call of `kind` for this policy; bound again when a policy tensor was replaced (its version
+        moved) or the env rebound. The entry keeps the policy, its tensors of that version and the call's scratch alive,
+        so the cache is bounded: beyond _POLICY_CALLS_MAX entries the one bound longest ago is dropped (a trainer that
+        builds policy after policy against one env does not keep them all; a dropped policy is simply bound again). A
+        graph captured from a call replays that entry's addresses: whoever holds such a graph keeps the number of
+        policies in use on this env within the bound, or captures again."""
+        key = (kind, id(policy))
+        calls = self._policy_calls
+        pc = calls.get(key)
+        if pc is None or pc[0] != policy.version or pc[1] is not policy:
+            calls.pop(key, None)
+            while len(calls) >= self._POLICY_CALLS_MAX:
+                del calls[next(iter(calls))]
+            pc = (policy.version, policy) + tuple(make())
+        else:
+            del calls[key]  # least recently used first: a hit moves the entry to the end
+        calls[key] = pc
+        return pc
+
+    def _act_inputs(self, policy, local, coarse, action_shape, n_logits, action_out, logits_out, value_out):
+        """act()'s checks up to its launch: (policy, local, coarse, action_out, logits_out, value_out), the observation
+        taken here unless both `local` and `coarse` are given, the three outputs the caller's or allocated."""
+        import torch
+
+        from . import policy_obs
+
+        policy = self._check_policy(policy, "act")
+        E = self.num_envs
+        ls, cs = policy_obs.output_shapes(self, policy.radius, policy.block)
+        if (local is None) != (coarse is None):
+            raise ValueError("act: give both local and coarse, or neither")
+        if local is None:
+            local, coarse = self.observe(policy.radius, policy.block)
+        else:
+            check_tensor(local, torch.uint8, ls, self._dev_index, "act", "local")
+            check_tensor(coarse, torch.float32, cs, self._dev_index, "act", "coarse")
+        action_out = self._out(action_out, torch.int32, action_shape, "act", "action_out")
+        logits_out = self._out(logits_out, torch.float32, (E, n_logits), "act", "logits_out")
+        value_out = self._out(value_out, torch.float32, (E,), "act", "value_out")
+        return policy, local, coarse, action_out, logits_out, value_out
+
+    def _policy_records(self, policy, K, record, given):
+        """rollout_policy()'s checks up to its launch: (policy, K, recs), recs the dict of the records named in
+        `record` and of every record whose output tensor is `given`, the caller's or allocated. _policy_spec(K, ls, cs)
+        is the subclass's table of each record's (dtype, shape)."""
+        from . import policy_obs
+
+        policy = self._check_policy(policy, "rollout_policy")
+        K = int(K)
+        if K < 0:
+            raise ValueError("rollout_policy: K >= 0")
+        spec = self._policy_spec(K, *policy_obs.output_shapes(self, policy.radius, policy.block))
+        unknown = [r for r in record if r not in spec]
+        if unknown:
+            raise ValueError(f"rollout_policy: unknown records {unknown}; choose from {self._POLICY_RECORDS}")
+        recs = {}
+        for name in self._POLICY_RECORDS:
+            dtype, shape = spec[name]
+            if given[name] is not None or name in record:
+                recs[name] = self._out(given[name], dtype, shape, "rollout_policy", f"{name}_out")
+        return policy, K, recs
+
     def _check_positions(self, positions):
         """positions as an int32 (E, 2) array of cells inside the grid, else ValueError."""
         E, H, W = self.num_envs, self.nrows, self.ncols

@@ -34,6 +34,7 @@ from ..._lib import SLOT, BoundCall, call
 from .._batched import BatchedEnvBase, check_tensor, rollout_actions, seed64
 from ..operators.move_modify import make_params
 from .bulldozer import ACTION_SETS, DEFAULT_WIND, bulldozer_timings, parse_wind
+from .policy import BulldozerPolicy
 
 
 class BatchedForestFireBulldozerEnv(BatchedEnvBase):
@@ -43,6 +44,7 @@ class BatchedForestFireBulldozerEnv(BatchedEnvBase):
                               "reward", "wind", "steps_elapsed", "params", "_meet", "_act_buf", "episode",
                               "last_episode_length", "_terminated", "_truncated_u8"})
     _BOUND_READY = "_fused_call"
+    _POLICY_CLASS = BulldozerPolicy
 
     def _check_replacement(self, name, old, value):
         # the two bound attributes that are no tensor: params keeps its type, _meet may be switched off
@@ -398,40 +400,6 @@ class BatchedForestFireBulldozerEnv(BatchedEnvBase):
         return reward_out, terminated_out, truncated_out
 
     # ------------------------------------------------------------------ the policy inside the env's launches
-    def _check_policy(self, policy, who):
-        from .policy import BulldozerPolicy
-
-        if not isinstance(policy, BulldozerPolicy):
-            raise ValueError(f"{who}: policy must be a BulldozerPolicy")
-        if policy.shape != (self.nrows, self.ncols):
-            raise ValueError(f"{who}: the policy was built for a {policy.shape} grid, the env is "
-                             f"{(self.nrows, self.ncols)}")
-        if policy.device != self.device:
-            raise ValueError(f"{who}: the policy lives on {policy.device}, the env on {self.device}")
-        return policy
-
-    def _policy_call(self, kind, policy, make):
-        """The pre-bound call of `kind` for this policy; bound again when a policy tensor was replaced (its version
-        moved) or the env rebound. The entry keeps the policy, its tensors of that version and the call's scratch alive,
-        so the cache is bounded: beyond _POLICY_CALLS_MAX entries the one bound longest ago is dropped (a trainer that
-        builds policy after policy against one env does not keep them all; a dropped policy is simply bound again). A
-        graph captured from a call replays that entry's addresses: whoever holds such a graph keeps the number of
-        policies in use on this env within the bound, or captures again."""
-        key = (kind, id(policy))
-        calls = self._policy_calls
-        pc = calls.get(key)
-        if pc is None or pc[0] != policy.version or pc[1] is not policy:
-            calls.pop(key, None)
-            while len(calls) >= self._POLICY_CALLS_MAX:
-                del calls[next(iter(calls))]
-            pc = (policy.version, policy) + tuple(make())
-        else:
-            del calls[key]  # least recently used first: a hit moves the entry to the end
-        calls[key] = pc
-        return pc
-
-    _POLICY_CALLS_MAX = 8
-
     def act(self, policy, local=None, coarse=None, seed=0, greedy=False, action_out=None, logits_out=None,
             value_out=None):
         """The policy's (move, shoot) for every env: observe(policy.radius, policy.block) unless both `local` and
@@ -440,23 +408,9 @@ class BatchedForestFireBulldozerEnv(BatchedEnvBase):
         logits, value float32 (E,)), written into the given outputs or allocated. The draw is keyed by (seed, global env
         id, the env's steps_elapsed and episode); greedy=True takes the first maximum of each head instead. No env state
         changes, so the value of the state after a rollout (the bootstrap) is free of side effects. No sync."""
-        import torch
-
-        from .. import policy_obs
-
-        policy = self._check_policy(policy, "act")
         E = self.num_envs
-        ls, cs = policy_obs.output_shapes(self, policy.radius, policy.block)
-        if (local is None) != (coarse is None):
-            raise ValueError("act: give both local and coarse, or neither")
-        if local is None:
-            local, coarse = self.observe(policy.radius, policy.block)
-        else:
-            check_tensor(local, torch.uint8, ls, self._dev_index, "act", "local")
-            check_tensor(coarse, torch.float32, cs, self._dev_index, "act", "coarse")
-        action_out = self._out(action_out, torch.int32, (E, 2), "act", "action_out")
-        logits_out = self._out(logits_out, torch.float32, (E, 11), "act", "logits_out")
-        value_out = self._out(value_out, torch.float32, (E,), "act", "value_out")
+        policy, local, coarse, action_out, logits_out, value_out = self._act_inputs(
+            policy, local, coarse, (E, 2), 11, action_out, logits_out, value_out)
         pc = self._policy_call("act", policy, lambda: (BoundCall(
             "gca_bulldozer_policy_act", policy.struct, policy.C, SLOT, SLOT, dev.ptr(self.steps_elapsed),
             dev.ptr(self.episode), self.env_offset, SLOT, SLOT, SLOT, SLOT, SLOT, E, SLOT,
@@ -466,6 +420,15 @@ class BatchedForestFireBulldozerEnv(BatchedEnvBase):
         return action_out, logits_out, value_out
 
     _POLICY_RECORDS = ("action", "logits", "value", "reward", "terminated", "truncated", "local", "coarse")
+
+    def _policy_spec(self, K, ls, cs):
+        import torch
+
+        E = self.num_envs
+        return {"action": (torch.int32, (K, E, 2)), "logits": (torch.float32, (K, E, 11)),
+                "value": (torch.float32, (K, E)), "reward": (torch.float64, (K, E)),
+                "terminated": (torch.uint8, (K, E)), "truncated": (torch.uint8, (K, E)),
+                "local": (torch.uint8, (K,) + ls), "coarse": (torch.float32, (K,) + cs)}
 
     def rollout_policy(self, policy, K, seed=0, greedy=False, record=_POLICY_RECORDS, action_out=None,
                        logits_out=None, value_out=None, reward_out=None, terminated_out=None, truncated_out=None,
@@ -485,28 +448,10 @@ class BatchedForestFireBulldozerEnv(BatchedEnvBase):
         copies into the records. No sync, and with every record given no allocation: capturable."""
         import torch
 
-        from .. import policy_obs
-
-        policy = self._check_policy(policy, "rollout_policy")
-        K = int(K)
-        if K < 0:
-            raise ValueError("rollout_policy: K >= 0")
         E = self.num_envs
-        ls, cs = policy_obs.output_shapes(self, policy.radius, policy.block)
-        spec = {"action": (torch.int32, (K, E, 2)), "logits": (torch.float32, (K, E, 11)),
-                "value": (torch.float32, (K, E)), "reward": (torch.float64, (K, E)),
-                "terminated": (torch.uint8, (K, E)), "truncated": (torch.uint8, (K, E)),
-                "local": (torch.uint8, (K,) + ls), "coarse": (torch.float32, (K,) + cs)}
-        unknown = [r for r in record if r not in spec]
-        if unknown:
-            raise ValueError(f"rollout_policy: unknown records {unknown}; choose from {self._POLICY_RECORDS}")
-        given = {"action": action_out, "logits": logits_out, "value": value_out, "reward": reward_out,
-                 "terminated": terminated_out, "truncated": truncated_out, "local": local_out, "coarse": coarse_out}
-        recs = {}
-        for name in self._POLICY_RECORDS:
-            dtype, shape = spec[name]
-            if given[name] is not None or name in record:
-                recs[name] = self._out(given[name], dtype, shape, "rollout_policy", f"{name}_out")
+        policy, K, recs = self._policy_records(policy, K, record, {
+            "action": action_out, "logits": logits_out, "value": value_out, "reward": reward_out,
+            "terminated": terminated_out, "truncated": truncated_out, "local": local_out, "coarse": coarse_out})
         if K == 0:
             return recs
         if not self.fused:

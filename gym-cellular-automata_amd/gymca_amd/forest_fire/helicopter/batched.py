@@ -16,9 +16,9 @@ import numpy as np
 
 from ... import _device as dev
 from ..._lib import SLOT, BoundCall, call
-from .. import policy_obs
 from .._batched import BatchedEnvBase, check_tensor, rollout_actions, seed64
 from ..operators.ca_DrosselSchwabl import choice_threshold
+from .policy import HelicopterPolicy
 
 
 class BatchedForestFireHelicopterEnv(BatchedEnvBase):
@@ -27,6 +27,7 @@ class BatchedForestFireHelicopterEnv(BatchedEnvBase):
     _BOUND_STATE = frozenset({"buf", "parity", "freeze", "pos", "counts", "rng_step", "hit", "reward", "steps_elapsed",
                               "thresholds", "_meet", "_act_buf", "_act2"})
     _BOUND_READY = "_step_call"
+    _POLICY_CLASS = HelicopterPolicy
 
     def __init__(self, num_envs, nrows, ncols, device=None, seed=0, env_offset=0, speed=0.5, freeze=None,
                  p_fire=0.033, p_tree=0.333, materialize_obs=True):
@@ -225,27 +226,6 @@ class BatchedForestFireHelicopterEnv(BatchedEnvBase):
         return reward_out, hit_out
 
     # ------------------------------------------------------------------ the policy inside the env's launches
-    def _check_policy(self, policy, who):
-        from .policy import HelicopterPolicy
-
-        if not isinstance(policy, HelicopterPolicy):
-            raise ValueError(f"{who}: policy must be a HelicopterPolicy")
-        if policy.shape != (self.nrows, self.ncols):
-            raise ValueError(f"{who}: the policy was built for a {policy.shape} grid, the env is "
-                             f"{(self.nrows, self.ncols)}")
-        if policy.device != self.device:
-            raise ValueError(f"{who}: the policy lives on {policy.device}, the env on {self.device}")
-        return policy
-
-    def _policy_call(self, kind, policy, make):
-        """The pre-bound call of `kind` for this policy; bound again when a policy tensor was replaced (its version
-        moved) or the env rebound. The entry keeps the policy's tensors of that version alive."""
-        key = (kind, id(policy))
-        pc = self._policy_calls.get(key)
-        if pc is None or pc[0] != policy.version or pc[1] is not policy:
-            pc = self._policy_calls[key] = (policy.version, policy) + tuple(make())
-        return pc
-
     def act(self, policy, local=None, coarse=None, seed=0, greedy=False, action_out=None, logits_out=None,
             value_out=None):
         """The policy's action for every env: observe(policy.radius, policy.block) unless both `local` and `coarse` are
@@ -253,21 +233,9 @@ class BatchedForestFireHelicopterEnv(BatchedEnvBase):
         Returns (action int32 (E,), logits float32 (E, 9), value float32 (E,)), written into the given outputs or
         allocated. The draw is keyed by (seed, global env id, the env's rng_step); greedy=True takes the first maximum
         instead. No env state changes, so the value of the state after a rollout is free of side effects. No sync."""
-        import torch
-
-        policy = self._check_policy(policy, "act")
         E = self.num_envs
-        ls, cs = policy_obs.output_shapes(self, policy.radius, policy.block)
-        if (local is None) != (coarse is None):
-            raise ValueError("act: give both local and coarse, or neither")
-        if local is None:
-            local, coarse = self.observe(policy.radius, policy.block)
-        else:
-            check_tensor(local, torch.uint8, ls, self._dev_index, "act", "local")
-            check_tensor(coarse, torch.float32, cs, self._dev_index, "act", "coarse")
-        action_out = self._out(action_out, torch.int32, (E,), "act", "action_out")
-        logits_out = self._out(logits_out, torch.float32, (E, 9), "act", "logits_out")
-        value_out = self._out(value_out, torch.float32, (E,), "act", "value_out")
+        policy, local, coarse, action_out, logits_out, value_out = self._act_inputs(
+            policy, local, coarse, (E,), 9, action_out, logits_out, value_out)
         pc = self._policy_call("act", policy, lambda: (BoundCall(
             "gca_helicopter_policy_act", policy.struct, policy.C, SLOT, SLOT, dev.ptr(self.rng_step), self.env_offset,
             SLOT, SLOT, SLOT, SLOT, SLOT, E, SLOT, keep=(self.rng_step,) + policy.tensors()),))
@@ -276,6 +244,14 @@ class BatchedForestFireHelicopterEnv(BatchedEnvBase):
         return action_out, logits_out, value_out
 
     _POLICY_RECORDS = ("action", "logits", "value", "reward", "hit", "local", "coarse")
+
+    def _policy_spec(self, K, ls, cs):
+        import torch
+
+        E = self.num_envs
+        return {"action": (torch.int32, (K, E)), "logits": (torch.float32, (K, E, 9)),
+                "value": (torch.float32, (K, E)), "reward": (torch.float64, (K, E)), "hit": (torch.uint8, (K, E)),
+                "local": (torch.uint8, (K,) + ls), "coarse": (torch.float32, (K,) + cs)}
 
     def rollout_policy(self, policy, K, seed=0, greedy=False, record=_POLICY_RECORDS, action_out=None,
                        logits_out=None, value_out=None, reward_out=None, hit_out=None, local_out=None,
@@ -291,25 +267,10 @@ class BatchedForestFireHelicopterEnv(BatchedEnvBase):
         run 3 K launches with the same results; no sync either way."""
         import torch
 
-        policy = self._check_policy(policy, "rollout_policy")
-        K = int(K)
-        if K < 0:
-            raise ValueError("rollout_policy: K >= 0")
         E = self.num_envs
-        ls, cs = policy_obs.output_shapes(self, policy.radius, policy.block)
-        spec = {"action": (torch.int32, (K, E)), "logits": (torch.float32, (K, E, 9)),
-                "value": (torch.float32, (K, E)), "reward": (torch.float64, (K, E)), "hit": (torch.uint8, (K, E)),
-                "local": (torch.uint8, (K,) + ls), "coarse": (torch.float32, (K,) + cs)}
-        unknown = [r for r in record if r not in spec]
-        if unknown:
-            raise ValueError(f"rollout_policy: unknown records {unknown}; choose from {self._POLICY_RECORDS}")
-        given = {"action": action_out, "logits": logits_out, "value": value_out, "reward": reward_out, "hit": hit_out,
-                 "local": local_out, "coarse": coarse_out}
-        recs = {}
-        for name in self._POLICY_RECORDS:
-            dtype, shape = spec[name]
-            if given[name] is not None or name in record:
-                recs[name] = self._out(given[name], dtype, shape, "rollout_policy", f"{name}_out")
+        policy, K, recs = self._policy_records(policy, K, record, {
+            "action": action_out, "logits": logits_out, "value": value_out, "reward": reward_out, "hit": hit_out,
+            "local": local_out, "coarse": coarse_out})
         if K == 0:
             return recs
 

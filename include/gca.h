@@ -622,22 +622,25 @@ int gca_policy_observation(const uint8_t* buf0, const uint8_t* buf1, const uint8
  *            DESIGN.md), c_i = c_{i-1} + p_i for i = 0..8 (c_{-1} = 0.0f), u = u01_f32(x.x) of Philox((0, env_offset +
  *            e, rng_step[e], GCA_TAG_POLICY), policy_seed); the action is the first i with u * c_8 < c_i, else 8.
  *            Non-finite weights still give an action in [0, 8]; nothing else is promised for them.
- * The order depends on (S, C, Hd) only: never on E, K, the launch shape or the path that runs. The device (one 256-thread
- * workgroup per env: a thread owns four consecutive units, Hd / 4 threads a weight row, which leaves the G groups; 16
- * lanes per output meet in an xor butterfly), the host build and the numpy restatement
+ * The order depends on (S, C, Hd) only: never on E, K, the launch shape or the path that runs. The device (one workgroup
+ * per env runs policy_outputs of csrc/gca_policy_dev.h, the one implementation both agents share: a thread owns four
+ * consecutive units, Hd / 4 threads a weight row, which leaves the G groups; 16 lanes per output meet in an xor
+ * butterfly), the host build (policy_outputs_host, gca_cpu.cpp) and the numpy restatement
  * tests/_helicopter_policy_ref.py all follow it, so they agree bit for bit.
  * Layouts: w_local f32 [S*S][4][Hd] and w_coarse f32 [C][Hd] (both 16-B aligned on the device), b1 f32 [Hd], w_out
- * f32 [Hd][10], b2 f32 [10] (device arrays; the struct itself is a host struct read at call time). */
+ * f32 [Hd][10], b2 f32 [10] (device arrays; the struct itself is a host struct read at call time). gca_policy is the
+ * struct of both agents' networks (the bulldozer's w_out and b2 have twelve columns). */
 typedef struct {
     int32_t radius, block;     /* gca_policy_observation's: radius in [0, 31], block a power of two in [1, 64] */
-    int32_t hidden;            /* Hd                                                                            */
+    int32_t hidden;            /* Hd, a power of two in [32, 256]                                               */
     int32_t reserved;          /* 0                                                                             */
     const float* w_local;
     const float* w_coarse;
     const float* b1;
     const float* w_out;
     const float* b2;
-} gca_heli_policy;
+} gca_policy;
+typedef gca_policy gca_heli_policy;
 
 /* The policy's action for E envs on a given observation, ONE launch (a workgroup per env), no allocation, no sync:
  * capturable. local u8 [E][S][S] and coarse f32 [E][C] as gca_policy_observation writes them (C = 2 Hc Wc is given; the
@@ -686,21 +689,13 @@ int gca_helicopter_policy_rollout(int empty, int tree, int fire, int max_freeze,
  *   greedy   != 0: the index of the first maximum of each head, nothing drawn.
  * Non-finite weights still give a move in [0, 8] and a shoot in {0, 1}; nothing else is promised for them.
  * The order depends on (S, C, Hd) only: never on E, K, the number of waves of the launch or the path that runs. The
- * device (the helicopter layout's 256 float4 "virtual threads" looped over the workgroup's real threads, so any wave
- * count gives the same sums), the host build and tests/_bulldozer_policy_ref.py follow it and agree bit for bit.
+ * device (the same policy_outputs of csrc/gca_policy_dev.h with twelve outputs: its 256 float4 "virtual threads" are
+ * looped over the workgroup's real threads, so any wave count gives the same sums), the host build (the same
+ * policy_outputs_host) and tests/_bulldozer_policy_ref.py follow it and agree bit for bit.
  * Layouts: w_local f32 [S*S][4][Hd] and w_coarse f32 [C][Hd] (16-B aligned on the device), b1 f32 [Hd], w_out f32
  * [Hd][12], b2 f32 [12] (device arrays; the struct itself is a host struct read at call time). */
 #define GCA_TAG_BPOLICY 0x42504F4Cu /* 'BPOL' : the bulldozer policy's draw (word 0 move, word 1 shoot) */
-typedef struct {
-    int32_t radius, block;     /* gca_policy_observation's: radius in [0, 31], block a power of two in [1, 64] */
-    int32_t hidden;            /* Hd, a power of two in [32, 256]                                               */
-    int32_t reserved;          /* 0                                                                             */
-    const float* w_local;
-    const float* w_coarse;
-    const float* b1;
-    const float* w_out;
-    const float* b2;
-} gca_bulldozer_policy;
+typedef gca_policy gca_bulldozer_policy;
 
 /* The policy's action for E envs on a given observation, ONE launch (a workgroup per env), no allocation, no sync:
  * capturable. local u8 [E][S][S] and coarse f32 [E][C] as gca_policy_observation writes them (C = 2 Hc Wc even, at most

@@ -32,6 +32,45 @@ def make_weights(d, seed=0, scale=1.0, head=1.0):
             "b2": f((N_OUT,), 0.5 * head)}
 
 
+def weights_from_helicopter(wh, seed=0):
+    """Bulldozer weights that share a helicopter network's trunk: the hidden layer as it is, the nine logit columns of
+    w_out / b2 in columns 0..8, the value column in column 11, and arbitrary shoot columns 9..10."""
+    rng = np.random.default_rng(seed)
+    Hd = wh["w_out"].shape[0]
+    w_out = rng.standard_normal((Hd, N_OUT)).astype(np.float32)
+    b2 = rng.standard_normal(N_OUT).astype(np.float32)
+    w_out[:, :9], w_out[:, 11] = wh["w_out"][:, :9], wh["w_out"][:, 9]
+    b2[:9], b2[11] = wh["b2"][:9], wh["b2"][9]
+    return {"w_local": wh["w_local"], "w_coarse": wh["w_coarse"], "b1": wh["b1"], "w_out": w_out, "b2": b2}
+
+
+# the two ends of the helicopter's and the bulldozer's SHAPES in one: the smallest and the largest network on grids
+# both agents' kernels take
+TRUNK_SHAPES = [(0, 8, 32, 32, 256), (31, 32, 256, 64, 256)]
+
+
+def trunk_case(shape, E=3):
+    """(d, helicopter weights, bulldozer weights sharing their trunk, local, coarse) for the tests that hold the two
+    agents' act entry points against each other."""
+    import _policy_obs_ref as obs
+
+    r, B, Hd, H, W = shape
+    d = dims(*shape)
+    wh = href.make_weights(d, seed=Hd, head=2.0)
+    buf, parity, _ = obs.make_case(E, H, W, B)
+    local, coarse = obs.host_observe(buf, parity, obs.positions(E, H, W), obs.CODES, r, B)
+    return d, wh, weights_from_helicopter(wh, seed=Hd + 1), local, coarse
+
+
+def assert_same_trunk(heli, bdz):
+    """heli = (action (E,), logits (E, 9), value (E,)), bdz = (action (E, 2), logits (E, 11), value (E,)), host arrays."""
+    bits = lambda a: np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+    assert np.array_equal(bits(heli[1]), bits(bdz[1][:, :9])), "the nine logits"
+    assert np.array_equal(bits(heli[2]), bits(bdz[2])), "the value"
+    assert np.array_equal(heli[0], bdz[0][:, 0]), "the move"
+    assert np.isfinite(heli[1]).all() and len(np.unique(bits(heli[1]))) > heli[1].shape[0]  # nothing left unwritten
+
+
 def outputs_ref(w, d, local, coarse):
     """(E, 12) float32: nine move logits, two shoot logits, the value; every multiply and add rounded on its own, in the
     header's order. Also returns the pre-activations."""

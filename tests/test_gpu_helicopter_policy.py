@@ -5,6 +5,7 @@ tensor and every record, bit for bit."""
 import numpy as np
 import pytest
 
+import _bulldozer_policy_ref as bref
 import _helicopter_policy_ref as pref
 import _helicopter_ref as href
 import _policy_obs_ref as obs
@@ -310,3 +311,59 @@ def test_rollout_policy_validation(device):
     rec = env.rollout_policy(pol, 0)
     assert tuple(rec["logits"].shape) == (0, E, 9) and tuple(rec["local"].shape) == (0, E, 3, 3)
     href.assert_states_equal(_state(env), before, "K = 0")
+
+
+def test_the_cache_of_bound_policy_calls_is_bounded(device):
+    """Many policies against one env do not all stay alive, and one that was dropped is bound again and acts as before."""
+    import torch
+
+    from gymca_amd.forest_fire.helicopter import HelicopterPolicy
+
+    E, H, W = 2, 5, 7
+    env = _env(device, pref.grids(E, H, W, seed=2), 1)
+    d = pref.dims(1, 4, 32, H, W)
+    pol = _policy(device, d, pref.make_weights(d))
+    lo, co = env.observe(1, 4)   # the rollouts below move the env on: the logits are compared on this observation
+    _, l0, _ = env.act(pol, lo, co, seed=1)
+    for i in range(env._POLICY_CALLS_MAX + 3):
+        env.act(HelicopterPolicy(env, 1, 4, 32, seed=i), seed=1)
+        env.rollout_policy(HelicopterPolicy(env, 1, 4, 32, seed=100 + i), 1, record=())
+    assert len(env._policy_calls) <= env._POLICY_CALLS_MAX
+    assert all(pc[1] is not pol for pc in env._policy_calls.values())
+    _, l1, _ = env.act(pol, lo, co, seed=1)
+    assert torch.equal(l1, l0)
+
+
+@pytest.mark.parametrize("shape", bref.TRUNK_SHAPES)
+def test_device_trunk_is_one_for_both_agents(device, shape):
+    """gca_helicopter_policy_act and gca_bulldozer_policy_act on weights that share the trunk: the same nine logits,
+    value and move, bit for bit (both kernels run policy_outputs of gca_policy_dev.h), and both equal the host build."""
+    import torch
+
+    from gymca_amd import _device as dev
+    from gymca_amd import _lib
+
+    d, wh, wb, local, coarse = bref.trunk_case(shape)
+    E = local.shape[0]
+    up = lambda a: torch.as_tensor(np.ascontiguousarray(a), device=device)
+    d_local, d_coarse = up(local), up(coarse)
+    d_rs, d_se = up(np.arange(E, dtype=np.int32)), up(np.arange(E, dtype=np.int64))
+    got = []
+    for w, name, n_act, n_log, key in ((wh, "gca_helicopter_policy_act", 1, 9, (dev.ptr(d_rs),)),
+                                       (wb, "gca_bulldozer_policy_act", 2, 11, (dev.ptr(d_se), None))):
+        dw = {k: up(v) for k, v in w.items()}
+        s = _lib.Policy()
+        s.radius, s.block, s.hidden = d["radius"], d["block"], d["hidden"]
+        for k, t in dw.items():
+            setattr(s, k, t.data_ptr())
+        action = torch.full((E, n_act), -7, dtype=torch.int32, device=device)
+        logits = torch.full((E, n_log), 5.5, dtype=torch.float32, device=device)
+        value = torch.full((E,), 5.5, dtype=torch.float32, device=device)
+        _lib.call(name, s, d["C"], dev.ptr(d_local), dev.ptr(d_coarse), *key, 0, 0, 1, dev.ptr(action), dev.ptr(logits),
+                  dev.ptr(value), E, dev.stream_ptr(device))
+        torch.cuda.synchronize(device)
+        got.append((action.cpu().numpy(), logits.cpu().numpy(), value.cpu().numpy()))
+    heli, bdz = (got[0][0][:, 0],) + got[0][1:], got[1]
+    bref.assert_same_trunk(heli, bdz)
+    want = pref.host_act(wh, d, local, coarse, np.arange(E, dtype=np.uint32), greedy=True)
+    bref.assert_same_trunk(want, bdz)
