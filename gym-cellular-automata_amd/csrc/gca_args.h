@@ -2,8 +2,9 @@
 // (gca_cpu.cpp) both export: one check function per entry point, or per group of checks that several share, holding
 // every refusal that does not depend on the build. Both builds call them first, so both refuse the same arguments
 // with the same words in the same order. What only one build can know (LDS fit, workgroup counts, plane alignment,
-// `scratch`, memset failures on the device; the idx scan and the walk's cap on the host) stays in that build, after
-// the shared call. Plain C++, no device code, like the two plan headers.
+// `scratch`, memset failures on the device; the walk's cap on the host) stays in that build, after the shared call;
+// the idx scan of the policy_grad entry points, which only the host build can make, is here for its two callers.
+// Plain C++, no device code, like the two plan headers.
 #pragma once
 #include <stdint.h>
 
@@ -218,12 +219,26 @@ static inline int gca_check_gae(const void* reward, const void* value, const voi
     return GCA_OK;
 }
 
+// The agent of a gca_*_policy_grad call: what heads its refusals, which policy check speaks, and the network's outputs
+// (the logits of its heads and the value; ppo_plan's NOUT). The checks below are the two agents' alike.
+struct GcaGradAgent {
+    const char* who;       // heads every refusal of the call
+    const char* who_ws;    // heads the workspace query's refusal
+    const char* short_ws;  // the refusal of a short workspace, which names the query
+    bool bdz;              // the policy check: gca_check_bdz_policy's texts, else gca_check_policy's
+    int nout;
+};
+constexpr GcaGradAgent GCA_GRAD_HELI{"helicopter_policy_grad", "helicopter_policy_grad_workspace",
+                                     "workspace smaller than gca_helicopter_policy_grad_workspace", false, 10};
+constexpr GcaGradAgent GCA_GRAD_BDZ{"bulldozer_policy_grad", "bulldozer_policy_grad_workspace",
+                                    "workspace smaller than gca_bulldozer_policy_grad_workspace", true, 12};
+
 // a workspace query answers -1 where this refuses
-static inline int gca_check_policy_grad_workspace(const gca_heli_policy* p, int C, int N) {
-    GCA_CHECK_ARG(p && p->radius >= 0 && p->radius <= 31 && p->hidden >= 32 && p->hidden <= 256 &&
-                      (p->hidden & (p->hidden - 1)) == 0 && C >= 2 && C % 2 == 0 && C <= GCA_POLICY_C_MAX && N >= 1,
-                  "helicopter_policy_grad_workspace: radius in [0, 31], hidden a power of two in [32, 256], "
-                  "C = 2 Hc Wc at most 15088, N >= 1");
+static inline int gca_check_policy_grad_workspace(const GcaGradAgent& a, const gca_policy* p, int C, int N) {
+    if (!(p && p->radius >= 0 && p->radius <= 31 && p->hidden >= 32 && p->hidden <= 256 &&
+          (p->hidden & (p->hidden - 1)) == 0 && C >= 2 && C % 2 == 0 && C <= GCA_POLICY_C_MAX && N >= 1))
+        return gca_refuse(a.who_ws, "radius in [0, 31], hidden a power of two in [32, 256], "
+                                    "C = 2 Hc Wc at most 15088, N >= 1");
     return GCA_OK;
 }
 
@@ -234,36 +249,43 @@ static inline bool gca_overlap(const void* a, int64_t na, const void* b, int64_t
 
 // *pl: the plan of the checked call. The alignment is the device's requirement, and the host build keeps it so that
 // a workspace or a policy moves between the builds as it is.
-static inline int gca_check_policy_grad(const gca_heli_policy* p, int C, const void* local, const void* coarse,
-                                        const void* action, const void* old_logits, const void* advantage,
-                                        const void* returns, int64_t T, const void* idx, int N, float clip_coef,
-                                        const void* g_w_local, const void* g_w_coarse, const void* g_b1,
-                                        const void* g_w_out, const void* g_b2, const void* stats,
+static inline int gca_check_policy_grad(const GcaGradAgent& a, const gca_policy* p, int C, const void* local,
+                                        const void* coarse, const void* action, const void* old_logits,
+                                        const void* advantage, const void* returns, int64_t T, const void* idx, int N,
+                                        float clip_coef, const void* g_w_local, const void* g_w_coarse,
+                                        const void* g_b1, const void* g_w_out, const void* g_b2, const void* stats,
                                         const void* workspace, int64_t workspace_bytes, PpoPlan* pl) {
-    if (const int st = gca_check_policy(p)) return st;
-    GCA_CHECK_ARG(local && coarse && action && old_logits && advantage && returns,
-                  "helicopter_policy_grad: null record");
-    GCA_CHECK_ARG(g_w_local && g_w_coarse && g_b1 && g_w_out && g_b2 && stats && workspace,
-                  "helicopter_policy_grad: null output or workspace");
-    if (const int st = gca_check_policy_c("helicopter_policy_grad", C)) return st;
-    GCA_CHECK_ARG(T >= 1 && T < (1ll << 31), "helicopter_policy_grad: 1 <= T < 2^31");
-    GCA_CHECK_ARG(N >= 1, "helicopter_policy_grad: N >= 1");
-    GCA_CHECK_ARG(idx || N <= T, "helicopter_policy_grad: N <= T without idx");
-    GCA_CHECK_ARG(clip_coef >= 0.0f, "helicopter_policy_grad: clip_coef >= 0");
+    if (const int st = a.bdz ? gca_check_bdz_policy(a.who, p) : gca_check_policy(p)) return st;
+    if (!(local && coarse && action && old_logits && advantage && returns)) return gca_refuse(a.who, "null record");
+    if (!(g_w_local && g_w_coarse && g_b1 && g_w_out && g_b2 && stats && workspace))
+        return gca_refuse(a.who, "null output or workspace");
+    if (const int st = gca_check_policy_c(a.who, C)) return st;
+    if (!(T >= 1 && T < (1ll << 31))) return gca_refuse(a.who, "1 <= T < 2^31");
+    if (!(N >= 1)) return gca_refuse(a.who, "N >= 1");
+    if (!(idx || N <= T)) return gca_refuse(a.who, "N <= T without idx");
+    if (!(clip_coef >= 0.0f)) return gca_refuse(a.who, "clip_coef >= 0");
     const int S = 2 * p->radius + 1, Hd = p->hidden;
-    *pl = ppo_plan(S * S, C, Hd, N);
-    GCA_CHECK_ARG(workspace_bytes >= pl->bytes,
-                  "helicopter_policy_grad: workspace smaller than gca_helicopter_policy_grad_workspace");
-    GCA_CHECK_ARG(gca_policy_weights_aligned(p) && (((uintptr_t)workspace | (uintptr_t)p->b1) & 15u) == 0,
-                  "helicopter_policy_grad: workspace, w_local, w_coarse and b1 16-B aligned");
+    *pl = ppo_plan(S * S, C, Hd, N, a.nout);
+    if (!(workspace_bytes >= pl->bytes)) return gca_refuse(a.who, a.short_ws);
+    if (!(gca_policy_weights_aligned(p) && (((uintptr_t)workspace | (uintptr_t)p->b1) & 15u) == 0))
+        return gca_refuse(a.who, "workspace, w_local, w_coarse and b1 16-B aligned");
+    const int64_t wo = (int64_t)Hd * a.nout * 4, b2 = a.nout * 4ll;
     const void* ptrs[11] = {g_w_local, g_w_coarse, g_b1, g_w_out, g_b2, stats,
                             p->w_local, p->w_coarse, p->b1, p->w_out, p->b2};
-    const int64_t sizes[11] = {pl->off_wc * 4, (int64_t)C * Hd * 4, Hd * 4ll, Hd * 40ll, 40, 32,
-                               pl->off_wc * 4, (int64_t)C * Hd * 4, Hd * 4ll, Hd * 40ll, 40};
+    const int64_t sizes[11] = {pl->off_wc * 4, (int64_t)C * Hd * 4, Hd * 4ll, wo, b2, 32,
+                               pl->off_wc * 4, (int64_t)C * Hd * 4, Hd * 4ll, wo, b2};
     for (int i = 0; i < 6; ++i)
         for (int j = i + 1; j < 11; ++j)
-            GCA_CHECK_ARG(!gca_overlap(ptrs[i], sizes[i], ptrs[j], sizes[j]),
-                          "helicopter_policy_grad: the outputs may alias neither each other nor the weights");
+            if (gca_overlap(ptrs[i], sizes[i], ptrs[j], sizes[j]))
+                return gca_refuse(a.who, "the outputs may alias neither each other nor the weights");
+    return GCA_OK;
+}
+
+// the host build alone can read idx (host memory there) before it indexes with it
+static inline int gca_check_policy_grad_idx(const GcaGradAgent& a, const int32_t* idx, int N, int64_t T) {
+    if (idx)
+        for (int t = 0; t < N; ++t)
+            if (!(idx[t] >= 0 && idx[t] < T)) return gca_refuse(a.who, "idx outside [0, T)");
     return GCA_OK;
 }
 

@@ -20,14 +20,15 @@
 //                     (gca_heli.hip, gca_policy_dev.h), in gca.h's summation order
 //   gca_bulldozer_policy_act  the bulldozer policy network alone (gca_policy_dev.h), in gca.h's summation order;
 //                     gca_bulldozer_policy_rollout needs the Windy CA and is in the device build only
-//   gca_gae / gca_helicopter_policy_grad(_workspace)  the PPO update (gca_ppo.hip): the GAE recurrence bit for bit, the
-//                     loss gradient in double as a second yardstick
+//   gca_gae / gca_helicopter_policy_grad(_workspace) / gca_bulldozer_policy_grad(_workspace)  the PPO update
+//                     (gca_ppo.hip): the GAE recurrence bit for bit, the loss gradient of either head layout in double
+//                     as a second yardstick
 //   gca_adam_step(_workspace) / gca_permutation  the optimizer and the minibatch shuffle (gca_opt.hip), bit for bit
 //   gca_philox        Random123 Philox4x32-10 (KAT hook)
 //
 // Arguments: every entry point first calls its check function of gca_args.h, the same one the device build calls, so
 // both builds refuse the same arguments with the same words. The only checks written here are the two that the host
-// alone can make (the idx scan of gca_helicopter_policy_grad, the permutation walk's cap) and the rollout's coarse-map
+// alone can make (the idx scan of the two policy_grad entry points, the permutation walk's cap) and the rollout's coarse-map
 // limit, which the host applies for every K; each says so where it stands.
 #include <math.h>
 #include <stdarg.h>
@@ -663,37 +664,44 @@ extern "C" int gca_gae(const double* reward, const float* value, const float* ne
     return GCA_OK;
 }
 
-extern "C" int64_t gca_helicopter_policy_grad_workspace(const gca_heli_policy* p, int C, int N) {
-    if (gca_check_policy_grad_workspace(p, C, N)) return -1;
+static int64_t policy_grad_workspace_host(const GcaGradAgent& ag, const gca_policy* p, int C, int N) {
+    if (gca_check_policy_grad_workspace(ag, p, C, N)) return -1;
     const int S = 2 * p->radius + 1;
-    return ppo_plan(S * S, C, p->hidden, N).bytes;
+    return ppo_plan(S * S, C, p->hidden, N, ag.nout).bytes;
 }
 
-static double lse9_host(const double* l) {
+extern "C" int64_t gca_helicopter_policy_grad_workspace(const gca_heli_policy* p, int C, int N) {
+    return policy_grad_workspace_host(GCA_GRAD_HELI, p, C, N);
+}
+
+extern "C" int64_t gca_bulldozer_policy_grad_workspace(const gca_bulldozer_policy* p, int C, int N) {
+    return policy_grad_workspace_host(GCA_GRAD_BDZ, p, C, N);
+}
+
+static double lse_host(const double* l, int n) {
     double m = l[0];
-    for (int i = 1; i < 9; ++i) m = l[i] > m ? l[i] : m;
+    for (int i = 1; i < n; ++i) m = l[i] > m ? l[i] : m;
     double s = 0.0;
-    for (int i = 0; i < 9; ++i) s += exp(l[i] - m);
+    for (int i = 0; i < n; ++i) s += exp(l[i] - m);
     return m + log(s);
 }
 
-// Plain loops: the network, the loss and every gradient sum in double, rounded to f32 once. The workspace is checked
-// as on the device and not used.
-extern "C" int gca_helicopter_policy_grad(const gca_heli_policy* p, int C, const uint8_t* local, const float* coarse,
-                                          const int32_t* action, const float* old_logits, const float* advantage,
-                                          const float* returns, int64_t T, const int32_t* idx, int N, float clip_coef,
-                                          float ent_coef, float vf_coef, int norm_adv, float* g_w_local,
-                                          float* g_w_coarse, float* g_b1, float* g_w_out, float* g_b2, float* stats,
-                                          void* workspace, int64_t workspace_bytes, void*) {
+// Both agents' gradient in plain loops over the head layout (nh heads of heads[h] logits, then the value): the network,
+// the per-head loss of gca.h and every gradient sum in double, rounded to f32 once. The workspace is checked as on the
+// device and not used.
+static int policy_grad_host(const GcaGradAgent& ag, int nh, const int* heads, const gca_policy* p, int C,
+                            const uint8_t* local, const float* coarse, const int32_t* action, const float* old_logits,
+                            const float* advantage, const float* returns, int64_t T, const int32_t* idx, int N,
+                            float clip_coef, float ent_coef, float vf_coef, int norm_adv, float* g_w_local,
+                            float* g_w_coarse, float* g_b1, float* g_w_out, float* g_b2, float* stats, void* workspace,
+                            int64_t workspace_bytes) {
     PpoPlan pl;
-    if (const int st = gca_check_policy_grad(p, C, local, coarse, action, old_logits, advantage, returns, T, idx, N,
+    if (const int st = gca_check_policy_grad(ag, p, C, local, coarse, action, old_logits, advantage, returns, T, idx, N,
                                              clip_coef, g_w_local, g_w_coarse, g_b1, g_w_out, g_b2, stats, workspace,
                                              workspace_bytes, &pl))
         return st;
-    const int S = 2 * p->radius + 1, SS = S * S, Hd = p->hidden;
-    // idx is host memory here, so the host build alone can read it before it indexes with it
-    if (idx)
-        for (int t = 0; t < N; ++t) GCA_CHECK_ARG(idx[t] >= 0 && idx[t] < T, "helicopter_policy_grad: idx outside [0, T)");
+    if (const int st = gca_check_policy_grad_idx(ag, idx, N, T)) return st;
+    const int S = 2 * p->radius + 1, SS = S * S, Hd = p->hidden, NO = ag.nout, NL = NO - 1;
     auto row_of = [&](int t) { return idx ? (size_t)idx[t] : (size_t)t; };
     double mean = 0.0, var = 0.0;
     for (int t = 0; t < N; ++t) mean += advantage[row_of(t)];
@@ -702,10 +710,10 @@ extern "C" int gca_helicopter_policy_grad(const gca_heli_policy* p, int C, const
         const double d = advantage[row_of(t)] - mean;
         var += d * d;
     }
-    const double sd = sqrt(var / N), inv_n = 1.0 / N;
-    std::vector<double> gwl((size_t)SS * 4 * Hd, 0.0), gwc((size_t)C * Hd, 0.0), gb1(Hd, 0.0), gwo((size_t)Hd * 10, 0.0);
-    std::vector<double> a(Hd), h(Hd), da(Hd);
-    double gb2[10] = {0}, st[5] = {0};
+    const double sd = sqrt(var / N), inv_n = 1.0 / N, inv_nh = 1.0 / ((double)N * nh);
+    std::vector<double> gwl((size_t)SS * 4 * Hd, 0.0), gwc((size_t)C * Hd, 0.0), gb1(Hd, 0.0), gwo((size_t)Hd * NO, 0.0);
+    std::vector<double> a(Hd), h(Hd), da(Hd), out(NO), d(NO), gb2(NO, 0.0), lo(NL), pr(NL), lp(NL);
+    double st[5] = {0};
     for (int t = 0; t < N; ++t) {
         const size_t row = row_of(t);
         const uint8_t* loc = local + row * SS;
@@ -720,43 +728,48 @@ extern "C" int gca_helicopter_policy_grad(const gca_heli_policy* p, int C, const
             const double x = co[c];
             for (int j = 0; j < Hd; ++j) a[j] += w[j] * x;
         }
-        double out[10], lo[9], d[10];
-        for (int o = 0; o < 10; ++o) out[o] = p->b2[o];
+        for (int o = 0; o < NO; ++o) out[o] = p->b2[o];
         for (int j = 0; j < Hd; ++j) {
             h[j] = a[j] > 0.0 ? a[j] : 0.0;
-            for (int o = 0; o < 10; ++o) out[o] += (double)p->w_out[j * 10 + o] * h[j];
+            for (int o = 0; o < NO; ++o) out[o] += (double)p->w_out[j * NO + o] * h[j];
         }
-        for (int i = 0; i < 9; ++i) lo[i] = old_logits[row * 9 + i];
-        const int act = action[row] < 0 ? 0 : (action[row] > 8 ? 8 : action[row]);
-        const double lse = lse9_host(out), lse_old = lse9_host(lo);
-        const double logratio = (out[act] - lse) - (lo[act] - lse_old), ratio = exp(logratio);
         double adv = advantage[row];
         if (norm_adv) adv = (adv - mean) / (sd + 1e-8);
         const double lo_c = 1.0 - (double)clip_coef, hi_c = 1.0 + (double)clip_coef;
-        const bool clipped = ratio < lo_c || ratio > hi_c;
-        const double pg1 = -adv * ratio, pg2 = -adv * (ratio < lo_c ? lo_c : (ratio > hi_c ? hi_c : ratio));
-        const double dpg_dr = (!clipped || pg1 > pg2) ? -adv : 0.0;
-        double pr[9], lp[9], ent = 0.0;
-        for (int i = 0; i < 9; ++i) {
-            lp[i] = out[i] - lse;
-            pr[i] = exp(lp[i]);
-            ent -= pr[i] * lp[i];
+        for (int hd = 0, off = 0; hd < nh; off += heads[hd], ++hd) {
+            const int n = heads[hd];
+            const double* l = out.data() + off;
+            for (int i = 0; i < n; ++i) lo[i] = old_logits[row * NL + off + i];
+            const int32_t ar = action[row * nh + hd];
+            const int act = ar < 0 ? 0 : (ar > n - 1 ? n - 1 : ar);
+            const double lse = lse_host(l, n), lse_old = lse_host(lo.data(), n);
+            const double logratio = (l[act] - lse) - (lo[act] - lse_old), ratio = exp(logratio);
+            const bool clipped = ratio < lo_c || ratio > hi_c;
+            const double pg1 = -adv * ratio, pg2 = -adv * (ratio < lo_c ? lo_c : (ratio > hi_c ? hi_c : ratio));
+            const double dpg_dr = (!clipped || pg1 > pg2) ? -adv : 0.0;
+            double ent = 0.0;
+            for (int i = 0; i < n; ++i) {
+                lp[i] = l[i] - lse;
+                pr[i] = exp(lp[i]);
+                ent -= pr[i] * lp[i];
+            }
+            for (int i = 0; i < n; ++i)
+                d[off + i] = (dpg_dr * ratio * ((i == act ? 1.0 : 0.0) - pr[i]) +
+                              (double)ent_coef * pr[i] * (lp[i] + ent)) * inv_nh;
+            st[0] += pg1 > pg2 ? pg1 : pg2;
+            st[2] += ent;
+            st[3] += (ratio - 1.0) - logratio;
+            st[4] += clipped ? 1.0 : 0.0;
         }
-        for (int i = 0; i < 9; ++i)
-            d[i] = (dpg_dr * ratio * ((i == act ? 1.0 : 0.0) - pr[i]) + (double)ent_coef * pr[i] * (lp[i] + ent)) * inv_n;
-        const double dv = out[9] - returns[row];
-        d[9] = (double)vf_coef * dv * inv_n;
-        st[0] += pg1 > pg2 ? pg1 : pg2;
+        const double dv = out[NL] - returns[row];
+        d[NL] = (double)vf_coef * dv * inv_n;
         st[1] += 0.5 * dv * dv;
-        st[2] += ent;
-        st[3] += (ratio - 1.0) - logratio;
-        st[4] += clipped ? 1.0 : 0.0;
-        for (int o = 0; o < 10; ++o) gb2[o] += d[o];
+        for (int o = 0; o < NO; ++o) gb2[o] += d[o];
         for (int j = 0; j < Hd; ++j) {
             double dh = 0.0;
-            for (int o = 0; o < 10; ++o) {
-                gwo[(size_t)j * 10 + o] += h[j] * d[o];
-                dh += (double)p->w_out[j * 10 + o] * d[o];
+            for (int o = 0; o < NO; ++o) {
+                gwo[(size_t)j * NO + o] += h[j] * d[o];
+                dh += (double)p->w_out[j * NO + o] * d[o];
             }
             da[j] = a[j] > 0.0 ? dh : 0.0;
             gb1[j] += da[j];
@@ -775,17 +788,41 @@ extern "C" int gca_helicopter_policy_grad(const gca_heli_policy* p, int C, const
     for (size_t i = 0; i < gwc.size(); ++i) g_w_coarse[i] = (float)gwc[i];
     for (int j = 0; j < Hd; ++j) g_b1[j] = (float)gb1[j];
     for (size_t i = 0; i < gwo.size(); ++i) g_w_out[i] = (float)gwo[i];
-    for (int o = 0; o < 10; ++o) g_b2[o] = (float)gb2[o];
-    const double pg = st[0] * inv_n, vl = st[1] * inv_n, en = st[2] * inv_n;
+    for (int o = 0; o < NO; ++o) g_b2[o] = (float)gb2[o];
+    const double pg = st[0] * inv_nh, vl = st[1] * inv_n, en = st[2] * inv_nh;
     stats[0] = (float)(pg - (double)ent_coef * en + (double)vf_coef * vl);
     stats[1] = (float)pg;
     stats[2] = (float)vl;
     stats[3] = (float)en;
-    stats[4] = (float)(st[3] * inv_n);
-    stats[5] = (float)(st[4] * inv_n);
+    stats[4] = (float)(st[3] * inv_nh);
+    stats[5] = (float)(st[4] * inv_nh);
     stats[6] = (float)mean;
     stats[7] = (float)sd;
     return GCA_OK;
+}
+
+extern "C" int gca_helicopter_policy_grad(const gca_heli_policy* p, int C, const uint8_t* local, const float* coarse,
+                                          const int32_t* action, const float* old_logits, const float* advantage,
+                                          const float* returns, int64_t T, const int32_t* idx, int N, float clip_coef,
+                                          float ent_coef, float vf_coef, int norm_adv, float* g_w_local,
+                                          float* g_w_coarse, float* g_b1, float* g_w_out, float* g_b2, float* stats,
+                                          void* workspace, int64_t workspace_bytes, void*) {
+    const int heads[1] = {9};
+    return policy_grad_host(GCA_GRAD_HELI, 1, heads, p, C, local, coarse, action, old_logits, advantage, returns, T, idx,
+                            N, clip_coef, ent_coef, vf_coef, norm_adv, g_w_local, g_w_coarse, g_b1, g_w_out, g_b2, stats,
+                            workspace, workspace_bytes);
+}
+
+extern "C" int gca_bulldozer_policy_grad(const gca_bulldozer_policy* p, int C, const uint8_t* local,
+                                         const float* coarse, const int32_t* action, const float* old_logits,
+                                         const float* advantage, const float* returns, int64_t T, const int32_t* idx,
+                                         int N, float clip_coef, float ent_coef, float vf_coef, int norm_adv,
+                                         float* g_w_local, float* g_w_coarse, float* g_b1, float* g_w_out, float* g_b2,
+                                         float* stats, void* workspace, int64_t workspace_bytes, void*) {
+    const int heads[2] = {9, 2};
+    return policy_grad_host(GCA_GRAD_BDZ, 2, heads, p, C, local, coarse, action, old_logits, advantage, returns, T, idx,
+                            N, clip_coef, ent_coef, vf_coef, norm_adv, g_w_local, g_w_coarse, g_b1, g_w_out, g_b2, stats,
+                            workspace, workspace_bytes);
 }
 
 // ---------------------------------------------------------------- the optimizer (gca.h "optimizer")

@@ -1,16 +1,18 @@
-// gca_ppo.hip — the learner's side of the helicopter policy (include/gca.h "PPO update"): gca_gae, the reference's
-// generalised advantage estimate in one launch, and gca_helicopter_policy_grad, the PPO clipped-surrogate loss, its
-// statistics and its gradient with respect to the five policy tensors over a minibatch of rollout_policy's records.
+// gca_ppo.hip — the learner's side of the two policies (include/gca.h "PPO update"): gca_gae, the reference's
+// generalised advantage estimate in one launch, and gca_helicopter_policy_grad / gca_bulldozer_policy_grad, the PPO
+// clipped-surrogate loss (per head), its statistics and its gradient with respect to the five policy tensors over a
+// minibatch of rollout_policy's records. The kernels are written over a compile-time head layout PpoHeads<N0, N1>:
+// (9) for the helicopter, NOUT = 10 outputs; (9, 2) for the bulldozer, NOUT = 12; the value is column NOUT - 1.
 //
-// gca_helicopter_policy_grad is four launches on the caller's stream, all sums in a fixed order (no atomics):
+// A policy_grad call is four launches on the caller's stream, all sums in a fixed order (no atomics):
 //   adv     one workgroup: mean and population standard deviation of the minibatch's advantages (two passes, a
 //           sequential partial per thread, a tree over the threads) -> workspace header.
 //   fwd     one workgroup per tile of TS samples (64; 32 at Hd = 256). The tile's hidden layer is a tiled matvec: a
 //           thread owns four consecutive units of SPT samples; w_local goes through LDS in chunks of 1024 / Hd cells
 //           (16 KiB) with the chunk's class bytes, w_coarse in chunks of 32 rows with the tile's coarse values, so a
-//           weight row is loaded from L2 once per tile, not once per sample. Then relu -> LDS, the ten outputs (a
+//           weight row is loaded from L2 once per tile, not once per sample. Then relu -> LDS, the NOUT outputs (a
 //           thread per (sample, output), sixteen running sums over j mod 16 and a tree), the loss of each sample in one
-//           thread, d loss / d outputs, and d loss / d pre-activations. Writes da (N, Hd), h (N, Hd) and dout (N, 10) to the workspace
+//           thread, d loss / d outputs, and d loss / d pre-activations. Writes da (N, Hd), h (N, Hd) and dout (N, NOUT) to the workspace
 //           and the tile's statistics and b2 gradient sums (a pairwise tree over the tile's samples).
 //   wgrad   G[r][j] = sum_s x[s][r] * D[s][j]: grid (row blocks, P sample splits). A thread owns one row r and four
 //           units: for a window cell the four class vectors (x the one-hot class: a select per class, so a class no
@@ -63,8 +65,8 @@ extern "C" int gca_gae(const double* reward, const float* value, const float* ne
 struct PpoBatch {
     const uint8_t* __restrict__ local;      // [T][SS]
     const float* __restrict__ coarse;       // [T][C]
-    const int32_t* __restrict__ action;     // [T]
-    const float* __restrict__ old_logits;   // [T][9]
+    const int32_t* __restrict__ action;     // [T][NH]
+    const float* __restrict__ old_logits;   // [T][NL]
     const float* __restrict__ advantage;    // [T]
     const float* __restrict__ returns;      // [T]
     const int32_t* __restrict__ idx;        // [N] or null
@@ -129,38 +131,99 @@ struct PpoLossArgs {
     int norm_adv;
 };
 
+// The head layout: N0 logits of the first head, N1 of the second (0: one head), then the value.
+template <int N0_, int N1_>
+struct PpoHeads {
+    static constexpr int N0 = N0_, N1 = N1_;
+    static constexpr int NH = N1 > 0 ? 2 : 1;  // heads
+    static constexpr int NL = N0 + N1;         // logits = the width of a record's old_logits
+    static constexpr int NOUT = NL + 1;        // outputs (ppo_plan's NOUT)
+    static constexpr int OST = NOUT + 1;       // row stride of a tile's outputs in LDS
+    static constexpr int TP = ppo_tp(NOUT);    // floats of a tile partial
+    static constexpr int WO = (NOUT + 3) & ~3;  // floats after w_out in LDS: b2, rounded up to four
+};
+
 // The loss of ONE sample is a chain of scalar operations in one thread with two cancellations (logp_new - logp_old,
 // and the mean of pg under normalised advantages, whose terms nearly cancel): it runs in double and is rounded to f32
 // once per term. Every sum over samples, units or inputs is f32.
-// logsumexp of nine logits: the maximum, the sum of exp(l_i - max) left to right, max + log(sum)
-__device__ __forceinline__ double ppo_lse9(const double (&l)[9]) {
+// logsumexp of a head's N logits: the maximum, the sum of exp(l_i - max) left to right, max + log(sum)
+template <int N>
+__device__ __forceinline__ double ppo_lse(const double (&l)[N]) {
     double m = l[0];
 #pragma unroll
-    for (int i = 1; i < 9; ++i) m = fmax(m, l[i]);
+    for (int i = 1; i < N; ++i) m = fmax(m, l[i]);
     double s = 0.0;
 #pragma unroll
-    for (int i = 0; i < 9; ++i) s = s + exp(l[i] - m);
+    for (int i = 0; i < N; ++i) s = s + exp(l[i] - m);
     return m + log(s);
 }
 
-__device__ __forceinline__ double ppo_pick9(const double (&l)[9], int a) {
+template <int N>
+__device__ __forceinline__ double ppo_pick(const double (&l)[N], int a) {
     double v = l[0];
 #pragma unroll
-    for (int i = 1; i < 9; ++i) v = (a == i) ? l[i] : v;
+    for (int i = 1; i < N; ++i) v = (a == i) ? l[i] : v;
     return v;
 }
 
-template <int HD>
+// One head of one sample (include/gca.h) on record row `row`: outs its N logits of this call, old the recorded ones, a
+// its action (clamped here); A^ is formed here, from the same values for every head. Writes d loss / d l to d[0..N)
+// and returns the head's terms of the four statistics sums.
+struct PpoHeadTerms {
+    double pg, ent, kl;
+    float clipped;
+};
+
+template <int N>
+__device__ __forceinline__ PpoHeadTerms ppo_head(const PpoBatch& b, int row, const float* __restrict__ hdr,
+                                                 const float* outs, const float* __restrict__ old, int a,
+                                                 const PpoLossArgs& la, double inv_nh, float* d) {
+    double l[N], lo[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        l[i] = (double)outs[i];
+        lo[i] = (double)old[i];
+    }
+    a = min(max(a, 0), N - 1);
+    const double lse = ppo_lse<N>(l), lse_old = ppo_lse<N>(lo);
+    const double logratio = (ppo_pick<N>(l, a) - lse) - (ppo_pick<N>(lo, a) - lse_old);
+    const double ratio = exp(logratio);
+    double adv = (double)b.advantage[row];
+    if (la.norm_adv) adv = (adv - (double)hdr[0]) / ((double)hdr[1] + 1e-8);
+    const double lo_c = 1.0 - (double)la.clip_coef, hi_c = 1.0 + (double)la.clip_coef;
+    const bool clipped = ratio < lo_c || ratio > hi_c;
+    const double pg1 = -adv * ratio, pg2 = -adv * fmin(fmax(ratio, lo_c), hi_c);
+    const double dpg_dr = (!clipped || pg1 > pg2) ? -adv : 0.0;
+    double p[N], lp[N], ent = 0.0;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        lp[i] = l[i] - lse;
+        p[i] = exp(lp[i]);
+        ent = ent - p[i] * lp[i];
+    }
+    const double g = dpg_dr * ratio;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        const double onehot = (a == i) ? 1.0 : 0.0;
+        d[i] = (float)((g * (onehot - p[i]) + (double)la.ent_coef * (p[i] * (lp[i] + ent))) * inv_nh);
+    }
+    return PpoHeadTerms{fmax(pg1, pg2), ent, (ratio - 1.0) - logratio, clipped ? 1.0f : 0.0f};
+}
+
+template <int HD, class HL>
 __global__ __launch_bounds__(PPO_THREADS) void ppo_fwd_kernel(
     PpoBatch b, const float* __restrict__ w_local, const float* __restrict__ w_coarse, const float* __restrict__ b1,
     const float* __restrict__ w_out, const float* __restrict__ b2, PpoLossArgs la, const float* __restrict__ hdr,
     float* __restrict__ DA, float* __restrict__ H, float* __restrict__ DO, float* __restrict__ TP) {
     using Cf = PpoCfg<HD>;
     constexpr int TS = Cf::TS, Q = Cf::Q, R = Cf::R, SPT = Cf::SPT, CH = Cf::CH, CC = Cf::CC;
+    constexpr int NOUT = HL::NOUT, NL = HL::NL, NH = HL::NH, OST = HL::OST, PPO_TP = HL::TP;
     __shared__ __attribute__((aligned(16))) float uni[Cf::UNI];  // weight chunk + x chunk, later the hidden vectors
-    __shared__ float wo[HD * 10 + 12];                           // w_out, then b2
-    __shared__ float outs[TS * 11], douts[TS * 11], tsum[TS * PPO_TP];
+    __shared__ float wo[HD * NOUT + HL::WO];                     // w_out, then b2
+    __shared__ float outs[TS * OST], douts[TS * OST], tsum[TS * PPO_TP];
     __shared__ int rows[TS];
+    static_assert((Cf::UNI + HD * NOUT + HL::WO + 2 * TS * OST + TS * PPO_TP + TS) * 4 <= 64 * 1024,
+                  "the forward kernel's static LDS (55344 B at NOUT = 12, HD = 256)");
     float* const wbuf = uni;
     float* const xs = uni + Cf::WBUF;
     uint8_t* const clsb = reinterpret_cast<uint8_t*>(xs);  // TS * CH <= 2048 bytes
@@ -169,8 +232,8 @@ __global__ __launch_bounds__(PPO_THREADS) void ppo_fwd_kernel(
     const int tid = threadIdx.x, jq = tid % Q, sg = tid / Q;
     const int64_t t0 = (int64_t)blockIdx.x * TS;
     const int SS = b.SS, C = b.C;
-    for (int i = tid; i < HD * 10; i += PPO_THREADS) wo[i] = w_out[i];
-    if (tid < 10) wo[HD * 10 + tid] = b2[tid];
+    for (int i = tid; i < HD * NOUT; i += PPO_THREADS) wo[i] = w_out[i];
+    if (tid < NOUT) wo[HD * NOUT + tid] = b2[tid];
     if (tid < TS) rows[tid] = t0 + tid < b.N ? ppo_row(b, (int)(t0 + tid)) : 0;
     __syncthreads();
 
@@ -262,10 +325,10 @@ __global__ __launch_bounds__(PPO_THREADS) void ppo_fwd_kernel(
         reinterpret_cast<float4*>(H + (size_t)(t0 + s) * HD)[jq] = make_float4(a[0], a[1], a[2], a[3]);
     }
     __syncthreads();
-    // the ten outputs: a thread per (sample, output)
+    // the NOUT outputs: a thread per (sample, output)
     {
         const int s = tid % TS;
-        for (int o = tid / TS; o < 10; o += PPO_THREADS / TS) {
+        for (int o = tid / TS; o < NOUT; o += PPO_THREADS / TS) {
             float q[16];  // sixteen running sums over j mod 16, then a pairwise tree: no chain longer than HD / 16 + 4
 #pragma unroll
             for (int k = 0; k < 16; ++k) q[k] = 0.0f;
@@ -273,74 +336,58 @@ __global__ __launch_bounds__(PPO_THREADS) void ppo_fwd_kernel(
 #pragma unroll 1
             for (int j = 0; j < HD; j += 16) {
 #pragma unroll
-                for (int k = 0; k < 16; ++k) q[k] = fmaf(wo[(j + k) * 10 + o], hrow[j + k], q[k]);
+                for (int k = 0; k < 16; ++k) q[k] = fmaf(wo[(j + k) * NOUT + o], hrow[j + k], q[k]);
             }
 #pragma unroll
             for (int half = 8; half >= 1; half >>= 1)
 #pragma unroll
                 for (int k = 0; k < half; ++k) q[k] = q[k] + q[k + half];
-            outs[s * 11 + o] = wo[HD * 10 + o] + q[0];
+            outs[s * OST + o] = wo[HD * NOUT + o] + q[0];
         }
     }
     __syncthreads();
-    // the loss of one sample per thread
+    // the loss of one sample per thread: its heads one after the other, their terms of a statistic added in double
+    // and rounded once
     if (tid < TS) {
         const int s = tid;
         const bool valid = t0 + s < b.N;
-        float d[10], st[5];
+        float d[NOUT], st[5];
 #pragma unroll
-        for (int o = 0; o < 10; ++o) d[o] = 0.0f;
+        for (int o = 0; o < NOUT; ++o) d[o] = 0.0f;
 #pragma unroll
         for (int o = 0; o < 5; ++o) st[o] = 0.0f;
         if (valid) {
             const int row = rows[s];
-            double l[9], lo[9];
-#pragma unroll
-            for (int i = 0; i < 9; ++i) {
-                l[i] = (double)outs[s * 11 + i];
-                lo[i] = (double)b.old_logits[(size_t)row * 9 + i];
+            const double inv_n = 1.0 / (double)b.N, inv_nh = NH == 1 ? inv_n : 1.0 / ((double)b.N * (double)NH);
+            const float* __restrict__ old = b.old_logits + (size_t)row * NL;
+            PpoHeadTerms t = ppo_head<HL::N0>(b, row, hdr, outs + s * OST, old, b.action[(size_t)row * NH], la, inv_nh, d);
+            if constexpr (NH == 2) {
+                const PpoHeadTerms u = ppo_head<HL::N1>(b, row, hdr, outs + s * OST + HL::N0, old + HL::N0,
+                                                        b.action[(size_t)row * NH + 1], la, inv_nh, d + HL::N0);
+                t.pg = t.pg + u.pg;
+                t.ent = t.ent + u.ent;
+                t.kl = t.kl + u.kl;
+                t.clipped = t.clipped + u.clipped;
             }
-            const int a = min(max(b.action[row], 0), 8);
-            const double lse = ppo_lse9(l), lse_old = ppo_lse9(lo);
-            const double logratio = (ppo_pick9(l, a) - lse) - (ppo_pick9(lo, a) - lse_old);
-            const double ratio = exp(logratio);
-            double adv = (double)b.advantage[row];
-            if (la.norm_adv) adv = (adv - (double)hdr[0]) / ((double)hdr[1] + 1e-8);
-            const double lo_c = 1.0 - (double)la.clip_coef, hi_c = 1.0 + (double)la.clip_coef;
-            const bool clipped = ratio < lo_c || ratio > hi_c;
-            const double pg1 = -adv * ratio, pg2 = -adv * fmin(fmax(ratio, lo_c), hi_c);
-            const double dpg_dr = (!clipped || pg1 > pg2) ? -adv : 0.0;
-            double p[9], lp[9], ent = 0.0;
-#pragma unroll
-            for (int i = 0; i < 9; ++i) {
-                lp[i] = l[i] - lse;
-                p[i] = exp(lp[i]);
-                ent = ent - p[i] * lp[i];
-            }
-            const double g = dpg_dr * ratio, inv_n = 1.0 / (double)b.N;
-#pragma unroll
-            for (int i = 0; i < 9; ++i) {
-                const double onehot = (a == i) ? 1.0 : 0.0;
-                d[i] = (float)((g * (onehot - p[i]) + (double)la.ent_coef * (p[i] * (lp[i] + ent))) * inv_n);
-            }
-            const double dv = (double)outs[s * 11 + 9] - (double)b.returns[row];
-            d[9] = (float)(((double)la.vf_coef * dv) * inv_n);
-            st[0] = (float)fmax(pg1, pg2);
+            const double dv = (double)outs[s * OST + NL] - (double)b.returns[row];
+            d[NL] = (float)(((double)la.vf_coef * dv) * inv_n);
+            st[0] = (float)t.pg;
             st[1] = (float)(0.5 * dv * dv);
-            st[2] = (float)ent;
-            st[3] = (float)((ratio - 1.0) - logratio);
-            st[4] = clipped ? 1.0f : 0.0f;
+            st[2] = (float)t.ent;
+            st[3] = (float)t.kl;
+            st[4] = t.clipped;
         }
 #pragma unroll
-        for (int o = 0; o < 10; ++o) {
-            douts[s * 11 + o] = d[o];
-            DO[(size_t)(t0 + s) * 10 + o] = d[o];
+        for (int o = 0; o < NOUT; ++o) {
+            douts[s * OST + o] = d[o];
+            DO[(size_t)(t0 + s) * NOUT + o] = d[o];
         }
 #pragma unroll
         for (int o = 0; o < 5; ++o) tsum[s * PPO_TP + o] = st[o];
 #pragma unroll
-        for (int o = 0; o < 10; ++o) tsum[s * PPO_TP + 5 + o] = d[o];
-        tsum[s * PPO_TP + 15] = 0.0f;
+        for (int o = 0; o < NOUT; ++o) tsum[s * PPO_TP + 5 + o] = d[o];
+#pragma unroll
+        for (int o = 5 + NOUT; o < PPO_TP; ++o) tsum[s * PPO_TP + o] = 0.0f;
     }
     __syncthreads();
     // the tile's partial sums: a pairwise tree over the samples (s += s + half), the same order on every call
@@ -350,18 +397,18 @@ __global__ __launch_bounds__(PPO_THREADS) void ppo_fwd_kernel(
     }
     if (tid < PPO_TP) TP[(size_t)blockIdx.x * PPO_TP + tid] = tsum[tid];
     // d loss / d pre-activation = relu'(a) * sum_o w_out[j][o] * dout[o]
-    float wr[4][10];
+    float wr[4][NOUT];
 #pragma unroll
     for (int k = 0; k < 4; ++k)
 #pragma unroll
-        for (int o = 0; o < 10; ++o) wr[k][o] = wo[(4 * jq + k) * 10 + o];
+        for (int o = 0; o < NOUT; ++o) wr[k][o] = wo[(4 * jq + k) * NOUT + o];
 #pragma unroll
     for (int i = 0; i < SPT; ++i) {
         const int s = sg + R * i;
         float da[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
-        for (int o = 0; o < 10; ++o) {
-            const float dd = douts[s * 11 + o];
+        for (int o = 0; o < NOUT; ++o) {
+            const float dd = douts[s * OST + o];
 #pragma unroll
             for (int k = 0; k < 4; ++k) da[k] = fmaf(wr[k][o], dd, da[k]);
         }
@@ -372,7 +419,7 @@ __global__ __launch_bounds__(PPO_THREADS) void ppo_fwd_kernel(
 }
 
 // ------------------------------------------------------------------ wgrad: partial weight gradients
-template <int HD>
+template <int HD, int NOUT>
 __global__ __launch_bounds__(PPO_THREADS) void ppo_wgrad_kernel(PpoBatch b, PpoPlan pl, const float* __restrict__ DA,
                                                                 const float* __restrict__ H,
                                                                 const float* __restrict__ DO,
@@ -386,7 +433,7 @@ __global__ __launch_bounds__(PPO_THREADS) void ppo_wgrad_kernel(PpoBatch b, PpoP
     // kind 0: window cells (x = class), 1: coarse rows and b1 (x = coarse value / 1), 2: w_out columns (x = dout, D = h)
     const int kind = blk < pl.nbL ? 0 : (blk < pl.nbL + pl.nbC ? 1 : 2);
     const int r0 = (kind == 0 ? blk : kind == 1 ? blk - pl.nbL : blk - pl.nbL - pl.nbC) * R;
-    const int nrows = kind == 0 ? SS : kind == 1 ? C + 1 : 10;
+    const int nrows = kind == 0 ? SS : kind == 1 ? C + 1 : NOUT;
     const float* __restrict__ D = kind == 2 ? H : DA;
     const int64_t tile0 = (int64_t)blockIdx.y * pl.tps;
     const int64_t tile1 = min(tile0 + pl.tps, pl.ntiles);
@@ -402,7 +449,7 @@ __global__ __launch_bounds__(PPO_THREADS) void ppo_wgrad_kernel(PpoBatch b, PpoP
             uint32_t x = 0u;  // a row past the block's last, or a sample past N (its D row is zero)
             if (r < nrows && t0 + s < b.N) {
                 if (kind == 2) {
-                    x = __float_as_uint(DO[(size_t)(t0 + s) * 10 + r]);
+                    x = __float_as_uint(DO[(size_t)(t0 + s) * NOUT + r]);
                 } else {
                     const int row = ppo_row(b, (int)(t0 + s));
                     if (kind == 0) x = b.local[(size_t)row * SS + r] & 3u;
@@ -458,11 +505,11 @@ __global__ __launch_bounds__(PPO_THREADS) void ppo_wgrad_kernel(PpoBatch b, PpoP
         // row C of this kind is b1, which follows w_coarse in the partial
         reinterpret_cast<float4*>(out + pl.off_wc + (size_t)r * HD)[jq] = tot[0];
     } else {
-        float* o = out + pl.off_wo + (size_t)(4 * jq) * 10 + r;
+        float* o = out + pl.off_wo + (size_t)(4 * jq) * NOUT + r;
         o[0] = tot[0].x;
-        o[10] = tot[0].y;
-        o[20] = tot[0].z;
-        o[30] = tot[0].w;
+        o[NOUT] = tot[0].y;
+        o[2 * NOUT] = tot[0].z;
+        o[3 * NOUT] = tot[0].w;
     }
 }
 
@@ -471,6 +518,7 @@ struct PpoOut {
     float *g_w_local, *g_w_coarse, *g_b1, *g_w_out, *g_b2, *stats;
 };
 
+template <int NOUT, int NH>
 __global__ __launch_bounds__(PPO_THREADS) void ppo_reduce_kernel(PpoPlan pl, PpoLossArgs la,
                                                                  const float* __restrict__ part,
                                                                  const float* __restrict__ TP,
@@ -488,45 +536,60 @@ __global__ __launch_bounds__(PPO_THREADS) void ppo_reduce_kernel(PpoPlan pl, Ppo
         else out.g_w_out[e - pl.off_wo] = s;
         return;
     }
+    constexpr int PPO_TP = ppo_tp(NOUT), USED = 5 + NOUT;
     __shared__ float red[PPO_THREADS * PPO_TP];
     float s[PPO_TP];
 #pragma unroll
     for (int q = 0; q < PPO_TP; ++q) s[q] = 0.0f;
     for (int64_t t = tid; t < pl.ntiles; t += PPO_THREADS) {
 #pragma unroll
-        for (int q = 0; q < 15; ++q) s[q] = s[q] + TP[(size_t)t * PPO_TP + q];
+        for (int q = 0; q < USED; ++q) s[q] = s[q] + TP[(size_t)t * PPO_TP + q];
     }
 #pragma unroll
     for (int q = 0; q < PPO_TP; ++q) red[tid * PPO_TP + q] = s[q];
     __syncthreads();
     for (int st = PPO_THREADS / 2; st >= 1; st >>= 1) {
         if (tid < st)
-            for (int q = 0; q < 15; ++q) red[tid * PPO_TP + q] = red[tid * PPO_TP + q] + red[(tid + st) * PPO_TP + q];
+            for (int q = 0; q < USED; ++q) red[tid * PPO_TP + q] = red[tid * PPO_TP + q] + red[(tid + st) * PPO_TP + q];
         __syncthreads();
     }
-    if (tid < 10) out.g_b2[tid] = red[5 + tid];
+    if (tid < NOUT) out.g_b2[tid] = red[5 + tid];
     if (tid == 0) {
-        const float pg = red[0] * la.inv_n, vl = red[1] * la.inv_n, ent = red[2] * la.inv_n;
+        // pg, the entropy, approx_kl and the clip fraction are means over the N * NH (sample, head) pairs (1 / NH is
+        // exact for one and two heads), the value loss over the N samples
+        const float inv_nh = NH == 1 ? la.inv_n : la.inv_n / (float)NH;
+        const float pg = red[0] * inv_nh, vl = red[1] * la.inv_n, ent = red[2] * inv_nh;
         out.stats[0] = (pg - la.ent_coef * ent) + la.vf_coef * vl;
         out.stats[1] = pg;
         out.stats[2] = vl;
         out.stats[3] = ent;
-        out.stats[4] = red[3] * la.inv_n;
-        out.stats[5] = red[4] * la.inv_n;
+        out.stats[4] = red[3] * inv_nh;
+        out.stats[5] = red[4] * inv_nh;
         out.stats[6] = hdr[0];
         out.stats[7] = hdr[1];
     }
 }
 
 // ------------------------------------------------------------------ host side
-extern "C" int64_t gca_helicopter_policy_grad_workspace(const gca_heli_policy* p, int C, int N) {
-    if (gca_check_policy_grad_workspace(p, C, N)) return -1;
+using PpoHeli = PpoHeads<9, 0>;
+using PpoBdz = PpoHeads<9, 2>;
+
+static int64_t ppo_workspace(const GcaGradAgent& ag, const gca_policy* p, int C, int N) {
+    if (gca_check_policy_grad_workspace(ag, p, C, N)) return -1;
     const int S = 2 * p->radius + 1;
-    return ppo_plan(S * S, C, p->hidden, N).bytes;
+    return ppo_plan(S * S, C, p->hidden, N, ag.nout).bytes;
 }
 
-template <int HD>
-static void ppo_launch(const PpoBatch& b, const PpoPlan& pl, const gca_heli_policy* p, const PpoLossArgs& la,
+extern "C" int64_t gca_helicopter_policy_grad_workspace(const gca_heli_policy* p, int C, int N) {
+    return ppo_workspace(GCA_GRAD_HELI, p, C, N);
+}
+
+extern "C" int64_t gca_bulldozer_policy_grad_workspace(const gca_bulldozer_policy* p, int C, int N) {
+    return ppo_workspace(GCA_GRAD_BDZ, p, C, N);
+}
+
+template <int HD, class HL>
+static void ppo_launch(const PpoBatch& b, const PpoPlan& pl, const gca_policy* p, const PpoLossArgs& la,
                        const PpoOut& out, char* ws, hipStream_t st) {
     float* hdr = reinterpret_cast<float*>(ws);
     float* DA = reinterpret_cast<float*>(ws + pl.off_da);
@@ -535,23 +598,26 @@ static void ppo_launch(const PpoBatch& b, const PpoPlan& pl, const gca_heli_poli
     float* TP = reinterpret_cast<float*>(ws + pl.off_tp);
     float* part = reinterpret_cast<float*>(ws + pl.off_part);
     hipLaunchKernelGGL(ppo_adv_kernel, dim3(1), dim3(PPO_ADV_THREADS), 0, st, b, hdr);
-    hipLaunchKernelGGL(ppo_fwd_kernel<HD>, dim3((unsigned)pl.ntiles), dim3(PPO_THREADS), 0, st, b, p->w_local,
+    hipLaunchKernelGGL((ppo_fwd_kernel<HD, HL>), dim3((unsigned)pl.ntiles), dim3(PPO_THREADS), 0, st, b, p->w_local,
                        p->w_coarse, p->b1, p->w_out, p->b2, la, hdr, DA, H, DO, TP);
-    hipLaunchKernelGGL(ppo_wgrad_kernel<HD>, dim3((unsigned)pl.nb, (unsigned)pl.P), dim3(PPO_THREADS), 0, st, b, pl, DA,
-                       H, DO, part);
+    hipLaunchKernelGGL((ppo_wgrad_kernel<HD, HL::NOUT>), dim3((unsigned)pl.nb, (unsigned)pl.P), dim3(PPO_THREADS), 0,
+                       st, b, pl, DA, H, DO, part);
     const int elem_blocks = (int)((pl.GF + PPO_THREADS - 1) / PPO_THREADS);
-    hipLaunchKernelGGL(ppo_reduce_kernel, dim3((unsigned)elem_blocks + 1), dim3(PPO_THREADS), 0, st, pl, la, part, TP,
-                       hdr, out, elem_blocks);
+    hipLaunchKernelGGL((ppo_reduce_kernel<HL::NOUT, HL::NH>), dim3((unsigned)elem_blocks + 1), dim3(PPO_THREADS), 0, st,
+                       pl, la, part, TP, hdr, out, elem_blocks);
 }
 
-extern "C" int gca_helicopter_policy_grad(const gca_heli_policy* p, int C, const uint8_t* local, const float* coarse,
-                                          const int32_t* action, const float* old_logits, const float* advantage,
-                                          const float* returns, int64_t T, const int32_t* idx, int N, float clip_coef,
-                                          float ent_coef, float vf_coef, int norm_adv, float* g_w_local,
-                                          float* g_w_coarse, float* g_b1, float* g_w_out, float* g_b2, float* stats,
-                                          void* workspace, int64_t workspace_bytes, void* stream) {
+// the body of both entry points: the shared checks, then the four launches of the agent's head layout
+template <class HL>
+static int ppo_policy_grad(const GcaGradAgent& ag, const gca_policy* p, int C, const uint8_t* local,
+                           const float* coarse, const int32_t* action, const float* old_logits,
+                           const float* advantage, const float* returns, int64_t T, const int32_t* idx, int N,
+                           float clip_coef, float ent_coef, float vf_coef, int norm_adv, float* g_w_local,
+                           float* g_w_coarse, float* g_b1, float* g_w_out, float* g_b2, float* stats, void* workspace,
+                           int64_t workspace_bytes, void* stream) {
+    static_assert(HL::NOUT == 10 || HL::NOUT == 12, "the agents' outputs (GcaGradAgent::nout)");
     PpoPlan pl;
-    if (const int st = gca_check_policy_grad(p, C, local, coarse, action, old_logits, advantage, returns, T, idx, N,
+    if (const int st = gca_check_policy_grad(ag, p, C, local, coarse, action, old_logits, advantage, returns, T, idx, N,
                                              clip_coef, g_w_local, g_w_coarse, g_b1, g_w_out, g_b2, stats, workspace,
                                              workspace_bytes, &pl))
         return st;
@@ -562,11 +628,33 @@ extern "C" int gca_helicopter_policy_grad(const gca_heli_policy* p, int C, const
     hipStream_t st = (hipStream_t)stream;
     char* ws = reinterpret_cast<char*>(workspace);
     switch (Hd) {
-        case 32: ppo_launch<32>(b, pl, p, la, out, ws, st); break;
-        case 64: ppo_launch<64>(b, pl, p, la, out, ws, st); break;
-        case 128: ppo_launch<128>(b, pl, p, la, out, ws, st); break;
-        default: ppo_launch<256>(b, pl, p, la, out, ws, st); break;
+        case 32: ppo_launch<32, HL>(b, pl, p, la, out, ws, st); break;
+        case 64: ppo_launch<64, HL>(b, pl, p, la, out, ws, st); break;
+        case 128: ppo_launch<128, HL>(b, pl, p, la, out, ws, st); break;
+        default: ppo_launch<256, HL>(b, pl, p, la, out, ws, st); break;
     }
-    GCA_CHECK_LAUNCH("helicopter_policy_grad");
+    GCA_CHECK_LAUNCH(ag.who);
     return GCA_OK;
+}
+
+extern "C" int gca_helicopter_policy_grad(const gca_heli_policy* p, int C, const uint8_t* local, const float* coarse,
+                                          const int32_t* action, const float* old_logits, const float* advantage,
+                                          const float* returns, int64_t T, const int32_t* idx, int N, float clip_coef,
+                                          float ent_coef, float vf_coef, int norm_adv, float* g_w_local,
+                                          float* g_w_coarse, float* g_b1, float* g_w_out, float* g_b2, float* stats,
+                                          void* workspace, int64_t workspace_bytes, void* stream) {
+    return ppo_policy_grad<PpoHeli>(GCA_GRAD_HELI, p, C, local, coarse, action, old_logits, advantage, returns, T, idx,
+                                    N, clip_coef, ent_coef, vf_coef, norm_adv, g_w_local, g_w_coarse, g_b1, g_w_out,
+                                    g_b2, stats, workspace, workspace_bytes, stream);
+}
+
+extern "C" int gca_bulldozer_policy_grad(const gca_bulldozer_policy* p, int C, const uint8_t* local,
+                                         const float* coarse, const int32_t* action, const float* old_logits,
+                                         const float* advantage, const float* returns, int64_t T, const int32_t* idx,
+                                         int N, float clip_coef, float ent_coef, float vf_coef, int norm_adv,
+                                         float* g_w_local, float* g_w_coarse, float* g_b1, float* g_w_out, float* g_b2,
+                                         float* stats, void* workspace, int64_t workspace_bytes, void* stream) {
+    return ppo_policy_grad<PpoBdz>(GCA_GRAD_BDZ, p, C, local, coarse, action, old_logits, advantage, returns, T, idx, N,
+                                   clip_coef, ent_coef, vf_coef, norm_adv, g_w_local, g_w_coarse, g_b1, g_w_out, g_b2,
+                                   stats, workspace, workspace_bytes, stream);
 }

@@ -291,6 +291,9 @@ _SIGNATURES = {
     "gca_helicopter_policy_grad_workspace": ([POINTER(HeliPolicy), c_int, c_int], c_int64),
     "gca_helicopter_policy_grad": ([POINTER(HeliPolicy), c_int, P, P, P, P, P, P, c_int64, P, c_int, c_float, c_float,
                                     c_float, c_int, P, P, P, P, P, P, P, c_int64, P], c_int),
+    "gca_bulldozer_policy_grad_workspace": ([POINTER(BulldozerPolicyStruct), c_int, c_int], c_int64),
+    "gca_bulldozer_policy_grad": ([POINTER(BulldozerPolicyStruct), c_int, P, P, P, P, P, P, c_int64, P, c_int, c_float,
+                                   c_float, c_float, c_int, P, P, P, P, P, P, P, c_int64, P], c_int),
     "gca_adam_step_workspace": ([c_int64], c_int64),
     "gca_adam_step": ([POINTER(AdamTensors), P, c_float, c_float, c_float, c_float, c_float, c_int64, c_int64, P, P,
                        c_int64, P], c_int),
@@ -306,8 +309,10 @@ CPU_SYMBOLS = ("gca_last_error", "gca_version", "gca_philox", "gca_count_cells",
                "gca_bulldozer_reset_where", "gca_policy_observation", "gca_helicopter_policy_act",
                "gca_helicopter_policy_rollout", "gca_gae", "gca_helicopter_policy_grad_workspace",
                "gca_helicopter_policy_grad", "gca_adam_step_workspace", "gca_adam_step", "gca_permutation")
-# the bulldozer policy's network on host arrays (the closed-loop rollout needs the Windy CA: device build only)
-CPU_BULLDOZER_POLICY_SYMBOLS = ("gca_bulldozer_policy_act",)
+# the bulldozer policy's network and its learner's step on host arrays (the closed-loop rollout needs the Windy CA:
+# device build only)
+CPU_BULLDOZER_POLICY_SYMBOLS = ("gca_bulldozer_policy_act", "gca_bulldozer_policy_grad_workspace",
+                                "gca_bulldozer_policy_grad")
 
 _lib = None
 _lib_cpu = None

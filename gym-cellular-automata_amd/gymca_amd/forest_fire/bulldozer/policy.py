@@ -4,11 +4,14 @@ The helicopter policy's two-layer MLP over observe(radius, block)'s tensors (inc
 outputs: nine move logits, two shoot logits (the reference's Actor(action_dims=[9, 2])) and the value. env.act(policy)
 is one launch on an observation; env.rollout_policy(policy, K) collects K closed-loop steps of every env, autoreset
 included, bit for bit K x (observe, act, step [, reset]) and in one launch where the shape allows. forward_torch is the
-same network in differentiable torch ops, for a learner that takes the loss through autograd
-(scripts/train_bulldozer_ppo.py); the two-head loss gradient on the device is not part of this class yet.
+same network in differentiable torch ops. ppo_grad is the learner's step on rollout_policy's records: the PPO
+clipped-surrogate loss taken per head (include/gca.h gca_bulldozer_policy_grad: the reference's ppo_loss, every mean over
+the (sample, head) pairs), its statistics and its gradient with respect to the five tensors in four launches, with
+forest_fire.ppo.gae for the advantages; ppo_update is the whole update (scripts/train_bulldozer_ppo.py).
 
-The bookkeeping (validated assignment of the five tensors, `version`, the C struct, load) is PolicyBase's (_policy.py),
-shared with HelicopterPolicy.
+The bookkeeping (validated assignment of the five tensors, `version`, the C struct, load) and ppo_grad / ppo_update are
+PolicyBase's (_policy.py), shared with HelicopterPolicy; a record's `action` holds T x 2 int32 values (move, shoot) and
+its `logits` T x 11 float32 values.
 """
 from .._policy import WEIGHTS, PolicyBase  # WEIGHTS: the trainers import it from here
 
@@ -19,7 +22,9 @@ N_OUT = N_LOGITS + 1  # the logits and the value
 
 
 class BulldozerPolicy(PolicyBase):
+    HEADS = (N_MOVE, N_SHOOT)
     N_LOGITS = N_LOGITS
+    GRAD_ENTRY = "gca_bulldozer_policy_grad"
 
     def forward_torch(self, local, coarse, weights=None):
         """(move_logits (..., 9), shoot_logits (..., 2), value (...)) of the same network in differentiable torch ops: an

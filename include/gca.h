@@ -788,6 +788,33 @@ int gca_helicopter_policy_grad(const gca_heli_policy* p, int C, const uint8_t* l
                                float* g_b1, float* g_w_out, float* g_b2, float* stats, void* workspace,
                                int64_t workspace_bytes, void* stream);
 
+/* gca_bulldozer_policy_grad: the same loss for the bulldozer's two heads (the reference's Actor(action_dims=[9, 2])),
+ * taken PER HEAD as the reference's ppo_loss takes it (agents/jax_ppo.py:902-930 get_action_and_value2 stacks the heads'
+ * log-probabilities and entropies to (N, heads), its .sum(axis=1) commented out; update_ppo :1066-1072 repeats the
+ * advantages per head, and every .mean() of ppo_loss :987-1041 runs over N x heads). The records are
+ * gca_bulldozer_policy_rollout's: action i32 [T][2] (move, shoot), old_logits f32 [T][11] (nine move logits, two shoot
+ * logits); the network has twelve outputs, the value in column 11. With NH = 2 heads, head h has logits l_h (9 or 2 of
+ * them), recorded logits lo_h and action a_h; A^ is the sample's (optionally normalised) advantage as above:
+ *   logratio_h = (l_h[a_h] - lse(l_h)) - (lo_h[a_h] - lse(lo_h)), ratio_h = exp(logratio_h)
+ *   pg_h = max(-A^ ratio_h, -A^ clip(ratio_h, 1 - c, 1 + c)); ent_h = -sum p log p over head h; vl = 0.5 (v - R)^2
+ *   loss = mean_{s,h} pg - ent_coef mean_{s,h} ent + vf_coef mean_s vl
+ * stats[8] in the order above: pg, entropy, approx_kl = mean((ratio - 1) - logratio) and the clip fraction are means
+ * over the N NH (sample, head) pairs; v_loss, adv mean and adv std are means over the N samples.
+ *   d loss / d l_h[i] = (1 / (N NH)) [dpg_dr_h ratio_h (1[i = a_h] - p_i) + ent_coef p_i (log p_i + ent_h)], with
+ *   dpg_dr_h = -A^ where the unclipped branch is the maximum (not clipped, or pg1 > pg2), else 0;
+ *   d loss / d v = vf_coef (v - R) / N.
+ * An action of head h outside [0, n_h - 1] is clamped. With one head this is gca_helicopter_policy_grad's loss exactly,
+ * and everything else said there (outputs, workspace, alignment, fixed summation order, idx, capturability, the host
+ * build) holds here with gca_bulldozer_policy_grad_workspace; one sample's terms of a statistic are added over its
+ * heads in double and rounded once. */
+int64_t gca_bulldozer_policy_grad_workspace(const gca_bulldozer_policy* p, int C, int N);
+int gca_bulldozer_policy_grad(const gca_bulldozer_policy* p, int C, const uint8_t* local, const float* coarse,
+                              const int32_t* action, const float* old_logits, const float* advantage,
+                              const float* returns, int64_t T, const int32_t* idx, int N, float clip_coef,
+                              float ent_coef, float vf_coef, int norm_adv, float* g_w_local, float* g_w_coarse,
+                              float* g_b1, float* g_w_out, float* g_b2, float* stats, void* workspace,
+                              int64_t workspace_bytes, void* stream);
+
 /* ------------------------------------------ optimizer (the rest of the reference's update_ppo, agents/jax_ppo.py:1045-1114:
  * optax.chain(clip_by_global_norm(max_norm), adam(lr, b1, b2, eps)) with linear_schedule, :677-702 and :775-783)
  * gca_adam_step: one optimizer step over n <= GCA_ADAM_MAX_TENSORS parameter tensors in TWO launches, no floating-point
