@@ -517,7 +517,13 @@ int gca_obs_color_table(const gca_obs_params* p, float* table, void* stream);
 int gca_obs_position(const gca_obs_params* p, int E, int H, int W, const int32_t* pos, const int32_t* is_night,
                      const int32_t* time_step, float* rgb, void* stream);
 
-/* Synthetic inputs for benches/tests (Philox, GCA_TAG_INIT / GCA_TAG_ACTION). */
+/* Synthetic inputs for benches/tests (Philox, GCA_TAG_INIT / GCA_TAG_ACTION).
+ * gca_fill_categorical: out[e][i] (u8, [E][n_per_env]) = values[k], u = u01_f32 of word i & 3 of Philox((i >> 2,
+ *   env_offset + e, 0, GCA_TAG_INIT), seed), k the first index < n_values - 1 with u < cdf[k]; a u at or above every
+ *   one of those entries FALLS THROUGH to the last value, values[n_values - 1] (cdf[n_values - 1] is never read, and
+ *   n_values = 1 fills with values[0]). cdf f32 and values u8 are device arrays.
+ * gca_random_actions: action[e] = (randint_ms(x.x, 0, 9), x.y >> 31), x = Philox((0, env_offset + e, rng_step[e]
+ *   (NULL: 0), GCA_TAG_ACTION), seed). */
 int gca_fill_categorical(uint8_t* out, int64_t n_per_env, int E, int env_offset, uint64_t seed,
                          const float* cdf, const uint8_t* values, int n_values, void* stream);
 int gca_random_actions(int32_t* action, int E, int env_offset, uint64_t seed, const uint32_t* rng_step,
@@ -527,7 +533,11 @@ int gca_random_actions(int32_t* action, int E, int env_offset, uint64_t seed, co
  * ForestFire.update (ca_DrosselSchwabl.py:32-66). The reference draws one f64
  * uniform per TREE-without-burning-neighbour and per EMPTY cell, in row-major
  * order, from op.np_random. Exact-stream mode: uniforms[] holds those draws in
- * order (n = gca_ds_count_draws). One workgroup per env (scan over the grid).   */
+ * order (n = gca_ds_count_draws). One workgroup per env (scan over the grid).
+ * uniforms is ONE array shared by all envs: env e's j-th draw is uniforms[uniform_offset[e] + j], so uniform_offset
+ * [E] indexes that array (typically the exclusive sum of n_draws), not a per-env slice. uniforms = NULL: Philox mode,
+ * u = u01_f64 of Philox((cell, env_offset + e, rng_step[e] or 0, GCA_TAG_DS_CELL), seed), uniform_offset unused.
+ * counts (nullable) [E][3] EMPTY / TREE / FIRE cells of grid_out, OVERWRITTEN (the caller need not zero them).   */
 int gca_ds_count_draws(const uint8_t* grid, int E, int H, int W, int empty, int tree, int fire,
                        int32_t* n_draws, void* stream);
 int gca_ds_step(const uint8_t* grid_in, uint8_t* grid_out, int E, int H, int W, int empty, int tree, int fire,
