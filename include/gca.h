@@ -66,7 +66,9 @@ int gca_count_cells(const uint8_t* grid, int E, int H, int W, int v0, int v1, in
  * wind: [E][9] f64 with env stride wind_stride (0 = one wind shared by all envs).
  * roll: [E][9] f64 injected uniforms, or NULL -> Philox(seed, (d/2, env_offset+e,
  *       rng_step[e] + pass, GCA_TAG_WINDY_ROLL)), 53-bit doubles.
- * Only envs with steps == NULL || steps[e] > pass are written.                */
+ * Only envs with steps == NULL || steps[e] > pass are written; dir_mask[e] of every
+ * other env keeps its value. roll < wind is strict: a tie leaves the bit clear.
+ * rng_step == NULL draws step `pass` for every env; rng_step[e] + pass wraps at 2^32. */
 int gca_windy_dirmask(const double* wind, int64_t wind_stride, const double* roll, uint64_t seed,
                       const uint32_t* rng_step, const int32_t* steps, int pass, int env_offset,
                       uint8_t* dir_mask, int E, void* stream);
@@ -79,7 +81,17 @@ int gca_windy_dirmask(const double* wind, int64_t wind_stride, const double* rol
  * SWAR kernel when it is exact (empty == 0, all cells in {empty, tree, fire}: the
  * caller guarantees the latter; W = 16*2^j <= 1024, 16-B aligned buffers).
  * counts (nullable, [E][3] empty/tree/fire of the NEW grid) are ACCUMULATED with
- * atomics: the caller zeroes the participating rows first.                    */
+ * atomics: the caller zeroes the participating rows first.
+ * An env that does not participate is not touched: neither of its buffers, nor its
+ * counts row. A participating env's source buffer is only read.
+ * The SWAR kernels apply the closed-form rule (TREE -> FIRE iff an active direction
+ * sees FIRE, FIRE -> EMPTY, else unchanged). It equals the thresholds on every grid of
+ * the three codes iff the codes satisfy the reference constructor's inequalities
+ * (ca_windy.py:163-173; with empty = 0: 8*tree < fire < 32*tree), which this entry
+ * point does NOT check: with other codes (e.g. 0, 2, 9) pass force_exact = 1 to get
+ * the thresholds (there a TREE ignites on the weight of its TREE neighbours alone).
+ * W = 256 and 512 take the row-stream kernel, every other eligible W the lane-tile
+ * kernel; any other W, an unaligned buffer or empty != 0 the literal kernel.   */
 int gca_windy_step(uint8_t* buf0, uint8_t* buf1, const uint8_t* parity, const int32_t* steps, int pass,
                    const uint8_t* dir_mask, int E, int H, int W, int empty, int tree, int fire,
                    int force_exact, int32_t* counts, void* stream);
@@ -100,18 +112,24 @@ typedef struct {
 
 /* Before the CA passes: for live envs (done[e]==0) accu += (t_move[a0]+t_shoot[a1]) + t_any,
  * (accu, steps) = modf(accu); zero counts of stepping envs; dir_mask for pass 0.
- * Done envs get steps = 0.                                                      */
+ * Done envs (done nullable: NULL = every env is live) get steps = -1 and nothing
+ * else: their accu, counts and dir_mask keep their values, as do the counts and
+ * dir_mask of live envs with steps == 0.                                        */
 int gca_bulldozer_pre(const gca_bulldozer_params* p, const int32_t* action, double* accu, int32_t* steps,
                       const uint8_t* done, const double* wind, int64_t wind_stride, const uint32_t* rng_step,
                       uint8_t* dir_mask, int32_t* counts, int E, void* stream);
 /* Between CA passes `pass` and `pass+1`: flip parity of envs that stepped in `pass`;
- * for envs stepping again, zero their counts and draw the dir_mask for pass+1.  */
+ * for envs stepping again (steps[e] > pass + 1), zero their counts and draw the
+ * dir_mask for pass+1 at Philox step rng_step[e] + pass + 1.                     */
 int gca_bulldozer_interpass(const gca_bulldozer_params* p, int pass, const int32_t* steps, uint8_t* parity,
                             const double* wind, int64_t wind_stride, const uint32_t* rng_step, uint8_t* dir_mask,
                             int32_t* counts, int E, void* stream);
 /* After the last pass (index last_pass): flip parity, Move, Modify (in place on the
  * current buffer), adjust counts, reward = -(f/(t+f)) (NaN if t+f==0), done = (f==0),
- * rng_step += steps. Done-on-entry envs: reward 0, nothing moves.                  */
+ * rng_step += steps. Done-on-entry envs (steps[e] < 0): reward 0, nothing else is
+ * written (pos, hit, done, counts, parity, rng_step keep their values).
+ * parity == NULL: no flip, Modify on buf0 (buf1 may be NULL). A Modify whose old or
+ * new value is none of the three codes changes only the count of the one that is.   */
 int gca_bulldozer_post(const gca_bulldozer_params* p, int last_pass, const int32_t* action, const int32_t* steps,
                        uint8_t* parity, uint8_t* buf0, uint8_t* buf1, int H, int W, int32_t* pos,
                        int32_t* counts, uint32_t* rng_step, uint8_t* done, uint8_t* hit, double* reward,
