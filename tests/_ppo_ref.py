@@ -1,24 +1,50 @@
-"""Yardsticks of the PPO update (include/gca.h "PPO update"): the GAE recurrence restated in numpy float32, the loss
-and its gradient by torch autograd of the network restated in float64 (and, for the tolerance, in float32), the sample
-filter of the kinks, the shared cases and drivers of the host build. Test infrastructure only: the product never imports
+"""Yardsticks of the PPO update (include/gca.h "PPO update"), one for both agents: the GAE recurrence restated in numpy
+float32, the per-head loss and its gradient by torch autograd of the network restated in float64 (and, for the
+tolerance, in float32), the sample filter of the kinks, the shared cases and drivers of the host build. An agent is a
+_policy_ref.Agent; its `heads` are all that the loss knows of it. Test infrastructure only: the product never imports
 it."""
 import ctypes
 import functools
 
 import numpy as np
 
-import _helicopter_policy_ref as pref
+import _policy_ref as P
 
-U = pref.U
+U = P.U
 FLOOR = 64 * U   # the tolerance's floor, for the cases where torch's float32 happens to be exact
 # Tolerance: 4 x the error torch's own float32 autograd of the restated network shows against the float64 yardstick on
 # the same case, at least FLOOR. Worst observed kernel error / max(torch-f32 error, FLOOR / 4) on an MI355X, per shape
-# of SHAPES in order: 1.09, 1.68, 2.36, 1.41, 1.97, 2.37 (pg_loss or loss; the gradients stay below 1.3): DESIGN.md
-# section 3.
+# of SHAPES in order.
+# helicopter: 1.09, 1.68, 2.36, 1.41, 1.97, 2.37 (pg_loss or loss; the gradients stay below 1.3);
+# bulldozer: 0.67 (pg_loss), 1.74 (loss), 1.37 (approx_kl), 1.18 (pg_loss); the gradients stay below 0.8.
 MARGIN = 4.0
-SHAPES = pref.SHAPES + [(5, 8, 128, 42, 42), (1, 4, 256, 5, 5)]
+HELI, BDZ = AGENTS = (P.HELICOPTER, P.BULLDOZER)
+SHAPES = {HELI: HELI.shapes + [(5, 8, 128, 42, 42), (1, 4, 256, 5, 5)], BDZ: BDZ.shapes}
 STATS = ("loss", "pg_loss", "v_loss", "entropy", "approx_kl", "clip_fraction", "adv_mean", "adv_std")
 GRADS = ("w_local", "w_coarse", "b1", "w_out", "b2")
+# the seed of each shape's case: the first for which the conditions of `check_case` hold (a seed that misses one is
+# replaced here; the conditions are not relaxed)
+SEEDS = {shape: 0 for agent in AGENTS for shape in SHAPES[agent]}
+# The relu rule wants ALL of a row's units outside 4 rounding bounds (S^2 + C + 1) U T_j of the kink, which the
+# bulldozer's two larger networks cannot meet on 90 % of the rows with make_weights' b1 ~ N(-0.1, 0.3), whatever the
+# seed: at 128 units (bound 3e-4, spread 1.1) 87 to 89 % of the rows are decided in each of thirty seeds; at radius 31
+# and 256 units (bound 0.018, spread 1.5: 4 % of a row's units near the kink) not one row in 1200 is. Those cases move
+# every b1 away from zero by B1_PUSH before anything else is drawn from the weights: by 1 at 128 units (94 % decided by
+# the relu rule, 122 of the 128 units still switch between samples), by 5 at 256 (97 %; about a third of the units on,
+# 17 still switch). Every other shape keeps make_weights' b1.
+B1_PUSH = {(5, 16, 128, 64, 512): 1.0, (31, 32, 256, 64, 256): 5.0}
+# What keeps each agent's cases the ones they have always been: the salt of the case's seed, and the columns one
+# perturbation draw has beyond its head's (the helicopter's draw covers the value column too and drops it).
+SALT = {HELI: 0, BDZ: 17}
+DRAW_EXTRA = {HELI: 1, BDZ: 0}
+
+
+def params(agents=AGENTS, pick=None):
+    """pytest parameters (agent, shape), with ids such as helicopter-shape1; pick: {agent: indices into its SHAPES}."""
+    import pytest
+
+    return [pytest.param(a, s, id=f"{a.name}-shape{i}") for a in agents for i, s in enumerate(SHAPES[a])
+            if pick is None or i in pick[a]]
 
 
 def gae_ref(reward, value, next_value, terminal, gamma, gae_lambda):
@@ -70,120 +96,161 @@ def gae_case(K, E, mode, seed=0):
 
 
 # ------------------------------------------------------------------ the loss and its gradient by autograd
-def _network(w, onehot, coarse):
+def _head_logp(logits, act):
     import torch
 
-    Hd = w["b1"].shape[0]
-    a = onehot @ w["w_local"].reshape(-1, Hd) + coarse @ w["w_coarse"] + w["b1"]
-    out = torch.relu(a) @ w["w_out"] + w["b2"]
-    return a, out
+    logp = torch.log_softmax(logits, 1)
+    return logp, logp.gather(1, act[:, None])[:, 0]
 
 
-def loss_and_grad(w, d, rec, adv, ret, idx, clip_coef=0.2, ent_coef=0.01, vf_coef=0.5, norm_adv=True, dtype="float64"):
-    """The loss of gca.h on rows `idx` of the records by torch autograd on the CPU in `dtype`, the network restated as
-    a one-hot matmul (the Dense layer over the one-hot classes that the lookup stands for). Returns (grads, stats, pre,
-    ratio): numpy float64 arrays; pre (N, Hd) the hidden pre-activations, ratio (N,)."""
+def loss_and_grad(w, d, rec, adv, ret, idx, heads, clip_coef=0.2, ent_coef=0.01, vf_coef=0.5, norm_adv=True,
+                  dtype="float64"):
+    """The per-head loss of gca.h on rows `idx` of the records by torch autograd on the CPU in `dtype`, the network
+    restated as a one-hot matmul (the Dense layer over the one-hot classes that the lookup stands for) with
+    sum(heads) + 1 outputs. Returns (grads, stats, pre, ratio): numpy float64 arrays; pre (N, Hd) the hidden
+    pre-activations, ratio (N, len(heads)) the heads' ratios."""
     import torch
 
     dt = getattr(torch, dtype)
     idx = np.asarray(idx, np.int64)
-    N, SS = len(idx), d["SS"]
+    N, SS, Hd, n_logits = len(idx), d["SS"], d["hidden"], sum(heads)
     leaves = {k: torch.tensor(np.asarray(v), dtype=dt, requires_grad=True) for k, v in w.items()}
     cls = rec["local"].reshape(-1, SS)[idx].astype(np.int64) & 3
     onehot = torch.zeros((N, SS * 4), dtype=dt)
     onehot[np.arange(N)[:, None], np.arange(SS)[None, :] * 4 + cls] = 1
     coarse = torch.tensor(rec["coarse"].reshape(-1, d["C"])[idx], dtype=dt)
-    a, out = _network(leaves, onehot, coarse)
-    logits, value = out[:, :9], out[:, 9]
-    act = torch.tensor(rec["action"].reshape(-1)[idx].astype(np.int64))
-    old = torch.tensor(rec["logits"].reshape(-1, 9)[idx], dtype=dt)
-    logp = torch.log_softmax(logits, 1)
-    logp_new = logp.gather(1, act[:, None])[:, 0]
-    logp_old = torch.log_softmax(old, 1).gather(1, act[:, None])[:, 0]
-    logratio = logp_new - logp_old
+    a = onehot @ leaves["w_local"].reshape(-1, Hd) + coarse @ leaves["w_coarse"] + leaves["b1"]
+    out = torch.relu(a) @ leaves["w_out"] + leaves["b2"]
+    value = out[:, n_logits]
+    act = torch.tensor(rec["action"].reshape(-1, len(heads))[idx].astype(np.int64))
+    old = torch.tensor(rec["logits"].reshape(-1, n_logits)[idx], dtype=dt)
+    logratio, ent, off = [], [], 0
+    for h, n in enumerate(heads):
+        logp, new = _head_logp(out[:, off:off + n], act[:, h])
+        _, prev = _head_logp(old[:, off:off + n], act[:, h])
+        logratio.append(new - prev)
+        ent.append(-(torch.exp(logp) * logp).sum(1))
+        off += n
+    logratio, ent = torch.stack(logratio, 1), torch.stack(ent, 1)  # (N, heads): nothing is summed over the heads
     ratio = torch.exp(logratio)
     A = torch.tensor(np.asarray(adv).reshape(-1)[idx], dtype=dt)
     mean, std = A.mean(), A.std(unbiased=False)
     if norm_adv:
         A = (A - mean) / (std + 1e-8)
-    pg = torch.maximum(-A * ratio, -A * torch.clamp(ratio, 1 - clip_coef, 1 + clip_coef)).mean()
-    R = torch.tensor(np.asarray(ret).reshape(-1)[idx], dtype=dt)
-    vl = (0.5 * (value - R) ** 2).mean()
-    ent = (-(torch.exp(logp) * logp).sum(1)).mean()
-    loss = pg - ent_coef * ent + vf_coef * vl
+    A2 = A[:, None].repeat(1, len(heads))  # the advantages repeated per head
+    pg = torch.maximum(-A2 * ratio, -A2 * torch.clamp(ratio, 1 - clip_coef, 1 + clip_coef)).mean()
+    Rt = torch.tensor(np.asarray(ret).reshape(-1)[idx], dtype=dt)
+    vl = (0.5 * (value - Rt) ** 2).mean()
+    en = ent.mean()
+    loss = pg - ent_coef * en + vf_coef * vl
     loss.backward()
     with torch.no_grad():
         kl = ((ratio - 1) - logratio).mean()
         clipfrac = ((ratio < 1 - clip_coef) | (ratio > 1 + clip_coef)).to(dt).mean()
-        stats = np.array([float(x) for x in (loss, pg, vl, ent, kl, clipfrac, mean, std)], np.float64)
+        stats = np.array([float(x) for x in (loss, pg, vl, en, kl, clipfrac, mean, std)], np.float64)
     grads = {k: leaves[k].grad.numpy().astype(np.float64) for k in GRADS}
     return grads, stats, a.detach().numpy().astype(np.float64), ratio.detach().numpy().astype(np.float64)
 
 
+def _lookup(w_local, cls):
+    """(T, Hd) float64: sum over the cells of w_local[cell, class], as four matmuls (a gather would hold T x S^2 x Hd
+    values, 10 GB at radius 31)."""
+    wl = np.asarray(w_local, np.float64)
+    return sum((cls == k).astype(np.float64) @ wl[:, k, :] for k in range(4))
+
+
 def pre_bound(w, d, rec):
     """(T, Hd): the rounding bound (S^2 + C + 1) 2^-24 T_j of every row's pre-activations in ANY float32 summation
-    order (the derivation in _helicopter_policy_ref.outputs_f64)."""
+    order (the derivation in _policy_ref.outputs_f64)."""
     SS, C = d["SS"], d["C"]
     cls = rec["local"].reshape(-1, SS).astype(np.int64) & 3
-    wl = np.abs(w["w_local"].astype(np.float64))
-    T = np.abs(w["b1"].astype(np.float64)) + wl[np.arange(SS)[None, :], cls].sum(1) + \
+    T = np.abs(w["b1"].astype(np.float64)) + _lookup(np.abs(w["w_local"]), cls) + \
         np.abs(rec["coarse"].reshape(-1, C).astype(np.float64)) @ np.abs(w["w_coarse"].astype(np.float64))
     return (SS + C + 1) * U * T
 
 
 def decided(pre, bound, ratio, clip_coef):
-    """A sample is decided when no pre-activation lies within 4 x its bound of 0 and its ratio is at least 1e-3 away
-    from 1 +- clip_coef: an f32 evaluation cannot legitimately take the other side of a kink."""
+    """A sample is decided when no pre-activation lies within 4 x its bound of 0 and every head's ratio is at least
+    1e-3 away from 1 +- clip_coef: an f32 evaluation cannot legitimately take the other side of a kink."""
     relu_ok = (np.abs(pre) > 4 * bound).all(1)
     ratio_ok = (np.abs(ratio - (1 - clip_coef)) >= 1e-3) & (np.abs(ratio - (1 + clip_coef)) >= 1e-3)
-    return relu_ok & ratio_ok
+    return relu_ok & ratio_ok.all(1)
 
 
 @functools.lru_cache(maxsize=None)
-def case(shape, T=1200, seed=0, clip_coef=0.2):
+def case(agent, shape, T=1200, seed=None, clip_coef=0.2):
     """The records of T rows for `shape`, shared (and left unchanged) by the tests: dims, weights (head = 2.0),
-    uniformly random class windows with one byte of 7, a coarse map, actions, old logits from perturbed head weights
-    scaled so that clipping is active on both sides, advantages of both signs, returns; `rows`: the decided rows."""
-    d = pref.dims(*shape)
-    rng = np.random.default_rng(seed + 7919 * shape[2] + shape[0])
-    w = pref.make_weights(d, seed=seed + shape[2], head=2.0)
+    uniformly random class windows with one byte of 7 at row 3, a coarse map, one action per head ((T,) for one head,
+    (T, heads) for more), old logits from perturbed head weights, each head scaled on its own so that clipping is
+    active on both of its sides, advantages of both signs, returns; `rows`: the decided rows."""
+    seed = SEEDS[shape] if seed is None else seed
+    heads = agent.heads
+    d = P.dims(*shape)
+    rng = np.random.default_rng(seed + 7919 * shape[2] + shape[0] + SALT[agent])
+    w = P.make_weights(d, agent.n_out, seed=seed + shape[2], head=2.0)
+    w["b1"] = (w["b1"] + np.float32(B1_PUSH.get(shape, 0.0)) * np.sign(w["b1"])).astype(np.float32)
     local = rng.integers(0, 4, (T, d["S"], d["S"])).astype(np.uint8)
     local[3, 0, 0] = 7  # a class byte above 3 counts modulo 4
     coarse = (rng.integers(0, shape[1] ** 2 + 1, (T, 2, d["Hc"], d["Wc"])) / shape[1] ** 2).astype(np.float32)
-    action = rng.integers(0, 9, T).astype(np.int32)
+    action = np.stack([rng.integers(0, n, T) for n in heads], 1).astype(np.int32)
     adv = (rng.standard_normal(T) + 0.3).astype(np.float32)
     ret = rng.standard_normal(T).astype(np.float32)
-    rec = {"local": local, "coarse": coarse, "action": action, "logits": np.zeros((T, 9), np.float32)}
-    out64, _ = pref.outputs_f64(w, d, local, coarse)
-    # the old policy: the head's weights perturbed, at the scale at which about 45 % of the ratios are clipped; a draw
-    # that leaves less than 12 % on either side is drawn again
     SS, C = d["SS"], d["C"]
     cls = local.reshape(T, SS).astype(np.int64) & 3
-    a64 = w["b1"].astype(np.float64) + w["w_local"].astype(np.float64)[np.arange(SS)[None, :], cls].sum(1) + \
+    a64 = w["b1"].astype(np.float64) + _lookup(w["w_local"], cls) + \
         coarse.reshape(T, C).astype(np.float64) @ w["w_coarse"].astype(np.float64)
+    # the network in float64 (_policy_ref.outputs_f64 gathers, which T rows at radius 31 do not allow)
+    out64 = np.maximum(a64, 0) @ w["w_out"].astype(np.float64) + w["b2"].astype(np.float64)
 
-    def lp(l):
+    def lp(l, a):
         z = l - l.max(1, keepdims=True)
-        return (z - np.log(np.exp(z).sum(1, keepdims=True)))[np.arange(T), action]
+        return (z - np.log(np.exp(z).sum(1, keepdims=True)))[np.arange(T), a]
 
-    for _ in range(50):
-        dw, db = rng.standard_normal(w["w_out"].shape) / np.sqrt(d["hidden"]), rng.standard_normal(10)
-        delta = (np.maximum(a64, 0) @ dw + db)[:, :9]
-        ratios = lambda scale: np.exp(lp(out64[:, :9]) - lp(out64[:, :9] - scale * delta))
-        lo, hi = 0.0, 8.0
-        for _ in range(40):
-            mid = 0.5 * (lo + hi)
-            r = ratios(mid)
-            lo, hi = (mid, hi) if ((r < 1 - clip_coef) | (r > 1 + clip_coef)).mean() < 0.45 else (lo, mid)
-        r = ratios(lo)
-        if min((r < 1 - clip_coef).mean(), (r > 1 + clip_coef).mean()) >= 0.12:
-            break
-    rec["logits"] = (out64[:, :9] - lo * delta).astype(np.float32)
-    _, _, pre, ratio = loss_and_grad(w, d, rec, adv, ret, np.arange(T), clip_coef)
+    old = np.zeros((T, agent.n_logits), np.float64)
+    off = 0
+    for h, n in enumerate(heads):
+        new = out64[:, off:off + n]
+        # the old policy of this head: its weights perturbed, at the scale at which about 45 % of its ratios are
+        # clipped; a draw that leaves less than 12 % on either side is drawn again
+        for _ in range(50):
+            m = n + DRAW_EXTRA[agent]
+            dw, db = rng.standard_normal((d["hidden"], m)) / np.sqrt(d["hidden"]), rng.standard_normal(m)
+            delta = (np.maximum(a64, 0) @ dw + db)[:, :n]
+            ratios = lambda scale: np.exp(lp(new, action[:, h]) - lp(new - scale * delta, action[:, h]))
+            lo, hi = 0.0, 8.0
+            for _ in range(40):
+                mid = 0.5 * (lo + hi)
+                r = ratios(mid)
+                lo, hi = (mid, hi) if ((r < 1 - clip_coef) | (r > 1 + clip_coef)).mean() < 0.45 else (lo, mid)
+            r = ratios(lo)
+            if min((r < 1 - clip_coef).mean(), (r > 1 + clip_coef).mean()) >= 0.12:
+                break
+        old[:, off:off + n] = new - lo * delta
+        off += n
+    if len(heads) == 1:
+        action = action[:, 0]
+    rec = {"local": local, "coarse": coarse, "action": action, "logits": old.astype(np.float32)}
+    _, _, pre, ratio = loss_and_grad(w, d, rec, adv, ret, np.arange(T), heads, clip_coef)
     ok = decided(pre, pre_bound(w, d, rec), ratio, clip_coef)
     for a in (local, coarse, action, adv, ret, rec["logits"]):
         a.setflags(write=False)
-    return dict(d=d, w=w, rec=rec, adv=adv, ret=ret, rows=np.flatnonzero(ok), ratio=ratio, T=T, clip_coef=clip_coef)
+    return dict(agent=agent, d=d, w=w, rec=rec, adv=adv, ret=ret, rows=np.flatnonzero(ok), ratio=ratio, T=T,
+                clip_coef=clip_coef)
+
+
+def check_case(c):
+    """What keeps a case honest; the tests assert it, and a seed that misses any of it is replaced (SEEDS)."""
+    cc, heads = c["clip_coef"], c["agent"].heads
+    assert len(c["rows"]) >= 0.9 * c["T"], "more than 10 % of the samples are undecided: pick another seed"
+    for h in range(len(heads)):
+        r = c["ratio"][c["rows"], h]
+        shares = ((r < 1 - cc).mean(), (r > 1 + cc).mean(), ((r >= 1 - cc) & (r <= 1 + cc)).mean())
+        assert min(shares) >= 0.1, (h, shares)
+    assert 3 in c["rows"] and c["rec"]["local"][3, 0, 0] == 7, "row 3 (the class byte 7) is undecided: another seed"
+    assert (c["adv"] > 0).any() and (c["adv"] < 0).any() and c["rec"]["local"].max() == 7
+    a = c["rec"]["action"]
+    assert a.shape == ((c["T"],) if len(heads) == 1 else (c["T"], len(heads)))
+    assert all(set(np.unique(a.reshape(c["T"], -1)[:, h])) == set(range(n)) for h, n in enumerate(heads))
 
 
 def minibatch(c, N, seed=0):
@@ -197,10 +264,11 @@ def minibatch(c, N, seed=0):
 
 
 def kernel_tile(lib, c):
-    """The kernels' sample tile, read off the library itself (nothing restates the constant): the workspace holds whole
-    tiles, so the tile is the largest N that needs no more than N = 1 does."""
-    s, keep = pref.policy_struct(c["w"], c["d"])
-    q = lambda N: lib.gca_helicopter_policy_grad_workspace(ctypes.byref(s), c["d"]["C"], N)
+    """The kernels' sample tile, read off the library itself through the agent's workspace query (nothing restates the
+    constant): the workspace holds whole tiles, so the tile is the largest N that needs no more than N = 1 does."""
+    s, keep = P.policy_struct(c["w"], c["d"])
+    query = getattr(lib, c["agent"].entry + "_grad_workspace")
+    q = lambda N: query(ctypes.byref(s), c["d"]["C"], N)
     N = 1
     while q(N + 1) == q(1):
         N += 1
@@ -229,17 +297,18 @@ def assert_within(got, torch32, where):
 
 
 # ------------------------------------------------------------------ the host build
-def host_grad(w, d, rec, adv, ret, idx, N=None, clip_coef=0.2, ent_coef=0.01, vf_coef=0.5, norm_adv=True, T=None,
-              ws_bytes=None, alias=None, ws_offset=0):
-    """gca_helicopter_policy_grad of the host build: (grads dict, stats), outputs prefilled with NaN."""
+def host_grad(agent, w, d, rec, adv, ret, idx, N=None, clip_coef=0.2, ent_coef=0.01, vf_coef=0.5, norm_adv=True,
+              T=None, ws_bytes=None, alias=None, ws_offset=0, null=None):
+    """The agent's <entry>_grad of the host build: (grads dict, stats), outputs prefilled with NaN. null: the name of a
+    record passed as a null pointer; alias: "outputs" or "weights", an output that overlaps one of them."""
     from gymca_amd import _lib
 
-    s, keep = pref.policy_struct(w, d)
+    s, keep = P.policy_struct(w, d)
     c = lambda a, t: np.ascontiguousarray(a, dtype=t)
-    local, coarse = c(rec["local"], np.uint8), c(rec["coarse"], np.float32)
-    action, logits = c(rec["action"], np.int32), c(rec["logits"], np.float32)
-    adv, ret = c(adv, np.float32), c(ret, np.float32)
-    Tn = action.size if T is None else T
+    records = {"local": c(rec["local"], np.uint8), "coarse": c(rec["coarse"], np.float32),
+               "action": c(rec["action"], np.int32), "logits": c(rec["logits"], np.float32),
+               "advantage": c(adv, np.float32), "returns": c(ret, np.float32)}
+    Tn = records["action"].size // len(agent.heads) if T is None else T
     idx = None if idx is None else c(idx, np.int32)
     N = (Tn if idx is None else idx.size) if N is None else N
     grads = {k: np.full(np.asarray(w[k]).shape, np.nan, np.float32) for k in GRADS}
@@ -248,10 +317,12 @@ def host_grad(w, d, rec, adv, ret, idx, N=None, clip_coef=0.2, ent_coef=0.01, vf
     if alias == "weights":
         grads["w_out"] = keep["w_out"]
     stats = np.full(8, np.nan, np.float32)
-    need = _lib.load_cpu().gca_helicopter_policy_grad_workspace(ctypes.byref(s), d["C"], max(N, 1))
+    need = getattr(_lib.load_cpu(), agent.entry + "_grad_workspace")(ctypes.byref(s), d["C"], max(N, 1))
     ws = np.zeros(max(need if ws_bytes is None else ws_bytes, 16) + 16, np.uint8)[ws_offset:]
     p = lambda a: None if a is None else a.ctypes.data
-    _lib.call_cpu("gca_helicopter_policy_grad", ctypes.byref(s), d["C"], p(local), p(coarse), p(action), p(logits),
-                  p(adv), p(ret), Tn, p(idx), N, clip_coef, ent_coef, vf_coef, 1 if norm_adv else 0,
-                  *[p(grads[k]) for k in GRADS], p(stats), p(ws), need if ws_bytes is None else ws_bytes, None)
+    if null is not None:
+        records[null] = None
+    _lib.call_cpu(agent.entry + "_grad", ctypes.byref(s), d["C"], *[p(records[k]) for k in records], Tn, p(idx), N,
+                  clip_coef, ent_coef, vf_coef, 1 if norm_adv else 0, *[p(grads[k]) for k in GRADS], p(stats), p(ws),
+                  need if ws_bytes is None else ws_bytes, None)
     return grads, stats

@@ -1,52 +1,20 @@
-"""CPU: the bulldozer's PPO step of the host build (gca_bulldozer_policy_grad, gca_bulldozer_policy_grad_workspace): the
-per-head loss gradient against the float64 autograd yardstick of tests/_bulldozer_ppo_ref.py within 4 x the error of
-torch's own float32 autograd, the reduction to the helicopter's one-head loss in closed form, the argument errors and
-their messages, and BulldozerPolicy.ppo_grad / ppo_update on a device="cpu" policy."""
+"""CPU: what only the bulldozer's PPO step of the host build has (the gradient against the yardstick, the argument
+errors and the rest of what both agents share are in test_ppo_host.py): the reduction of the per-head loss to the
+helicopter's one-head loss in closed form, the device build refusing as the host build does, and
+BulldozerPolicy.ppo_grad / ppo_update on a device="cpu" policy."""
 import ctypes
 
 import numpy as np
 import pytest
 
 import _bulldozer_policy_ref as bref
-import _bulldozer_ppo_ref as B
 import _ppo_ref as R
+
+HELI, BDZ = R.HELI, R.BDZ
 
 
 def _bits(a):
     return np.ascontiguousarray(a).view(np.uint32)
-
-
-@pytest.mark.parametrize("shape", B.SHAPES)
-def test_host_gradient_against_the_float64_yardstick(shape):
-    c = B.case(shape)
-    B.check_case(c)
-    for N, norm_adv in ((1, True), (2, False), (65, True), (257, False), (1000, True)):
-        idx = B.minibatch(c, N)
-        args = (c["w"], c["d"], c["rec"], c["adv"], c["ret"], idx)
-        g64, s64, _, _ = B.loss_and_grad(*args, norm_adv=norm_adv)
-        g32, s32, _, _ = B.loss_and_grad(*args, norm_adv=norm_adv, dtype="float32")
-        grads, stats = B.host_grad(*args, norm_adv=norm_adv)
-        assert all(np.isfinite(g).all() for g in grads.values()) and np.isfinite(stats).all()
-        B.assert_within(B.errors(grads, stats, g64, s64), B.errors(g32, s32, g64, s64), f"{shape} N={N} {norm_adv}")
-        # a (cell, class) row the minibatch never selects is exactly zero
-        cls = c["rec"]["local"].reshape(c["T"], -1)[idx] & 3
-        absent = np.ones((c["d"]["SS"], 4), bool)
-        absent[np.arange(c["d"]["SS"])[None, :].repeat(N, 0), cls] = False
-        assert (grads["w_local"][absent] == 0).all() and (N > 2 or absent.any())
-        if N == 1:
-            assert stats[1] == 0 and stats[7] == 0  # the normalised advantage of one sample is zero
-    if shape == B.SHAPES[0]:  # idx = None is rows 0 .. N - 1
-        rows = np.arange(c["T"], dtype=np.int32)
-        a, sa = B.host_grad(c["w"], c["d"], c["rec"], c["adv"], c["ret"], None)
-        b, sb = B.host_grad(c["w"], c["d"], c["rec"], c["adv"], c["ret"], rows)
-        assert all(np.array_equal(_bits(a[k]), _bits(b[k])) for k in B.GRADS) and np.array_equal(_bits(sa), _bits(sb))
-
-
-def test_normalised_advantage_of_one_sample_is_zero():
-    c = B.case(B.SHAPES[0])
-    idx = B.minibatch(c, 1)
-    grads, stats = B.host_grad(c["w"], c["d"], c["rec"], c["adv"], c["ret"], idx, ent_coef=0.0, vf_coef=0.0)
-    assert stats[1] == 0 and stats[7] == 0 and all((g == 0).all() for g in grads.values())
 
 
 @pytest.mark.parametrize("norm_adv", [True, False])
@@ -58,7 +26,7 @@ def test_constant_shoot_logits_reduce_to_the_one_head_loss(norm_adv):
       pg = (pg_heli - mean A^) / 2, entropy = (ent_heli + ln 2) / 2, approx_kl = kl_heli / 2, clip = clip_heli / 2,
       v_loss = v_loss_heli; the move columns of g_w_out / g_b2 are half the helicopter's, the value column equal;
       g_b2[9] = -(1 / 2N) sum_s A^_s (1[shoot_s = 0] - 1/2) = -g_b2[10], the shoot columns of g_w_out likewise with h_s."""
-    ch = R.case(R.SHAPES[0])
+    ch = R.case(HELI, R.SHAPES[HELI][0])
     d, wh, T = ch["d"], ch["w"], ch["T"]
     w = bref.weights_from_helicopter(wh, seed=1)
     w["w_out"][:, 9:11] = 0
@@ -70,18 +38,18 @@ def test_constant_shoot_logits_reduce_to_the_one_head_loss(norm_adv):
            "logits": np.concatenate([ch["rec"]["logits"], np.full((T, 2), -0.3, np.float32)], 1)}
     idx = R.minibatch(ch, 257)
     ent_coef, vf_coef = 0.01, 0.5
-    gh, sh = R.host_grad(wh, d, ch["rec"], ch["adv"], ch["ret"], idx, norm_adv=norm_adv)
-    gb, sb = B.host_grad(w, d, rec, ch["adv"], ch["ret"], idx, norm_adv=norm_adv)
+    gh, sh = R.host_grad(HELI, wh, d, ch["rec"], ch["adv"], ch["ret"], idx, norm_adv=norm_adv)
+    gb, sb = R.host_grad(BDZ, w, d, rec, ch["adv"], ch["ret"], idx, norm_adv=norm_adv)
     A = ch["adv"][idx].astype(np.float64)
     if norm_adv:
         A = (A - A.mean()) / (A.std() + 1e-8)
     N = len(idx)
-    close = lambda got, want: np.all(np.abs(np.asarray(got, np.float64) - want) <= 2 * B.U * max(np.abs(want).max(), 1e-30)
-                                     + 2 * B.U * np.abs(want))
+    close = lambda got, want: np.all(np.abs(np.asarray(got, np.float64) - want) <= 2 * R.U * max(np.abs(want).max(), 1e-30)
+                                     + 2 * R.U * np.abs(want))
     pg, ent = (float(sh[1]) - A.mean()) / 2, (float(sh[3]) + np.log(2.0)) / 2
     want = np.array([pg - ent_coef * ent + vf_coef * float(sh[2]), pg, sh[2], ent, sh[4] / 2, sh[5] / 2, sh[6], sh[7]])
-    for i, k in enumerate(B.STATS):
-        assert abs(float(sb[i]) - want[i]) <= 8 * B.U * max(abs(want[i]), 1.0), (k, sb[i], want[i])  # O(1) figures
+    for i, k in enumerate(R.STATS):
+        assert abs(float(sb[i]) - want[i]) <= 8 * R.U * max(abs(want[i]), 1.0), (k, sb[i], want[i])  # O(1) figures
     g_shoot = -(A * ((shoot[idx] == 0) - 0.5)).sum() / (2 * N)
     assert close(gb["b2"][9], np.array(g_shoot)) and close(gb["b2"][10], np.array(-g_shoot)) and g_shoot != 0
     assert close(gb["b2"][:9], gh["b2"][:9].astype(np.float64) / 2) and close(gb["b2"][11], gh["b2"][9].astype(np.float64))
@@ -90,50 +58,10 @@ def test_constant_shoot_logits_reduce_to_the_one_head_loss(norm_adv):
     assert np.array_equal(gb["w_out"][:, 9], -gb["w_out"][:, 10]) and np.abs(gb["w_out"][:, 9]).max() > 0
     # the shoot columns of w_out are zero, so the hidden layer sees the move head at half weight and the value head
     # whole: without the value term its gradients are half the helicopter's
-    gh0, _ = R.host_grad(wh, d, ch["rec"], ch["adv"], ch["ret"], idx, norm_adv=norm_adv, vf_coef=0.0)
-    gb0, _ = B.host_grad(w, d, rec, ch["adv"], ch["ret"], idx, norm_adv=norm_adv, vf_coef=0.0)
+    gh0, _ = R.host_grad(HELI, wh, d, ch["rec"], ch["adv"], ch["ret"], idx, norm_adv=norm_adv, vf_coef=0.0)
+    gb0, _ = R.host_grad(BDZ, w, d, rec, ch["adv"], ch["ret"], idx, norm_adv=norm_adv, vf_coef=0.0)
     for k in ("w_local", "w_coarse", "b1"):
         assert close(gb0[k], gh0[k].astype(np.float64) / 2), k
-
-
-def test_argument_errors_and_their_messages():
-    from gymca_amd import GCAError, _lib
-
-    c = B.case(B.SHAPES[0])
-    w, d, rec, adv, ret, T = c["w"], c["d"], c["rec"], c["adv"], c["ret"], c["T"]
-    who = "argument: bulldozer_policy_grad: "
-
-    def refused(text, **kw):
-        with pytest.raises(GCAError) as e:
-            B.host_grad(kw.pop("w", w), kw.pop("d", d), rec, adv, ret, kw.pop("idx", None), **kw)
-        assert str(e.value).endswith(text), str(e.value)
-
-    for name in ("local", "coarse", "action", "logits", "advantage", "returns"):
-        refused(who + "null record", null=name)
-    refused(who + "workspace smaller than gca_bulldozer_policy_grad_workspace", ws_bytes=64)
-    refused(who + "workspace, w_local, w_coarse and b1 16-B aligned", ws_offset=4)
-    refused(who + "the outputs may alias neither each other nor the weights", alias="outputs")
-    refused(who + "the outputs may alias neither each other nor the weights", alias="weights")
-    refused(who + "idx outside [0, T)", idx=np.array([0, T], np.int32))
-    refused(who + "idx outside [0, T)", idx=np.array([-1], np.int32))
-    refused(who + "N <= T without idx", N=T + 1)
-    refused(who + "N >= 1", N=0)
-    refused(who + "1 <= T < 2^31", T=0)
-    refused(who + "clip_coef >= 0", clip_coef=-0.1)
-    refused(who + "policy.hidden must be a power of two in [32, 256]", d={**d, "hidden": 48})
-    # which check fires first when several fail; a refused call has written nothing
-    refused(who + "null record", null="action", N=T + 1, ws_bytes=64)
-    refused(who + "N <= T without idx", N=T + 1, ws_bytes=64)
-    # the workspace query: bytes, growing with N and larger than the helicopter's; < 0 with the message on an error
-    s, keep = bref.policy_struct(w, d)
-    lib = _lib.load_cpu()
-    q = lambda N: lib.gca_bulldozer_policy_grad_workspace(ctypes.byref(s), d["C"], N)
-    tile = B.kernel_tile(lib, c)
-    assert 0 < q(1) == q(tile) < q(tile + 1) < q(100000) and tile > 1
-    assert q(1) > lib.gca_helicopter_policy_grad_workspace(ctypes.byref(s), d["C"], 1)
-    assert q(0) == -1 and b"argument: bulldozer_policy_grad_workspace: radius in [0, 31]" in lib.gca_last_error()
-    assert {"gca_bulldozer_policy_grad", "gca_bulldozer_policy_grad_workspace"} <= set(_lib.CPU_BULLDOZER_POLICY_SYMBOLS)
-    assert len(_lib._SIGNATURES["gca_bulldozer_policy_grad"][0]) == 24
 
 
 def test_both_builds_refuse_alike_without_a_gpu():
@@ -141,7 +69,7 @@ def test_both_builds_refuse_alike_without_a_gpu():
     call (host pointers are never read: every call here is refused by an argument check)."""
     from gymca_amd import _lib
 
-    c = B.case(B.SHAPES[0])
+    c = R.case(BDZ, R.SHAPES[BDZ][0])
     s, keep = bref.policy_struct(c["w"], c["d"])
     A = lambda i: 0x5000000 + 0x100000 * i
     base = [ctypes.byref(s), c["d"]["C"], A(0), A(1), A(2), A(3), A(4), A(5), 16, None, 4, 0.2, 0.01, 0.5, 1, A(6), A(7),
@@ -164,8 +92,8 @@ def test_ppo_grad_python_surface_on_a_host_policy():
     from gymca_amd.forest_fire import ppo
     from gymca_amd.forest_fire.bulldozer import BulldozerPolicy
 
-    shape = B.SHAPES[0]
-    c = B.case(shape)
+    shape = R.SHAPES[BDZ][0]
+    c = R.case(BDZ, shape)
     r, Bk, Hd, H, W = shape
     pol = BulldozerPolicy((H, W), r, Bk, Hd, device="cpu").load(c["w"])
     assert pol.HEADS == (9, 2) and pol.N_LOGITS == 11 and pol.GRAD_ENTRY == "gca_bulldozer_policy_grad"
@@ -173,11 +101,11 @@ def test_ppo_grad_python_surface_on_a_host_policy():
     rec = {k: torch.from_numpy(v.copy()).reshape((K, E) + v.shape[1:]) for k, v in c["rec"].items()}
     assert rec["action"].shape == (K, E, 2) and rec["logits"].shape == (K, E, 11)
     adv, ret = torch.from_numpy(c["adv"].copy()).reshape(K, E), torch.from_numpy(c["ret"].copy()).reshape(K, E)
-    idx = torch.from_numpy(B.minibatch(c, 257))
+    idx = torch.from_numpy(R.minibatch(c, 257))
     grads, stats = pol.ppo_grad(rec, adv, ret, idx)
-    want, ws = B.host_grad(c["w"], c["d"], c["rec"], c["adv"], c["ret"], idx.numpy())
-    assert set(grads) == set(B.GRADS) and {k: tuple(v.shape) for k, v in grads.items()} == pol.weight_shapes()
-    assert all(np.array_equal(_bits(grads[k].numpy()), _bits(want[k])) for k in B.GRADS)
+    want, ws = R.host_grad(BDZ, c["w"], c["d"], c["rec"], c["adv"], c["ret"], idx.numpy())
+    assert set(grads) == set(R.GRADS) and {k: tuple(v.shape) for k, v in grads.items()} == pol.weight_shapes()
+    assert all(np.array_equal(_bits(grads[k].numpy()), _bits(want[k])) for k in R.GRADS)
     assert stats.dtype is torch.float32 and tuple(stats.shape) == (8,) and len(ppo.STATS) == 8
     assert np.array_equal(_bits(stats.numpy()), _bits(ws))
     # the caller's outputs and workspace; flattened records; an in-place update keeps the bound addresses
@@ -186,11 +114,11 @@ def test_ppo_grad_python_surface_on_a_host_policy():
     flat = {k: v.reshape((K * E,) + v.shape[2:]) for k, v in rec.items()}
     g2, s2 = pol.ppo_grad(flat, adv.reshape(-1), ret.reshape(-1), idx, grads_out=out, stats_out=st,
                           workspace=torch.empty(1 << 22, dtype=torch.uint8))
-    assert s2 is st and all(g2[k] is out[k] and torch.equal(out[k], grads[k]) for k in B.GRADS)
+    assert s2 is st and all(g2[k] is out[k] and torch.equal(out[k], grads[k]) for k in R.GRADS)
     # idx = None: all T rows in order
     ga, sa = pol.ppo_grad(rec, adv, ret)
     gb, sb = pol.ppo_grad(rec, adv, ret, torch.arange(c["T"], dtype=torch.int32))
-    assert all(torch.equal(ga[k], gb[k]) for k in B.GRADS) and torch.equal(sa, sb)
+    assert all(torch.equal(ga[k], gb[k]) for k in R.GRADS) and torch.equal(sa, sb)
     v0 = pol.version
     pol.w_out.add_(grads["w_out"], alpha=-0.1)
     g3, _ = pol.ppo_grad(rec, adv, ret, idx)
@@ -218,8 +146,8 @@ def test_ppo_update_on_a_host_policy_equals_the_hand_written_loop():
     from gymca_amd.forest_fire.bulldozer import BulldozerPolicy
     from gymca_amd.forest_fire.bulldozer.policy import WEIGHTS
 
-    shape = B.SHAPES[0]
-    c = B.case(shape)
+    shape = R.SHAPES[BDZ][0]
+    c = R.case(BDZ, shape)
     r, Bk, Hd, H, W = shape
 
     def setup():

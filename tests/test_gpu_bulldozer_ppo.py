@@ -1,19 +1,17 @@
-"""GPU: the bulldozer's PPO update on the device. BulldozerPolicy.ppo_grad (gca_bulldozer_policy_grad) against the
-float64 autograd yardstick of tests/_bulldozer_ppo_ref.py (the per-head loss) within 4 x the error of torch's own
-float32 autograd, and against the host build; every element written, exact zeros where no sample selects a class, equal
-bits across calls, idx=None, graph capture, several tiles per split; BulldozerPolicy.ppo_update against the hand-written
-loop, as one graph, its argument errors and twenty steps that lower the loss; and the loop end to end on an env's
-records with truncations inside the window. All on synthetic records of T = 1200 rows but the last."""
+"""GPU: what only the bulldozer's PPO update on the device has (ppo_grad against the yardstick, its reproducibility,
+capture and tile paths are in test_gpu_ppo.py, with the helicopter's): BulldozerPolicy.ppo_update against the
+hand-written loop, as one graph, its argument errors and twenty steps that lower the loss, on synthetic records of
+T = 1200 rows; and the loop end to end on an env's records with truncations inside the window."""
 import numpy as np
 import pytest
 
 import _adam_ref as A
 import _bulldozer_policy_ref as bref
-import _bulldozer_ppo_ref as B
 import _ppo_ref as R
 
 pytestmark = pytest.mark.gpu
 
+BDZ = R.BDZ
 EPOCHS, MINIBATCHES = 2, 2
 
 
@@ -38,128 +36,12 @@ def _records(device, c):
     return ({k: _dev(v, device) for k, v in c["rec"].items()}, _dev(c["adv"], device), _dev(c["ret"], device))
 
 
-def _nan_outputs(pol):
-    import torch
-
-    grads = {k: torch.full(s, float("nan"), device=pol.device) for k, s in pol.weight_shapes().items()}
-    return grads, torch.full((8,), float("nan"), device=pol.device)
-
-
-@pytest.mark.parametrize("shape", B.SHAPES)
-def test_ppo_grad_against_the_float64_yardstick(device, shape):
-    from gymca_amd import _lib
-
-    c = B.case(shape)
-    B.check_case(c)
-    pol = _policy(device, c)
-    rec, adv, ret = _records(device, c)
-    ts = B.kernel_tile(_lib.load(), c)  # the kernels' own sample tile
-    assert ts > 1
-    sizes = sorted({1, 2, ts - 1, ts, ts + 1, 257, 1000})
-    worst = {}
-    for N in sizes:
-        idx = B.minibatch(c, N)
-        assert idx[0] == 3 and (N < 257 or len(np.unique(idx)) < N)  # the class byte 7 is in; repeats
-        cls = c["rec"]["local"].reshape(c["T"], -1)[idx] & 3
-        if N >= 257:
-            assert all((cls == k).any() for k in range(4))
-        absent = np.ones((c["d"]["SS"], 4), bool)
-        absent[np.arange(c["d"]["SS"])[None, :].repeat(N, 0), cls] = False
-        for norm_adv in ((True, False) if N in (1, 1000, ts + 1) else (True,)):
-            args = (c["w"], c["d"], c["rec"], c["adv"], c["ret"], idx)
-            g64, s64, _, _ = B.loss_and_grad(*args, norm_adv=norm_adv)
-            g32, s32, _, _ = B.loss_and_grad(*args, norm_adv=norm_adv, dtype="float32")
-            gh, sh = B.host_grad(*args, norm_adv=norm_adv)
-            grads, stats = _nan_outputs(pol)
-            pol.ppo_grad(rec, adv, ret, _dev(idx, device), norm_adv=norm_adv, grads_out=grads, stats_out=stats)
-            got = {k: v.cpu().numpy() for k, v in grads.items()}
-            st = stats.cpu().numpy()
-            assert all(np.isfinite(g).all() for g in got.values()) and np.isfinite(st).all()
-            assert (got["w_local"][absent] == 0).all() and (N > 2 or absent.any())
-            where = f"{shape} N={N} norm_adv={norm_adv}"
-            e, e32 = B.errors(got, st, g64, s64), B.errors(g32, s32, g64, s64)
-            B.assert_within(e, e32, where)
-            B.assert_within(B.errors(got, st, {k: gh[k].astype(np.float64) for k in gh}, sh.astype(np.float64)), e32,
-                            where + " vs host")
-            for k in e:
-                worst[k] = max(worst.get(k, 0.0), e[k] / max(e32[k], B.FLOOR / B.MARGIN))
-            if N == 1 and norm_adv:
-                assert st[1] == 0 and st[7] == 0  # the normalised advantage of one sample is zero
-    print(f"{shape} worst kernel / max(torch-f32, floor / 4):", {k: round(v, 2) for k, v in worst.items()})
-
-
-@pytest.mark.parametrize("shape", [B.SHAPES[1], B.SHAPES[3]])
-def test_ppo_grad_is_reproducible_and_capturable(device, shape):
-    import torch
-
-    c = B.case(shape)
-    pol = _policy(device, c)
-    rec, adv, ret = _records(device, c)
-    idx = _dev(B.minibatch(c, 333), device)
-    g1, s1 = pol.ppo_grad(rec, adv, ret, idx)
-    g2, s2 = _nan_outputs(pol)
-    pol.ppo_grad(rec, adv, ret, idx, grads_out=g2, stats_out=s2)
-    assert all(torch.equal(g1[k].view(torch.int32), g2[k].view(torch.int32)) for k in g1)
-    assert torch.equal(s1.view(torch.int32), s2.view(torch.int32))
-    # idx = None is rows 0 .. T - 1 (undecided rows included: both calls take the same side of every kink)
-    ga, sa = pol.ppo_grad(rec, adv, ret, None)
-    gb, sb = pol.ppo_grad(rec, adv, ret, torch.arange(c["T"], dtype=torch.int32, device=device))
-    assert all(torch.equal(ga[k].view(torch.int32), gb[k].view(torch.int32)) for k in ga)
-    assert torch.equal(sa.view(torch.int32), sb.view(torch.int32))
-    # inside a graph capture: no allocation, no sync; the replay gives the same bits
-    g3, s3 = _nan_outputs(pol)
-    torch.cuda.synchronize(device)
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        pol.ppo_grad(rec, adv, ret, idx, grads_out=g3, stats_out=s3)
-    for t in list(g3.values()) + [s3]:
-        t.fill_(float("nan"))
-    graph.replay()
-    torch.cuda.synchronize(device)
-    assert all(torch.equal(g1[k].view(torch.int32), g3[k].view(torch.int32)) for k in g1)
-    assert torch.equal(s1.view(torch.int32), s3.view(torch.int32))
-    # a replaced tensor moves the version and is bound; an in-place update is seen without binding again
-    v0 = pol.version
-    pol.b2.add_(0.25)
-    g4, _ = pol.ppo_grad(rec, adv, ret, idx)
-    assert pol.version == v0 and not torch.equal(g4["b2"], g1["b2"])
-    pol.b2 = pol.b2 - 0.25
-    assert pol.version == v0 + 1
-    g5, _ = pol.ppo_grad(rec, adv, ret, idx)
-    assert torch.allclose(g5["b2"], g1["b2"], atol=1e-6)
-    with pytest.raises(ValueError, match="idx"):
-        pol.ppo_grad(rec, adv, ret, idx.cpu())
-
-
-def test_ppo_grad_many_tiles_per_split(device):
-    """Several tiles per split in wgrad (LDS staged again per tile, the split's running sum) and more than 256 tile
-    partials in reduce, on the two smallest networks: with at least three row blocks there are at most 341 splits, so
-    more than 341 tiles means more than one tile per split, whatever the shape."""
-    from gymca_amd import _lib
-
-    for shape in B.SHAPES[:2]:
-        c = B.case(shape)
-        ts = B.kernel_tile(_lib.load(), c)
-        N = 342 * ts + 5
-        idx = B.minibatch(c, N)
-        pol = _policy(device, c)
-        rec, adv, ret = _records(device, c)
-        args = (c["w"], c["d"], c["rec"], c["adv"], c["ret"], idx)
-        g64, s64, _, _ = B.loss_and_grad(*args)
-        g32, s32, _, _ = B.loss_and_grad(*args, dtype="float32")
-        grads, stats = _nan_outputs(pol)
-        pol.ppo_grad(rec, adv, ret, _dev(idx, device), grads_out=grads, stats_out=stats)
-        got = {k: v.cpu().numpy() for k, v in grads.items()}
-        assert all(np.isfinite(g).all() for g in got.values())
-        B.assert_within(B.errors(got, stats.cpu().numpy(), g64, s64), B.errors(g32, s32, g64, s64), f"{shape} N={N}")
-
-
 # ------------------------------------------------------------------ ppo_update
 def _setup(device, lr=2.5e-4):
     from gymca_amd.forest_fire import ppo
     from gymca_amd.forest_fire.bulldozer.policy import WEIGHTS
 
-    c = B.case(B.SHAPES[0])
+    c = R.case(BDZ, R.SHAPES[BDZ][0])
     pol = _policy(device, c)
     opt = ppo.Adam({n: getattr(pol, n) for n in WEIGHTS}, lr=lr)
     return (c, pol, opt) + _records(device, c)
@@ -258,7 +140,7 @@ def test_ppo_update_argument_errors(device):
 
 def test_twenty_full_batch_steps_lower_the_loss(device):
     """lr = 1e-3, the other hyper-parameters the defaults, 20 epochs of one minibatch of all T = 1200 rows of the
-    smallest shape. The float64 yardstick (autograd of _bulldozer_ppo_ref.loss_and_grad, optax restated in
+    smallest shape. The float64 yardstick (autograd of _ppo_ref.loss_and_grad, optax restated in
     _adam_ref.OptaxRef) takes the loss from 2.7400 to 0.3469, a factor 0.127; the host build gives 2.7400 -> 0.3469
     too. The assertion asks for less than half of the first loss."""
     from gymca_amd.forest_fire.bulldozer.policy import WEIGHTS
@@ -268,7 +150,7 @@ def test_twenty_full_batch_steps_lower_the_loss(device):
     losses = []
     for _ in range(20):
         cur = {k: gold.w[i] for i, k in enumerate(WEIGHTS)}
-        g, st, _, _ = B.loss_and_grad(cur, c["d"], c["rec"], c["adv"], c["ret"], np.arange(c["T"]))
+        g, st, _, _ = R.loss_and_grad(cur, c["d"], c["rec"], c["adv"], c["ret"], np.arange(c["T"]), BDZ.heads)
         losses.append(st[0])
         gold.step([g[k] for k in WEIGHTS])
     assert losses[-1] < 0.3 * losses[0], (losses[0], losses[-1])  # the yardstick's own margin
@@ -289,7 +171,7 @@ def test_rollout_gae_ppo_grad_end_to_end(device):
     from gymca_amd.forest_fire import ppo
     from gymca_amd.forest_fire.bulldozer import BatchedForestFireBulldozerEnv, BulldozerPolicy
 
-    r, Bk, Hd, H, W = shape = B.SHAPES[0]
+    r, Bk, Hd, H, W = shape = R.SHAPES[BDZ][0]
     d = bref.dims(*shape)
     E, K = 4, 6
     env = BatchedForestFireBulldozerEnv(E, H, W, device=device, seed=17, materialize_obs=False, t_move=0.3, t_shoot=0.25,
@@ -313,8 +195,8 @@ def test_rollout_gae_ppo_grad_end_to_end(device):
     grads, stats = pol.ppo_grad(rec, adv, ret)
     st = stats.cpu().numpy()
     rows = np.arange(K * E)
-    g64, s64, _, _ = B.loss_and_grad(w, d, host, want_a, want_r, rows)
-    g32, s32, _, _ = B.loss_and_grad(w, d, host, want_a, want_r, rows, dtype="float32")
+    g64, s64, _, _ = R.loss_and_grad(w, d, host, want_a, want_r, rows, BDZ.heads)
+    g32, s32, _, _ = R.loss_and_grad(w, d, host, want_a, want_r, rows, BDZ.heads, dtype="float32")
     # the weights are unchanged, so every ratio the kernel forms is 1 within rounding: nothing is clipped, and
     # approx_kl = mean((r - 1) - log r) ~ mean((r - 1)^2) / 2 bounds the kernel's own |ratio - 1| in the mean square;
     # 1e-10 is (1.4e-5)^2 / 2, a hundred roundings of a logit of a few units (the bound of test_gpu_ppo.py: the heads'
@@ -322,7 +204,7 @@ def test_rollout_gae_ppo_grad_end_to_end(device):
     assert st[5] == 0 and 0 <= st[4] < 1e-10, (st[4], st[5])
     # with ratio = 1 and normalised advantages pg is -mean(A^), zero but for rounding: an absolute figure
     assert abs(st[1]) < 1e-6 and abs(s64[1]) < 1e-6
-    e = B.errors({k: v.cpu().numpy() for k, v in grads.items()}, st, g64, s64)
-    e32 = B.errors(g32, s32, g64, s64)
+    e = R.errors({k: v.cpu().numpy() for k, v in grads.items()}, st, g64, s64)
+    e32 = R.errors(g32, s32, g64, s64)
     keep = ("loss", "v_loss", "entropy", "adv_mean", "adv_std", "b2", "w_out")  # w_local / w_coarse / b1: relu kinks
-    B.assert_within({k: e[k] for k in keep}, e32, "end to end")
+    R.assert_within({k: e[k] for k in keep}, e32, "end to end")

@@ -1,6 +1,6 @@
 """GPU: HelicopterPolicy.ppo_grad computes what it computed before its kernels were generalised over the head layout.
-tests/golden/helicopter_ppo_bits.npz holds the uint32 bits of the five gradients and of `stats` for _ppo_ref.SHAPES[1]
-and [5] with _ppo_ref.minibatch(c, 333), recorded on an MI355X at the commit before the generalisation (e66b18c). The
+tests/golden/helicopter_ppo_bits.npz holds the uint32 bits of the five gradients and of `stats` for the helicopter's
+_ppo_ref.SHAPES [1] and [5] with _ppo_ref.minibatch(c, 333), recorded on an MI355X at the commit before the generalisation (e66b18c). The
 head layout is a template parameter and the helicopter's instantiation runs the same operations in the same order, so
 the bits must be the same; a difference means the helicopter path was changed."""
 import numpy as np
@@ -18,7 +18,7 @@ def test_helicopter_ppo_grad_bits_are_the_parents(device, golden, si):
     from gymca_amd.forest_fire.helicopter import HelicopterPolicy
 
     want = golden("helicopter_ppo_bits")
-    c = R.case(R.SHAPES[si])
+    c = R.case(R.HELI, R.SHAPES[R.HELI][si])
     d = c["d"]
     pol = HelicopterPolicy((d["H"], d["W"]), d["radius"], d["block"], d["hidden"], device=device).load(c["w"])
     t = lambda a: torch.from_numpy(np.array(a)).to(device)

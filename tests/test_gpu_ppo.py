@@ -1,8 +1,9 @@
-"""GPU: the PPO update on the device. forest_fire.ppo.gae (gca_gae) against the host build bit for bit;
-HelicopterPolicy.ppo_grad (gca_helicopter_policy_grad) against the float64 autograd yardstick of tests/_ppo_ref.py
-within 4 x the error of torch's own float32 autograd (and against the host build), every element written, exact zeros
-where no sample selects a class, equal bits across calls, idx=None, graph capture, several tiles per split, and the loop
-end to end on an env's records."""
+"""GPU: the PPO update on the device, for both agents. forest_fire.ppo.gae (gca_gae) against the host build bit for
+bit; <Agent>Policy.ppo_grad (gca_<agent>_policy_grad) against the float64 autograd yardstick of tests/_ppo_ref.py (the
+per-head loss) within 4 x the error of torch's own float32 autograd (and against the host build), every element
+written, exact zeros where no sample selects a class, equal bits across calls, idx=None, graph capture, several tiles
+per split, and the helicopter's loop end to end on an env's records. All but the last on synthetic records of T = 1200
+rows. The bulldozer's ppo_update and its end-to-end loop are in test_gpu_bulldozer_ppo.py."""
 import numpy as np
 import pytest
 
@@ -19,7 +20,7 @@ def _bits(a):
 def _dev(a, device):
     import torch
 
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(device)
+    return None if a is None else torch.from_numpy(np.array(a)).to(device)
 
 
 @pytest.mark.parametrize("mode", [None, "ones", "random"])
@@ -47,10 +48,8 @@ def test_gae_equals_the_host_build(device, K, E, mode):
 
 
 def _policy(device, c):
-    from gymca_amd.forest_fire.helicopter import HelicopterPolicy
-
     d = c["d"]
-    return HelicopterPolicy((d["H"], d["W"]), d["radius"], d["block"], d["hidden"], device=device).load(c["w"])
+    return c["agent"].policy_class()((d["H"], d["W"]), d["radius"], d["block"], d["hidden"], device=device).load(c["w"])
 
 
 def _records(device, c):
@@ -64,24 +63,24 @@ def _nan_outputs(pol):
     return grads, torch.full((8,), float("nan"), device=pol.device)
 
 
-@pytest.mark.parametrize("shape", R.SHAPES)
-def test_ppo_grad_against_the_float64_yardstick(device, shape):
-    import torch
+# Each agent's own minibatch sizes beside those around the kernels' sample tile ts, and those that run without the
+# normalisation too (beside ts + 1): the union would only add time at radius 31.
+SIZES = {R.HELI: {1, 2, 63, 64, 65, 257, 1000}, R.BDZ: {1, 2, 257, 1000}}
+BOTH_NORMS = {R.HELI: {1, 65, 1000}, R.BDZ: {1, 1000}}
 
+
+@pytest.mark.parametrize("agent, shape", R.params())
+def test_ppo_grad_against_the_float64_yardstick(device, agent, shape):
     from gymca_amd import _lib
 
-    c = R.case(shape)
-    assert len(c["rows"]) >= 0.9 * c["T"], "more than 10 % of the samples are undecided: pick another seed"
-    r = c["ratio"][c["rows"]]
-    assert (r < 0.8).mean() >= 0.1 and (r > 1.2).mean() >= 0.1 and ((r >= 0.8) & (r <= 1.2)).mean() >= 0.1
-    assert (c["adv"] > 0).any() and (c["adv"] < 0).any() and c["rec"]["local"].max() == 7
+    c = R.case(agent, shape)
+    R.check_case(c)
     pol = _policy(device, c)
     rec, adv, ret = _records(device, c)
     ts = R.kernel_tile(_lib.load(), c)  # the kernels' own sample tile
     assert ts > 1
-    sizes = sorted({1, 2, 63, 64, 65, 257, 1000, ts - 1, ts, ts + 1})
     worst = {}
-    for N in sizes:
+    for N in sorted(SIZES[agent] | {ts - 1, ts, ts + 1}):
         idx = R.minibatch(c, N)
         assert idx[0] == 3 and (N < 257 or len(np.unique(idx)) < N)  # the class byte 7 is in; repeats
         cls = c["rec"]["local"].reshape(c["T"], -1)[idx] & 3
@@ -89,18 +88,18 @@ def test_ppo_grad_against_the_float64_yardstick(device, shape):
             assert all((cls == k).any() for k in range(4))
         absent = np.ones((c["d"]["SS"], 4), bool)
         absent[np.arange(c["d"]["SS"])[None, :].repeat(N, 0), cls] = False
-        for norm_adv in ((True, False) if N in (1, 65, 1000, ts + 1) else (True,)):
+        for norm_adv in ((True, False) if N in BOTH_NORMS[agent] | {ts + 1} else (True,)):
             args = (c["w"], c["d"], c["rec"], c["adv"], c["ret"], idx)
-            g64, s64, _, _ = R.loss_and_grad(*args, norm_adv=norm_adv)
-            g32, s32, _, _ = R.loss_and_grad(*args, norm_adv=norm_adv, dtype="float32")
-            gh, sh = R.host_grad(*args, norm_adv=norm_adv)
+            g64, s64, _, _ = R.loss_and_grad(*args, agent.heads, norm_adv=norm_adv)
+            g32, s32, _, _ = R.loss_and_grad(*args, agent.heads, norm_adv=norm_adv, dtype="float32")
+            gh, sh = R.host_grad(agent, *args, norm_adv=norm_adv)
             grads, stats = _nan_outputs(pol)
             pol.ppo_grad(rec, adv, ret, _dev(idx, device), norm_adv=norm_adv, grads_out=grads, stats_out=stats)
             got = {k: v.cpu().numpy() for k, v in grads.items()}
             st = stats.cpu().numpy()
             assert all(np.isfinite(g).all() for g in got.values()) and np.isfinite(st).all()
             assert (got["w_local"][absent] == 0).all() and (N > 2 or absent.any())
-            where = f"{shape} N={N} norm_adv={norm_adv}"
+            where = f"{agent} {shape} N={N} norm_adv={norm_adv}"
             e, e32 = R.errors(got, st, g64, s64), R.errors(g32, s32, g64, s64)
             R.assert_within(e, e32, where)
             R.assert_within(R.errors(got, st, {k: gh[k].astype(np.float64) for k in gh}, sh.astype(np.float64)), e32,
@@ -109,18 +108,17 @@ def test_ppo_grad_against_the_float64_yardstick(device, shape):
                 worst[k] = max(worst.get(k, 0.0), e[k] / max(e32[k], R.FLOOR / R.MARGIN))
             if N == 1 and norm_adv:
                 assert st[1] == 0 and st[7] == 0  # the normalised advantage of one sample is zero
-    print(f"{shape} worst kernel / max(torch-f32, floor / 4):", {k: round(v, 2) for k, v in worst.items()})
+    print(f"{agent} {shape} worst kernel / max(torch-f32, floor / 4):", {k: round(v, 2) for k, v in worst.items()})
 
 
-@pytest.mark.parametrize("shape", [R.SHAPES[1], R.SHAPES[5]])
-def test_ppo_grad_is_reproducible_and_capturable(device, shape):
+@pytest.mark.parametrize("agent, shape", R.params(pick={R.HELI: (1, 5), R.BDZ: (1, 3)}))
+def test_ppo_grad_is_reproducible_and_capturable(device, agent, shape):
     import torch
 
-    c = R.case(shape)
+    c = R.case(agent, shape)
     pol = _policy(device, c)
     rec, adv, ret = _records(device, c)
-    N = 333
-    idx = _dev(R.minibatch(c, N), device)
+    idx = _dev(R.minibatch(c, 333), device)
     g1, s1 = pol.ppo_grad(rec, adv, ret, idx)
     g2, s2 = _nan_outputs(pol)
     pol.ppo_grad(rec, adv, ret, idx, grads_out=g2, stats_out=s2)
@@ -181,8 +179,8 @@ def test_rollout_gae_ppo_grad_end_to_end(device):
     st = stats.cpu().numpy()
     host = {k: v.cpu().numpy() for k, v in rec.items()}
     rows = np.arange(K * E)
-    g64, s64, _, _ = R.loss_and_grad(w, d, host, want_a, want_r, rows)
-    g32, s32, _, _ = R.loss_and_grad(w, d, host, want_a, want_r, rows, dtype="float32")
+    g64, s64, _, _ = R.loss_and_grad(w, d, host, want_a, want_r, rows, R.HELI.heads)
+    g32, s32, _, _ = R.loss_and_grad(w, d, host, want_a, want_r, rows, R.HELI.heads, dtype="float32")
     # the weights are unchanged, so every ratio the kernel forms is 1 within rounding: nothing is clipped, and
     # approx_kl = mean((r - 1) - log r) ~ mean((r - 1)^2) / 2 bounds the kernel's own |ratio - 1| in the mean square;
     # 1e-10 is (1.4e-5)^2 / 2, a hundred roundings of a logit of a few units
@@ -195,24 +193,34 @@ def test_rollout_gae_ppo_grad_end_to_end(device):
     R.assert_within({k: e[k] for k in keep}, e32, "end to end")
 
 
-def test_ppo_grad_many_tiles_per_split(device):
+def _many_tiles(device, agent, picks):
     """The production path the small cases never reach: several tiles per split in wgrad (LDS staged again per tile,
     the split's running sum) and more than 256 tile partials in reduce. With at least three row blocks there are at
     most 341 splits, so more than 341 tiles means more than one tile per split, whatever the shape."""
     from gymca_amd import _lib
 
-    for shape in (R.SHAPES[1], R.SHAPES[5]):
-        c = R.case(shape)
+    for si in picks:
+        shape = R.SHAPES[agent][si]
+        c = R.case(agent, shape)
         ts = R.kernel_tile(_lib.load(), c)
         N = 342 * ts + 5
         idx = R.minibatch(c, N)
         pol = _policy(device, c)
         rec, adv, ret = _records(device, c)
         args = (c["w"], c["d"], c["rec"], c["adv"], c["ret"], idx)
-        g64, s64, _, _ = R.loss_and_grad(*args)
-        g32, s32, _, _ = R.loss_and_grad(*args, dtype="float32")
+        g64, s64, _, _ = R.loss_and_grad(*args, agent.heads)
+        g32, s32, _, _ = R.loss_and_grad(*args, agent.heads, dtype="float32")
         grads, stats = _nan_outputs(pol)
         pol.ppo_grad(rec, adv, ret, _dev(idx, device), grads_out=grads, stats_out=stats)
         got = {k: v.cpu().numpy() for k, v in grads.items()}
         assert all(np.isfinite(g).all() for g in got.values())
-        R.assert_within(R.errors(got, stats.cpu().numpy(), g64, s64), R.errors(g32, s32, g64, s64), f"{shape} N={N}")
+        R.assert_within(R.errors(got, stats.cpu().numpy(), g64, s64), R.errors(g32, s32, g64, s64),
+                        f"{agent} {shape} N={N}")
+
+
+def test_ppo_grad_many_tiles_per_split(device):  # the helicopter's, under the name it has always had
+    _many_tiles(device, R.HELI, (1, 5))
+
+
+def test_ppo_grad_many_tiles_per_split_bulldozer(device):  # its two smallest networks
+    _many_tiles(device, R.BDZ, (0, 1))

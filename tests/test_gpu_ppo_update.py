@@ -10,7 +10,7 @@ import _ppo_ref as R
 
 pytestmark = pytest.mark.gpu
 
-SHAPE = R.SHAPES[0]
+SHAPE = R.SHAPES[R.HELI][0]
 EPOCHS, MINIBATCHES = 2, 2
 
 
@@ -21,7 +21,7 @@ def _setup(device, lr=2.5e-4):
     from gymca_amd.forest_fire.helicopter import HelicopterPolicy
     from gymca_amd.forest_fire.helicopter.policy import WEIGHTS
 
-    c = R.case(SHAPE)
+    c = R.case(R.HELI, SHAPE)
     d = c["d"]
     pol = HelicopterPolicy((d["H"], d["W"]), d["radius"], d["block"], d["hidden"], device=device).load(c["w"])
     opt = ppo.Adam({n: getattr(pol, n) for n in WEIGHTS}, lr=lr)
@@ -132,7 +132,7 @@ def test_twenty_full_batch_steps_lower_the_loss(device):
     losses = []
     for _ in range(20):
         cur = {k: gold.w[i] for i, k in enumerate(WEIGHTS)}
-        g, st, _, _ = R.loss_and_grad(cur, c["d"], c["rec"], c["adv"], c["ret"], np.arange(c["T"]))
+        g, st, _, _ = R.loss_and_grad(cur, c["d"], c["rec"], c["adv"], c["ret"], np.arange(c["T"]), R.HELI.heads)
         losses.append(st[0])
         gold.step([g[k] for k in WEIGHTS])
     assert losses[-1] < 0.3 * losses[0], (losses[0], losses[-1])  # the yardstick's own margin

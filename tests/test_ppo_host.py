@@ -1,12 +1,20 @@
-"""CPU: the PPO update of the host build (gca_gae, gca_helicopter_policy_grad): the GAE recurrence against its numpy
-float32 restatement bit for bit, the loss gradient and statistics against a float64 autograd yardstick, every argument
-error with its message, the Python surface on a host policy. No GPU."""
+"""CPU: the PPO update of the host build for both agents (gca_gae, gca_<agent>_policy_grad and its workspace query):
+the GAE recurrence against its numpy float32 restatement bit for bit, the per-head loss gradient and statistics against
+the float64 autograd yardstick of tests/_ppo_ref.py within 4 x the error of torch's own float32 autograd, every argument
+error with its message, and the Python surface on a host policy. What only the bulldozer has is in
+test_bulldozer_ppo_host.py. No GPU."""
 import ctypes
 
 import numpy as np
 import pytest
 
+import _policy_ref as P
 import _ppo_ref as R
+
+agents = pytest.mark.parametrize("agent", R.AGENTS, ids=repr)
+# (N, norm_adv) of the gradient test, each agent's own
+BATCHES = {R.HELI: ((1, True), (2, False), (65, True), (1000, True), (1000, False)),
+           R.BDZ: ((1, True), (2, False), (65, True), (257, False), (1000, True))}
 
 
 def _bits(a):
@@ -51,19 +59,16 @@ def test_gae_python_surface_on_host_arrays():
     assert ppo.STATS == R.STATS
 
 
-@pytest.mark.parametrize("shape", R.SHAPES)
-def test_host_gradient_against_the_float64_yardstick(shape):
-    c = R.case(shape)
-    assert len(c["rows"]) >= 0.9 * c["T"], "more than 10 % of the samples are undecided: pick another seed"
-    r = c["ratio"][c["rows"]]
-    assert (r < 0.8).mean() >= 0.1 and (r > 1.2).mean() >= 0.1 and ((r >= 0.8) & (r <= 1.2)).mean() >= 0.1
-    assert (c["adv"] > 0).any() and (c["adv"] < 0).any() and c["rec"]["local"].max() == 7
-    for N, norm_adv in ((1, True), (2, False), (65, True), (1000, True), (1000, False)):
+@pytest.mark.parametrize("agent, shape", R.params())
+def test_host_gradient_against_the_float64_yardstick(agent, shape):
+    c = R.case(agent, shape)
+    R.check_case(c)
+    for N, norm_adv in BATCHES[agent]:
         idx = R.minibatch(c, N)
         args = (c["w"], c["d"], c["rec"], c["adv"], c["ret"], idx)
-        g64, s64, _, _ = R.loss_and_grad(*args, norm_adv=norm_adv)
-        g32, s32, _, _ = R.loss_and_grad(*args, norm_adv=norm_adv, dtype="float32")
-        grads, stats = R.host_grad(*args, norm_adv=norm_adv)
+        g64, s64, _, _ = R.loss_and_grad(*args, agent.heads, norm_adv=norm_adv)
+        g32, s32, _, _ = R.loss_and_grad(*args, agent.heads, norm_adv=norm_adv, dtype="float32")
+        grads, stats = R.host_grad(agent, *args, norm_adv=norm_adv)
         assert all(np.isfinite(g).all() for g in grads.values()) and np.isfinite(stats).all()
         R.assert_within(R.errors(grads, stats, g64, s64), R.errors(g32, s32, g64, s64), f"{shape} N={N} {norm_adv}")
         # a (cell, class) row the minibatch never selects is exactly zero
@@ -71,54 +76,78 @@ def test_host_gradient_against_the_float64_yardstick(shape):
         absent = np.ones((c["d"]["SS"], 4), bool)
         absent[np.arange(c["d"]["SS"])[None, :].repeat(N, 0), cls] = False
         assert (grads["w_local"][absent] == 0).all() and (N > 2 or absent.any())
-    # idx = None is rows 0 .. N - 1
-    rows = np.arange(c["T"], dtype=np.int32)
-    a, sa = R.host_grad(c["w"], c["d"], c["rec"], c["adv"], c["ret"], None)
-    b, sb = R.host_grad(c["w"], c["d"], c["rec"], c["adv"], c["ret"], rows)
-    assert all(np.array_equal(_bits(a[k]), _bits(b[k])) for k in R.GRADS) and np.array_equal(_bits(sa), _bits(sb))
+        if N == 1:
+            assert stats[1] == 0 and stats[7] == 0  # the normalised advantage of one sample is zero
+    # idx = None is rows 0 .. N - 1 (all T rows on the host: every helicopter shape, the bulldozer's smallest)
+    if agent is R.HELI or shape == R.SHAPES[agent][0]:
+        rows = np.arange(c["T"], dtype=np.int32)
+        a, sa = R.host_grad(agent, c["w"], c["d"], c["rec"], c["adv"], c["ret"], None)
+        b, sb = R.host_grad(agent, c["w"], c["d"], c["rec"], c["adv"], c["ret"], rows)
+        assert all(np.array_equal(_bits(a[k]), _bits(b[k])) for k in R.GRADS) and np.array_equal(_bits(sa), _bits(sb))
 
 
-def test_normalised_advantage_of_one_sample_is_zero():
-    c = R.case(R.SHAPES[0])
+def _one_sample(agent):
+    c = R.case(agent, R.SHAPES[agent][0])
     idx = R.minibatch(c, 1)
-    grads, stats = R.host_grad(c["w"], c["d"], c["rec"], c["adv"], c["ret"], idx, ent_coef=0.0, vf_coef=0.0)
+    grads, stats = R.host_grad(agent, c["w"], c["d"], c["rec"], c["adv"], c["ret"], idx, ent_coef=0.0, vf_coef=0.0)
     assert stats[1] == 0 and stats[7] == 0 and all((g == 0).all() for g in grads.values())
 
 
-def test_argument_errors_and_their_messages():
+def test_normalised_advantage_of_one_sample_is_zero():  # the helicopter's, under the name it has always had
+    _one_sample(R.HELI)
+
+
+def test_normalised_advantage_of_one_sample_is_zero_bulldozer():
+    _one_sample(R.BDZ)
+
+
+@agents
+def test_argument_errors_and_their_messages(agent):
     from gymca_amd import GCAError, _lib
 
-    c = R.case(R.SHAPES[0])
+    c = R.case(agent, R.SHAPES[agent][0])
     w, d, rec, adv, ret, T = c["w"], c["d"], c["rec"], c["adv"], c["ret"], c["T"]
-    who = "argument: helicopter_policy_grad: "
+    name = agent.entry[len("gca_"):]  # helicopter_policy, bulldozer_policy
+    who = f"argument: {name}_grad: "
 
     def refused(text, **kw):
         with pytest.raises(GCAError) as e:
-            R.host_grad(w, kw.pop("d", d), rec, adv, ret, kw.pop("idx", None), **kw)
+            R.host_grad(agent, kw.pop("w", w), kw.pop("d", d), rec, adv, ret, kw.pop("idx", None), **kw)
         assert str(e.value).endswith(text), str(e.value)
 
-    refused(who + "N <= T without idx", N=T + 1)
-    refused(who + "idx outside [0, T)", idx=np.array([0, T], np.int32))
-    refused(who + "idx outside [0, T)", idx=np.array([-1], np.int32))
-    refused(who + "workspace smaller than gca_helicopter_policy_grad_workspace", ws_bytes=64)
+    for record in ("local", "coarse", "action", "logits", "advantage", "returns"):
+        refused(who + "null record", null=record)
+    refused(who + f"workspace smaller than {agent.entry}_grad_workspace", ws_bytes=64)
+    refused(who + "workspace, w_local, w_coarse and b1 16-B aligned", ws_offset=4)
     refused(who + "the outputs may alias neither each other nor the weights", alias="outputs")
     refused(who + "the outputs may alias neither each other nor the weights", alias="weights")
+    refused(who + "idx outside [0, T)", idx=np.array([0, T], np.int32))
+    refused(who + "idx outside [0, T)", idx=np.array([-1], np.int32))
+    refused(who + "N <= T without idx", N=T + 1)
     refused(who + "N >= 1", N=0)
     refused(who + "1 <= T < 2^31", T=0)
     refused(who + "clip_coef >= 0", clip_coef=-0.1)
-    refused(who + "workspace, w_local, w_coarse and b1 16-B aligned", ws_offset=4)
-    refused("argument: helicopter_policy: hidden must be a power of two in [32, 256]", d={**d, "hidden": 48})
-    # which check fires first when several fail
+    # the one message the two entry points word differently
+    refused({R.HELI: "argument: helicopter_policy: hidden must be a power of two in [32, 256]",
+             R.BDZ: who + "policy.hidden must be a power of two in [32, 256]"}[agent], d={**d, "hidden": 48})
+    # which check fires first when several fail; a refused call has written nothing
+    refused(who + "null record", null="action", N=T + 1, ws_bytes=64)
     refused(who + "N <= T without idx", N=T + 1, ws_bytes=64)
     # the workspace query: bytes, growing with N; < 0 with the message on an argument error
-    s, keep = R.pref.policy_struct(w, d)
+    s, keep = P.policy_struct(w, d)
     lib = _lib.load_cpu()
-    q = lambda N: lib.gca_helicopter_policy_grad_workspace(ctypes.byref(s), d["C"], N)
+    q = lambda N: getattr(lib, agent.entry + "_grad_workspace")(ctypes.byref(s), d["C"], N)
     tile = R.kernel_tile(lib, c)
     assert 0 < q(1) == q(tile) < q(tile + 1) < q(100000) and tile > 1
-    assert q(0) == -1 and b"helicopter_policy_grad_workspace" in lib.gca_last_error()
-    assert {"gca_gae", "gca_helicopter_policy_grad", "gca_helicopter_policy_grad_workspace"} <= set(_lib.CPU_SYMBOLS)
-    assert len(_lib._SIGNATURES["gca_helicopter_policy_grad"][0]) == 24
+    assert q(0) == -1 and {R.HELI: b"helicopter_policy_grad_workspace",
+                           R.BDZ: b"argument: bulldozer_policy_grad_workspace: radius in [0, 31]"}[agent] \
+        in lib.gca_last_error()
+    assert len(_lib._SIGNATURES[agent.entry + "_grad"][0]) == 24
+    if agent is R.HELI:
+        assert {"gca_gae", "gca_helicopter_policy_grad", "gca_helicopter_policy_grad_workspace"} <= set(_lib.CPU_SYMBOLS)
+    else:  # two heads' partials: larger than the helicopter's on the same network
+        assert q(1) > lib.gca_helicopter_policy_grad_workspace(ctypes.byref(s), d["C"], 1)
+        assert {"gca_bulldozer_policy_grad", "gca_bulldozer_policy_grad_workspace"} <= set(_lib.CPU_BULLDOZER_POLICY_SYMBOLS)
 
 
 def test_ppo_grad_python_surface_on_a_host_policy():
@@ -127,8 +156,8 @@ def test_ppo_grad_python_surface_on_a_host_policy():
     from gymca_amd.forest_fire import ppo
     from gymca_amd.forest_fire.helicopter import HelicopterPolicy
 
-    shape = R.SHAPES[0]
-    c = R.case(shape)
+    shape = R.SHAPES[R.HELI][0]
+    c = R.case(R.HELI, shape)
     r, B, Hd, H, W = shape
     pol = HelicopterPolicy((H, W), r, B, Hd, device="cpu").load(c["w"])
     K, E = 4, c["T"] // 4
@@ -136,7 +165,7 @@ def test_ppo_grad_python_surface_on_a_host_policy():
     adv, ret = torch.from_numpy(c["adv"].copy()).reshape(K, E), torch.from_numpy(c["ret"].copy()).reshape(K, E)
     idx = torch.from_numpy(R.minibatch(c, 257))
     grads, stats = pol.ppo_grad(rec, adv, ret, idx)
-    want, ws = R.host_grad(c["w"], c["d"], c["rec"], c["adv"], c["ret"], idx.numpy())
+    want, ws = R.host_grad(R.HELI, c["w"], c["d"], c["rec"], c["adv"], c["ret"], idx.numpy())
     assert set(grads) == set(R.GRADS) and {k: tuple(v.shape) for k, v in grads.items()} == pol.weight_shapes()
     assert all(np.array_equal(_bits(grads[k].numpy()), _bits(want[k])) for k in R.GRADS)
     assert stats.dtype is torch.float32 and tuple(stats.shape) == (8,) and len(ppo.STATS) == 8
