@@ -210,6 +210,26 @@ static inline int gca_check_bdz_policy_act(const gca_bulldozer_policy* p, int C,
     return gca_check_policy_c(who, C);
 }
 
+// gca_advanced_policy_act: gca_policy_observation's conditions on the plane (parity NULL, both parts always built; the
+// radius and the block are the policy's, checked with it), the bulldozer policy's, and the action's stride
+static inline int gca_check_advanced_policy_act(const gca_bulldozer_policy* p, const void* grid, const void* pos,
+                                                const void* time_step, int E, int H, int W, int empty, int tree,
+                                                int fire, const void* action, int action_stride) {
+    const char* who = "advanced_policy_act";
+    if (const int st = gca_check_bdz_policy(who, p)) return st;
+    if (!grid) return gca_refuse(who, "grid is null");
+    if (!pos) return gca_refuse(who, "pos is null");
+    if (!time_step) return gca_refuse(who, "time_step is null");
+    if (!action) return gca_refuse(who, "action is null");
+    if (!(E > 0 && H > 0 && W > 0)) return gca_refuse(who, "E, H, W must be positive");
+    if (!((int64_t)H * W < (1 << 30))) return gca_refuse(who, "grid too large (H * W < 2^30)");
+    if (((empty | tree | fire) & ~0xFF) != 0) return gca_refuse(who, "the codes must be u8 values");
+    if (!(action_stride >= 2)) return gca_refuse(who, "action_stride >= 2");
+    const int64_t Hc = (H - 1) / p->block + 1, Wc = (W - 1) / p->block + 1;
+    if (2 * Hc * Wc > GCA_POLICY_C_MAX) return gca_refuse(who, "C = 2 Hc Wc, at most 15088");
+    return gca_check_policy_c(who, (int)(2 * Hc * Wc));
+}
+
 // ----------------------------------------------------------------- the PPO update
 static inline int gca_check_gae(const void* reward, const void* value, const void* next_value, int K, int E,
                                 const void* advantage, const void* returns) {

@@ -20,6 +20,8 @@
 //                     (gca_heli.hip, gca_policy_dev.h), in gca.h's summation order
 //   gca_bulldozer_policy_act  the bulldozer policy network alone (gca_policy_dev.h), in gca.h's summation order;
 //                     gca_bulldozer_policy_rollout needs the Windy CA and is in the device build only
+//   gca_advanced_policy_act  the Advanced env's observe-and-act (gca_adv_policy.hip) as the observation followed by
+//                     the bulldozer policy
 //   gca_gae / gca_helicopter_policy_grad(_workspace) / gca_bulldozer_policy_grad(_workspace)  the PPO update
 //                     (gca_ppo.hip): the GAE recurrence bit for bit, the loss gradient of either head layout in double
 //                     as a second yardstick
@@ -638,6 +640,39 @@ extern "C" int gca_bulldozer_policy_act(const gca_bulldozer_policy* p, int C, co
                              action + 2 * (size_t)e);
         if (logits) memcpy(logits + (size_t)e * 11, out, 11 * sizeof(float));
         if (value) value[e] = out[11];
+    }
+    return GCA_OK;
+}
+
+// The Advanced env's observe-and-act (gca.h "advanced policy") as the two host functions it is defined by: the
+// observation of the one plane, then the bulldozer policy on the widened time_step; a record the caller does not keep
+// lives in a vector.
+extern "C" int gca_advanced_policy_act(const gca_bulldozer_policy* policy, const uint8_t* grid, const int32_t* pos,
+                                       const int32_t* time_step, int E, int H, int W, int empty, int tree, int fire,
+                                       int env_offset, uint64_t policy_seed, int greedy, int32_t* action,
+                                       int action_stride, float* logits, float* value, uint8_t* local_out,
+                                       float* coarse_out, void*) {
+    if (const int st = gca_check_advanced_policy_act(policy, grid, pos, time_step, E, H, W, empty, tree, fire, action,
+                                                     action_stride))
+        return st;
+    const int B = policy->block, S = 2 * policy->radius + 1;
+    const int C = 2 * ((H + B - 1) / B) * ((W + B - 1) / B);
+    std::vector<uint8_t> loc(local_out ? 0 : (size_t)E * S * S);
+    std::vector<float> coa(coarse_out ? 0 : (size_t)E * C);
+    uint8_t* loc_p = local_out ? local_out : loc.data();
+    float* coa_p = coarse_out ? coarse_out : coa.data();
+    if (const int st = gca_policy_observation(grid, nullptr, nullptr, pos, E, H, W, empty, tree, fire, policy->radius, B,
+                                              0, loc_p, coa_p, nullptr))
+        return st;
+    std::vector<int64_t> se((size_t)E);
+    std::vector<int32_t> act(2 * (size_t)E);
+    for (int e = 0; e < E; ++e) se[e] = (int64_t)time_step[e];
+    if (const int st = gca_bulldozer_policy_act(policy, C, loc_p, coa_p, se.data(), nullptr, env_offset, policy_seed,
+                                                greedy, act.data(), logits, value, E, nullptr))
+        return st;
+    for (int e = 0; e < E; ++e) {
+        action[(size_t)e * action_stride] = act[2 * (size_t)e];
+        action[(size_t)e * action_stride + 1] = act[2 * (size_t)e + 1];
     }
     return GCA_OK;
 }

@@ -42,7 +42,7 @@ cell-update).
 import numpy as np
 
 from ... import _device as dev
-from ..._lib import AdvEnvParams, call
+from ..._lib import SLOT, AdvEnvParams, BoundCall, call
 from ..._seeding import env_integers
 from ..operators.ca_alexandridis import make_alex_params
 from .bulldozer import ACTION_SETS, bulldozer_timings
@@ -833,6 +833,233 @@ class AdvancedForestFireBulldozerEnv:
              dev.ptr(self.dous_bits), dev.ptr(self.pos),
              dev.ptr(init["pos"]), dev.ptr(self.accu), dev.ptr(self.wind_index), dev.ptr(init["wind_index"]), st)
         return self._obs(), self.reward, self.done.bool(), self.truncated, self._info()
+
+    # ------------------------------------------------------------------ the agent: observe, policy_act, rollout_policy
+    # (the other batched envs call it act(); here `act` is the tile activity map of the tiled step)
+    # The bulldozer agent of the batched Windy env (BulldozerPolicy, forest_fire.ppo) on this env. Out of scope: a third
+    # head for the extension choice (the network holds at most 12 outputs; rollout_policy takes a constant `extension`),
+    # retardant in the observation (ModifyJax writes `dousing`, not the grid, so the agent does not see where it has
+    # doused) and K steps in one launch (the CA step is HBM traffic, not launch-bound: DESIGN.md).
+    _POLICY_RECORDS = ("action", "logits", "value", "reward", "terminated", "truncated", "local", "coarse")
+    _POLICY_CALLS_MAX = 8
+
+    @property
+    def _dev_index(self):
+        return dev.device_index(self.device)
+
+    def _agent_state(self):
+        """The addresses the agent's pre-bound calls hold: a call bound to other ones is bound again."""
+        return (self.grid.data_ptr(), self.pos.data_ptr(), self.time_step.data_ptr())
+
+    def _bound(self, key, make, keep=None):
+        """The pre-bound call of `key`, bound again when the state tensors it reads were replaced or `keep` (a policy)
+        changed its tensors; at most _POLICY_CALLS_MAX of them, the one bound longest ago dropped first."""
+        calls = self.__dict__.setdefault("_agent_calls", {})
+        stamp = (self._agent_state(), None if keep is None else keep.version)
+        bc = calls.pop(key, None)
+        if bc is None or bc[0] != stamp or bc[1] is not keep:
+            while len(calls) >= self._POLICY_CALLS_MAX:
+                del calls[next(iter(calls))]
+            bc = (stamp, keep, make())
+        calls[key] = bc
+        return bc[2]
+
+    def observe(self, radius=16, block=16, local_out=None, coarse_out=None, form=0):
+        """The policy observation of every env in one launch (gca_policy_observation on the current plane): `local`,
+        uint8 (E, 2 radius + 1, 2 radius + 1), the classes of the cells around the bulldozer (0 other, 1 TREE, 2 FIRE, 3
+        outside the grid), and `coarse`, float32 (E, 2, ceil(H / block), ceil(W / block)), the TREE and the FIRE share
+        of every block x block tile. Given outputs (contiguous tensors of that dtype and shape on the env's device) are
+        written in place and returned; no sync. The dousing layer is not part of it. The call is pre-bound per (current
+        plane, radius, block, form)."""
+        import torch
+
+        from .. import policy_obs
+        from .._batched import check_tensor
+
+        radius, block, form = int(radius), int(block), int(form)
+        if not 0 <= radius <= 31:
+            raise ValueError("observe: radius must be in [0, 31]")
+        if not (1 <= block <= 64 and block & (block - 1) == 0):
+            raise ValueError("observe: block must be a power of two in [1, 64]")
+        if form not in (0, 1, 2):
+            raise ValueError("observe: form must be 0 (by shape), 1 (generic) or 2 (rows)")
+        ls, cs = policy_obs.output_shapes(self, radius, block)
+        di = self._dev_index
+        local_out = torch.empty(ls, dtype=torch.uint8, device=self.device) if local_out is None else \
+            check_tensor(local_out, torch.uint8, ls, di, "observe", "local_out")
+        coarse_out = torch.empty(cs, dtype=torch.float32, device=self.device) if coarse_out is None else \
+            check_tensor(coarse_out, torch.float32, cs, di, "observe", "coarse_out")
+        cur = self.cur
+        oc = self._bound(("observe", cur, radius, block, form), lambda: BoundCall(
+            "gca_policy_observation", dev.ptr(self.grid[cur]), None, None, dev.ptr(self.pos), self.num_envs, self.nrows,
+            self.ncols, self._empty, self._tree, self._fire, radius, block, form, SLOT, SLOT, SLOT,
+            keep=(self.grid, self.pos)))
+        oc(local_out.data_ptr(), coarse_out.data_ptr(), dev.raw_stream(di))
+        return local_out, coarse_out
+
+    def _check_policy(self, policy, who):
+        from .policy import BulldozerPolicy
+
+        if not isinstance(policy, BulldozerPolicy):
+            raise ValueError(f"{who}: policy must be a BulldozerPolicy")
+        if policy.shape != (self.nrows, self.ncols):
+            raise ValueError(f"{who}: the policy was built for a {policy.shape} grid, the env is "
+                             f"{(self.nrows, self.ncols)}")
+        if policy.device != self.device:
+            raise ValueError(f"{who}: the policy lives on {policy.device}, the env on {self.device}")
+        return policy
+
+    def _act(self, policy, seed, greedy, action, logits, value, local, coarse, fused):
+        """policy_act() after its checks: `action` a contiguous int32 (E, 2) or (E, 3) tensor, the others tensors or None (the
+        fused launch takes NULL for them; the pair allocates what it needs)."""
+        import torch
+
+        from .._batched import seed64
+
+        E, di = self.num_envs, self._dev_index
+        p = lambda t: None if t is None else t.data_ptr()
+        stride = int(action.shape[1])
+        if fused:
+            cur = self.cur
+            ac = self._bound(("act", cur, id(policy)), lambda: BoundCall(
+                "gca_advanced_policy_act", policy.struct, dev.ptr(self.grid[cur]), dev.ptr(self.pos),
+                dev.ptr(self.time_step), E, self.nrows, self.ncols, self._empty, self._tree, self._fire, self.env_offset,
+                SLOT, SLOT, SLOT, SLOT, SLOT, SLOT, SLOT, SLOT, SLOT,
+                keep=(self.grid, self.pos, self.time_step) + policy.tensors()), keep=policy)
+            ac(seed64(seed), 1 if greedy else 0, action.data_ptr(), stride, p(logits), p(value), p(local), p(coarse),
+               dev.raw_stream(di))
+            return
+        local, coarse = self.observe(policy.radius, policy.block, local, coarse)
+        pair = action if stride == 2 else torch.empty((E, 2), dtype=torch.int32, device=self.device)
+        call("gca_bulldozer_policy_act", policy.struct, policy.C, dev.ptr(local), dev.ptr(coarse),
+             dev.ptr(self.time_step.to(torch.int64)), None, self.env_offset, seed64(seed), 1 if greedy else 0,
+             dev.ptr(pair), p(logits), p(value), E, dev.raw_stream(di))
+        if pair is not action:
+            action[:, :2].copy_(pair)
+
+    def policy_act(self, policy, seed=0, greedy=False, action_out=None, logits_out=None, value_out=None,
+                   local_out=None, coarse_out=None, fused=True):
+        """The policy's (move, shoot) for every env on the env's current state, observation and network in ONE launch
+        (gca_advanced_policy_act: the coarse map is counted into the workgroup's LDS and never written out unless
+        `coarse_out` asks for it). policy: a BulldozerPolicy built for this grid shape on this device. Returns (action
+        int32 (E, 2), logits float32 (E, 11): nine move logits then two shoot logits, value float32 (E,)), written into
+        the given outputs or allocated. action_out may be (E, 2) or (E, 3): only columns 0 and 1 are written, the
+        extension choice in column 2 stays the caller's. local_out / coarse_out (observe(policy.radius, policy.block)'s
+        dtypes and shapes), when given, receive what the network saw. The draw is keyed by (seed, global env id, the
+        env's time_step), which conditional_reset keeps, so it never repeats within an env's life; greedy=True takes the
+        first maximum of each head. No env state changes: the value of the state after a rollout (the bootstrap) is free
+        of side effects. No sync.
+        fused=False runs the two calls the fused launch is defined by, observe() and then gca_bulldozer_policy_act on
+        time_step.to(int64): the same bits, the yardstick of the tests and of scripts/bench_advanced_policy.py."""
+        import torch
+
+        from .. import policy_obs
+        from .._batched import _is_kernel_tensor, check_tensor
+
+        policy = self._check_policy(policy, "policy_act")
+        E, di = self.num_envs, self._dev_index
+        ls, cs = policy_obs.output_shapes(self, policy.radius, policy.block)
+        if action_out is None:
+            action_out = torch.empty((E, 2), dtype=torch.int32, device=self.device)
+        elif not (_is_kernel_tensor(action_out, torch.int32, di) and tuple(action_out.shape) in ((E, 2), (E, 3))):
+            raise ValueError(f"policy_act: action_out must be a contiguous int32 ({E}, 2) or ({E}, 3) tensor on the env's "
+                             "device")
+        new = lambda dtype, shape: torch.empty(shape, dtype=dtype, device=self.device)
+        logits_out = new(torch.float32, (E, 11)) if logits_out is None else \
+            check_tensor(logits_out, torch.float32, (E, 11), di, "policy_act", "logits_out")
+        value_out = new(torch.float32, (E,)) if value_out is None else \
+            check_tensor(value_out, torch.float32, (E,), di, "policy_act", "value_out")
+        if local_out is not None:
+            check_tensor(local_out, torch.uint8, ls, di, "policy_act", "local_out")
+        if coarse_out is not None:
+            check_tensor(coarse_out, torch.float32, cs, di, "policy_act", "coarse_out")
+        self._act(policy, seed, greedy, action_out, logits_out, value_out, local_out, coarse_out, fused)
+        return action_out, logits_out, value_out
+
+    def policy_record_shapes(self, policy, K):
+        """{record name: (dtype, shape)} of rollout_policy(policy, K): the keys, dtypes and layout of
+        BatchedForestFireBulldozerEnv.rollout_policy's records."""
+        import torch
+
+        from .. import policy_obs
+
+        E, K = self.num_envs, int(K)
+        ls, cs = policy_obs.output_shapes(self, policy.radius, policy.block)
+        return {"action": (torch.int32, (K, E, 2)), "logits": (torch.float32, (K, E, 11)),
+                "value": (torch.float32, (K, E)), "reward": (torch.float64, (K, E)),
+                "terminated": (torch.uint8, (K, E)), "truncated": (torch.uint8, (K, E)),
+                "local": (torch.uint8, (K,) + ls), "coarse": (torch.float32, (K,) + cs)}
+
+    def rollout_policy(self, policy, K, seed=0, greedy=False, autoreset=True, extension=0, record=_POLICY_RECORDS,
+                       action_out=None, logits_out=None, value_out=None, reward_out=None, terminated_out=None,
+                       truncated_out=None, local_out=None, coarse_out=None):
+        """K closed-loop env steps of every env: bit for bit the loop, for k = 0 .. K - 1, of
+            policy_act(policy, seed, greedy) into row k  ->  step(action)  ->  row k of reward and terminated
+            ->  conditional_reset() when `autoreset`
+        -- a PPO collection loop's on-policy experience on the env the reference's agent trains on. Returns a dict of the
+        records named in `record` (and of every record whose output tensor is given) in the layout of
+        BatchedForestFireBulldozerEnv.rollout_policy, so forest_fire.ppo.gae and BulldozerPolicy.ppo_update take it
+        unchanged: action int32 (K, E, 2), logits float32 (K, E, 11), value float32 (K, E), reward float64 (K, E) (the
+        env's float32 reward widened, which is exact), terminated uint8 (K, E) (the step's `done`, taken before the
+        reset), truncated uint8 (K, E), all zero (the reference never truncates), local uint8 (K, E, S, S), coarse
+        float32 (K, E, 2, Hc, Wc). Row k's observation is of the state before step k, so after an episode's end row k + 1
+        is the new episode's. With enable_extensions the env's action is (move, shoot, `extension`), the third column
+        that constant for every env and step; the record keeps (move, shoot). Given outputs must be contiguous tensors of
+        policy_record_shapes(policy, K) on the env's device; with every one given the call issues launches only and
+        does not sync. It can be captured in a graph for an EVEN K only: the plane the step reads (`cur`) is host state
+        that alternates per step, and a replay must find it where the capture did; an odd K under capture raises."""
+        import torch
+
+        from .._batched import check_tensor
+
+        policy = self._check_policy(policy, "rollout_policy")
+        K = int(K)
+        if K < 0:
+            raise ValueError("rollout_policy: K >= 0")
+        if K % 2 and torch.cuda.is_current_stream_capturing():
+            raise ValueError("rollout_policy: a graph capture needs an even K (the current plane alternates per step)")
+        E, di = self.num_envs, self._dev_index
+        spec = self.policy_record_shapes(policy, K)
+        unknown = [r for r in record if r not in spec]
+        if unknown:
+            raise ValueError(f"rollout_policy: unknown records {unknown}; choose from {self._POLICY_RECORDS}")
+        given = {"action": action_out, "logits": logits_out, "value": value_out, "reward": reward_out,
+                 "terminated": terminated_out, "truncated": truncated_out, "local": local_out, "coarse": coarse_out}
+        recs = {}
+        for name in self._POLICY_RECORDS:
+            dtype, shape = spec[name]
+            if given[name] is not None:
+                recs[name] = check_tensor(given[name], dtype, shape, di, "rollout_policy", f"{name}_out")
+            elif name in record:
+                recs[name] = torch.empty(shape, dtype=dtype, device=self.device)
+        if K == 0:
+            return recs
+        if "truncated" in recs:
+            recs["truncated"].zero_()
+        row = lambda name, k: recs[name][k] if name in recs else None
+        ext = self.enable_extensions
+        a = None
+        if ext or "action" not in recs:
+            # the env's own action: (move, shoot, extension) with extensions, else where no record keeps the pair
+            a = self.__dict__.get("_agent_action")
+            if a is None or a.shape[1] != (3 if ext else 2):
+                a = self._agent_action = torch.zeros((E, 3 if ext else 2), dtype=torch.int32, device=self.device)
+            if ext:
+                a[:, 2].fill_(int(extension))
+        for k in range(K):
+            ak = recs["action"][k] if a is None else a
+            self._act(policy, seed, greedy, ak, row("logits", k), row("value", k), row("local", k), row("coarse", k),
+                      True)
+            if ext and "action" in recs:
+                recs["action"][k].copy_(ak[:, :2])
+            self.step(ak)
+            if "reward" in recs:
+                recs["reward"][k].copy_(self.reward)
+            if "terminated" in recs:
+                recs["terminated"][k].copy_(self.done)
+            if autoreset:
+                self.conditional_reset()
+        return recs
 
 
 def _per_env_bull(pos_bull, E):

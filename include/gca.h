@@ -768,6 +768,30 @@ int gca_bulldozer_policy_rollout(const gca_bulldozer_params* p, const gca_bulldo
                                  int32_t* pos, int32_t* counts, uint8_t* hit, double* reward, int64_t* steps_elapsed,
                                  int E, void* stream);
 
+/* ------------------------------------------ advanced policy (the bulldozer policy on the Advanced bulldozer env, the
+ * env the reference's PPO agent trains on: observe and act in one launch)
+ * The results are bit for bit those of two calls in sequence:
+ *   1. gca_policy_observation(grid, NULL, NULL, pos, E, H, W, empty, tree, fire, policy->radius, policy->block, 0,
+ *      local, coarse)
+ *   2. gca_bulldozer_policy_act(policy, C, local, coarse, steps_elapsed, NULL, env_offset, policy_seed, greedy, ...)
+ *      with steps_elapsed[e] = (int64)time_step[e] and C = 2 Hc Wc of (H, W, policy->block).
+ * The network, its summation order and both samplers are those of "bulldozer policy" above. The draw is
+ * Philox(((uint32)time_step[e], env_offset + e, 0, GCA_TAG_BPOLICY), policy_seed): the env's time_step advances by one
+ * per env step and is kept across its conditional reset, so a draw never repeats within an env's life.
+ * grid u8 [E][H][W] is the env's current plane, pos i32 [E][2], time_step i32 [E]. action i32 [E][action_stride],
+ * action_stride >= 2: only columns 0 (move) and 1 (shoot) are written, a third column (the env's extension choice)
+ * stays the caller's. logits f32 [E][11], value f32 [E], local_out u8 [E][S][S] and coarse_out f32 [E][C] are nullable;
+ * the last two record what the network saw. No env state changes.
+ * Always ONE launch, one 256-thread workgroup per env: the coarse map is counted straight into LDS (the observation's
+ * rows form where W = 256 / 512, block = 8 / 16 / 32, H % block == 0 and grid is 8-B aligned, else its generic form;
+ * same bytes), the window is read from the plane. No scratch, no allocation, no sync, no atomics: capturable. H * W <
+ * 2^30, C at most 15088, u8 codes; argument errors are reported before the launch. The host build runs the two host
+ * functions above in plain loops. */
+int gca_advanced_policy_act(const gca_bulldozer_policy* policy, const uint8_t* grid, const int32_t* pos,
+                            const int32_t* time_step, int E, int H, int W, int empty, int tree, int fire,
+                            int env_offset, uint64_t policy_seed, int greedy, int32_t* action, int action_stride,
+                            float* logits, float* value, uint8_t* local_out, float* coarse_out, void* stream);
+
 /* ------------------------------------------ PPO update (the learner's half of the reference's main loop:
  * agents/jax_ppo.py:932-984 compute_gae, :987-1043 ppo_loss and its gradient), on rollout_policy's records
  * gca_gae: reward f64 (K, E) and value f32 (K, E) as gca_helicopter_policy_rollout records them, next_value f32 (E) the
