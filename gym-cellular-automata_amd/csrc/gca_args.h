@@ -230,6 +230,61 @@ static inline int gca_check_advanced_policy_act(const gca_bulldozer_policy* p, c
     return gca_check_policy_c(who, (int)(2 * Hc * Wc));
 }
 
+// ----------------------------------------------------------------- the retardant observation (gca.h "advanced policy")
+// C2 = 3 Hc Wc + S*S, rounded up to even: the floats of one env's feature vector
+static inline int64_t gca_retardant_c2(int H, int W, int block, int radius) {
+    const int64_t Hc = (H - 1) / block + 1, Wc = (W - 1) / block + 1, S = 2 * radius + 1;
+    return (3 * Hc * Wc + S * S + 1) & ~(int64_t)1;
+}
+
+// what gca_advanced_policy_observation and gca_advanced_policy_act_retardant ask of the plane, its two retardant
+// layers and the position
+static inline int gca_check_retardant_state(const char* who, const void* grid, const void* dousing,
+                                            const void* dous_bits, const void* pos, int E, int H, int W, int empty,
+                                            int tree, int fire) {
+    if (!grid) return gca_refuse(who, "grid is null");
+    if (!dousing) return gca_refuse(who, "dousing is null");
+    if (!pos) return gca_refuse(who, "pos is null");
+    if (!(E > 0 && H > 0 && W > 0)) return gca_refuse(who, "E, H, W must be positive");
+    if (!((int64_t)H * W < (1 << 30))) return gca_refuse(who, "grid too large (H * W < 2^30)");
+    if (((empty | tree | fire) & ~0xFF) != 0) return gca_refuse(who, "the codes must be u8 values");
+    if (dous_bits && W % 16 != 0) return gca_refuse(who, "dous_bits needs W % 16 == 0");
+    if (((uintptr_t)dous_bits & 1u) != 0) return gca_refuse(who, "dous_bits must be 2-B aligned");
+    return GCA_OK;
+}
+
+static inline int gca_check_advanced_policy_observation(const void* grid, const void* dousing, const void* dous_bits,
+                                                        const void* pos, int E, int H, int W, int empty, int tree,
+                                                        int fire, int radius, int block, const void* local_out,
+                                                        const void* feat_out) {
+    const char* who = "advanced_policy_observation";
+    if (const int st = gca_check_retardant_state(who, grid, dousing, dous_bits, pos, E, H, W, empty, tree, fire))
+        return st;
+    if (!(local_out || feat_out)) return gca_refuse(who, "local_out or feat_out required");
+    if (!(radius >= 0 && radius <= 31)) return gca_refuse(who, "radius in [0, 31]");
+    if (!(block >= 1 && block <= 64 && (block & (block - 1)) == 0))
+        return gca_refuse(who, "block must be a power of two in [1, 64]");
+    if (!(gca_retardant_c2(H, W, block, radius) < (1ll << 31)))
+        return gca_refuse(who, "feat too large (C2 = 3 Hc Wc + S*S < 2^31)");
+    return GCA_OK;
+}
+
+static inline int gca_check_advanced_policy_act_retardant(const gca_bulldozer_policy* p, const void* grid,
+                                                          const void* dousing, const void* dous_bits, const void* pos,
+                                                          const void* time_step, int E, int H, int W, int empty,
+                                                          int tree, int fire, const void* action, int action_stride) {
+    const char* who = "advanced_policy_act_retardant";
+    if (const int st = gca_check_bdz_policy(who, p)) return st;
+    if (!time_step) return gca_refuse(who, "time_step is null");
+    if (!action) return gca_refuse(who, "action is null");
+    if (const int st = gca_check_retardant_state(who, grid, dousing, dous_bits, pos, E, H, W, empty, tree, fire))
+        return st;
+    if (!(action_stride >= 2)) return gca_refuse(who, "action_stride >= 2");
+    if (gca_retardant_c2(H, W, p->block, p->radius) > GCA_POLICY_C_MAX)
+        return gca_refuse(who, "C2 = 3 Hc Wc + S*S rounded up to even, at most 15088");
+    return GCA_OK;
+}
+
 // ----------------------------------------------------------------- the PPO update
 static inline int gca_check_gae(const void* reward, const void* value, const void* next_value, int K, int E,
                                 const void* advantage, const void* returns) {

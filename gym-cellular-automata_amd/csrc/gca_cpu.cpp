@@ -22,6 +22,8 @@
 //                     gca_bulldozer_policy_rollout needs the Windy CA and is in the device build only
 //   gca_advanced_policy_act  the Advanced env's observe-and-act (gca_adv_policy.hip) as the observation followed by
 //                     the bulldozer policy
+//   gca_advanced_policy_observation / gca_advanced_policy_act_retardant  the same with the env's retardant in the
+//                     observation (gca_adv_policy.hip), pinned by tests/_retardant_obs_ref.py
 //   gca_gae / gca_helicopter_policy_grad(_workspace) / gca_bulldozer_policy_grad(_workspace)  the PPO update
 //                     (gca_ppo.hip): the GAE recurrence bit for bit, the loss gradient of either head layout in double
 //                     as a second yardstick
@@ -668,6 +670,79 @@ extern "C" int gca_advanced_policy_act(const gca_bulldozer_policy* policy, const
     std::vector<int32_t> act(2 * (size_t)E);
     for (int e = 0; e < E; ++e) se[e] = (int64_t)time_step[e];
     if (const int st = gca_bulldozer_policy_act(policy, C, loc_p, coa_p, se.data(), nullptr, env_offset, policy_seed,
+                                                greedy, act.data(), logits, value, E, nullptr))
+        return st;
+    for (int e = 0; e < E; ++e) {
+        action[(size_t)e * action_stride] = act[2 * (size_t)e];
+        action[(size_t)e * action_stride + 1] = act[2 * (size_t)e + 1];
+    }
+    return GCA_OK;
+}
+
+// The observation with the retardant in it (gca.h "advanced policy") in plain loops on `dousing`: the window and the
+// grid's two channels are gca_policy_observation's, copied into the head of each env's feature vector. dous_bits is
+// validated and not read.
+extern "C" int gca_advanced_policy_observation(const uint8_t* grid, const uint8_t* dousing, const uint16_t* dous_bits,
+                                               const int32_t* pos, int E, int H, int W, int empty, int tree, int fire,
+                                               int radius, int block, uint8_t* local_out, float* feat_out, void*) {
+    if (const int st = gca_check_advanced_policy_observation(grid, dousing, dous_bits, pos, E, H, W, empty, tree, fire,
+                                                             radius, block, local_out, feat_out))
+        return st;
+    const int S = 2 * radius + 1, Hc = (H + block - 1) / block, Wc = (W + block - 1) / block;
+    const int64_t HW = (int64_t)H * W, HcWc = (int64_t)Hc * Wc, C2 = gca_retardant_c2(H, W, block, radius);
+    std::vector<float> coa(feat_out ? (size_t)E * 2 * HcWc : 0);
+    if (const int st = gca_policy_observation(grid, nullptr, nullptr, pos, E, H, W, empty, tree, fire, radius, block, 0,
+                                              local_out, feat_out ? coa.data() : nullptr, nullptr))
+        return st;
+    if (!feat_out) return GCA_OK;
+    const float inv = 1.0f / (float)(block * block);
+    for (int e = 0; e < E; ++e) {
+        const uint8_t* d = dousing + e * HW;
+        float* f = feat_out + e * C2;
+        memcpy(f, coa.data() + (size_t)e * 2 * HcWc, (size_t)(2 * HcWc) * sizeof(float));
+        for (int bi = 0; bi < Hc; ++bi)
+            for (int bj = 0; bj < Wc; ++bj) {
+                const int r1 = (bi + 1) * block < H ? (bi + 1) * block : H;
+                const int c1 = (bj + 1) * block < W ? (bj + 1) * block : W;
+                int32_t cD = 0;
+                for (int r = bi * block; r < r1; ++r)
+                    for (int c = bj * block; c < c1; ++c) cD += d[(int64_t)r * W + c] != 0;
+                f[2 * HcWc + (int64_t)bi * Wc + bj] = (float)cD * inv;
+            }
+        for (int i = 0; i < S; ++i)
+            for (int j = 0; j < S; ++j) {
+                const int64_t r = (int64_t)pos[2 * e] - radius + i, c = (int64_t)pos[2 * e + 1] - radius + j;
+                const bool in = r >= 0 && r < H && c >= 0 && c < W;
+                f[3 * HcWc + i * S + j] = in && d[r * W + c] != 0 ? 1.0f : 0.0f;
+            }
+        if (3 * HcWc + S * S < C2) f[C2 - 1] = 0.0f;
+    }
+    return GCA_OK;
+}
+
+// gca_advanced_policy_act on that observation, as the two host functions it is defined by.
+extern "C" int gca_advanced_policy_act_retardant(const gca_bulldozer_policy* policy, const uint8_t* grid,
+                                                 const uint8_t* dousing, const uint16_t* dous_bits, const int32_t* pos,
+                                                 const int32_t* time_step, int E, int H, int W, int empty, int tree,
+                                                 int fire, int env_offset, uint64_t policy_seed, int greedy,
+                                                 int32_t* action, int action_stride, float* logits, float* value,
+                                                 uint8_t* local_out, float* feat_out, void*) {
+    if (const int st = gca_check_advanced_policy_act_retardant(policy, grid, dousing, dous_bits, pos, time_step, E, H, W,
+                                                               empty, tree, fire, action, action_stride))
+        return st;
+    const int S = 2 * policy->radius + 1;
+    const int C2 = (int)gca_retardant_c2(H, W, policy->block, policy->radius);
+    std::vector<uint8_t> loc(local_out ? 0 : (size_t)E * S * S);
+    std::vector<float> fea(feat_out ? 0 : (size_t)E * C2);
+    uint8_t* loc_p = local_out ? local_out : loc.data();
+    float* fea_p = feat_out ? feat_out : fea.data();
+    if (const int st = gca_advanced_policy_observation(grid, dousing, dous_bits, pos, E, H, W, empty, tree, fire,
+                                                       policy->radius, policy->block, loc_p, fea_p, nullptr))
+        return st;
+    std::vector<int64_t> se((size_t)E);
+    std::vector<int32_t> act(2 * (size_t)E);
+    for (int e = 0; e < E; ++e) se[e] = (int64_t)time_step[e];
+    if (const int st = gca_bulldozer_policy_act(policy, C2, loc_p, fea_p, se.data(), nullptr, env_offset, policy_seed,
                                                 greedy, act.data(), logits, value, E, nullptr))
         return st;
     for (int e = 0; e < E; ++e) {

@@ -289,6 +289,10 @@ _SIGNATURES = {
                                       P, c_int64, P, P, P, P, c_int, c_int, P, P, P, P, P, c_int, P], c_int),
     "gca_advanced_policy_act": ([POINTER(BulldozerPolicyStruct), P, P, P, c_int, c_int, c_int, c_int, c_int, c_int,
                                  c_int, c_uint64, c_int, P, c_int, P, P, P, P, P], c_int),
+    "gca_advanced_policy_observation": ([P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P],
+                                        c_int),
+    "gca_advanced_policy_act_retardant": ([POINTER(BulldozerPolicyStruct), P, P, P, P, P, c_int, c_int, c_int, c_int,
+                                           c_int, c_int, c_int, c_uint64, c_int, P, c_int, P, P, P, P, P], c_int),
     "gca_gae": ([P, P, P, P, c_float, c_float, c_int, c_int, P, P, P], c_int),
     "gca_helicopter_policy_grad_workspace": ([POINTER(HeliPolicy), c_int, c_int], c_int64),
     "gca_helicopter_policy_grad": ([POINTER(HeliPolicy), c_int, P, P, P, P, P, P, c_int64, P, c_int, c_float, c_float,
@@ -314,7 +318,8 @@ CPU_SYMBOLS = ("gca_last_error", "gca_version", "gca_philox", "gca_count_cells",
 # the bulldozer policy's network and its learner's step on host arrays (the closed-loop rollout needs the Windy CA:
 # device build only)
 CPU_BULLDOZER_POLICY_SYMBOLS = ("gca_bulldozer_policy_act", "gca_bulldozer_policy_grad_workspace",
-                                "gca_bulldozer_policy_grad", "gca_advanced_policy_act")
+                                "gca_bulldozer_policy_grad", "gca_advanced_policy_act",
+                                "gca_advanced_policy_observation", "gca_advanced_policy_act_retardant")
 
 _lib = None
 _lib_cpu = None

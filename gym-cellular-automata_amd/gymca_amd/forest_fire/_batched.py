@@ -144,6 +144,9 @@ class BatchedEnvBase:
     def _check_policy(self, policy, who):
         if not isinstance(policy, self._POLICY_CLASS):
             raise ValueError(f"{who}: policy must be a {self._POLICY_CLASS.__name__}")
+        if getattr(policy, "retardant", False):
+            raise ValueError(f"{who}: the policy was built with retardant=True, and this env has no retardant layer to "
+                             "observe (only AdvancedForestFireBulldozerEnv keeps one)")
         if policy.shape != (self.nrows, self.ncols):
             raise ValueError(f"{who}: the policy was built for a {policy.shape} grid, the env is "
                              f"{(self.nrows, self.ncols)}")

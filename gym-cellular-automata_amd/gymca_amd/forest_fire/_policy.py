@@ -31,6 +31,10 @@ class PolicyBase:
             return
         object.__setattr__(self, name, value)
 
+    def _coarse_len(self):
+        """C, the floats of the network's coarse part: the coarse map's 2 Hc Wc (a subclass may widen it)."""
+        return 2 * self.Hc * self.Wc
+
     def __init__(self, env_or_shape, radius=5, block=8, hidden=64, seed=0, device=None):
         import torch
 
@@ -53,7 +57,7 @@ class PolicyBase:
         self.shape, self.radius, self.block, self.hidden = (H, W), radius, block, hidden
         self.S = 2 * radius + 1
         self.Hc, self.Wc = -(-H // block), -(-W // block)
-        self.C = 2 * self.Hc * self.Wc
+        self.C = self._coarse_len()
         self.version = 0
         # a seeded draw on the scale of the reference agent's initialisation (orthogonal(sqrt 2) hidden layers, 0.01 on
         # the policy heads, a unit value head): normal entries of that standard deviation per fan-in, zero biases

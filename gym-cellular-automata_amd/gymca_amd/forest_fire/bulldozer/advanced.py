@@ -837,9 +837,11 @@ class AdvancedForestFireBulldozerEnv:
     # ------------------------------------------------------------------ the agent: observe, policy_act, rollout_policy
     # (the other batched envs call it act(); here `act` is the tile activity map of the tiled step)
     # The bulldozer agent of the batched Windy env (BulldozerPolicy, forest_fire.ppo) on this env. Out of scope: a third
-    # head for the extension choice (the network holds at most 12 outputs; rollout_policy takes a constant `extension`),
-    # retardant in the observation (ModifyJax writes `dousing`, not the grid, so the agent does not see where it has
-    # doused) and K steps in one launch (the CA step is HBM traffic, not launch-bound: DESIGN.md).
+    # head for the extension choice (the network holds at most 12 outputs; rollout_policy takes a constant `extension`;
+    # the extensions change the RGB frame, and this agent reads the true grid) and K steps in one launch (the CA step is
+    # HBM traffic, not launch-bound: DESIGN.md).
+    # ModifyJax writes the retardant into `dousing`, not into the grid: a BulldozerPolicy(retardant=True) sees it through
+    # the feature vector of observe(retardant=True), which takes the coarse map's place in every call and record below.
     _POLICY_RECORDS = ("action", "logits", "value", "reward", "terminated", "truncated", "local", "coarse")
     _POLICY_CALLS_MAX = 8
 
@@ -849,7 +851,8 @@ class AdvancedForestFireBulldozerEnv:
 
     def _agent_state(self):
         """The addresses the agent's pre-bound calls hold: a call bound to other ones is bound again."""
-        return (self.grid.data_ptr(), self.pos.data_ptr(), self.time_step.data_ptr())
+        return (self.grid.data_ptr(), self.pos.data_ptr(), self.time_step.data_ptr(), self.dousing.data_ptr(),
+                None if self.dous_bits is None else self.dous_bits.data_ptr())
 
     def _bound(self, key, make, keep=None):
         """The pre-bound call of `key`, bound again when the state tensors it reads were replaced or `keep` (a policy)
@@ -864,16 +867,29 @@ class AdvancedForestFireBulldozerEnv:
         calls[key] = bc
         return bc[2]
 
-    def observe(self, radius=16, block=16, local_out=None, coarse_out=None, form=0):
+    def _obs_shapes(self, radius, block, retardant):
+        """(local's shape, the shape of the network's coarse part) of observe(radius, block, retardant=retardant)."""
+        from .. import policy_obs
+
+        ls, cs = policy_obs.output_shapes(self, radius, block)
+        if retardant:
+            cs = (self.num_envs, (3 * cs[2] * cs[3] + ls[1] * ls[2] + 1) & ~1)
+        return ls, cs
+
+    def observe(self, radius=16, block=16, local_out=None, coarse_out=None, form=0, retardant=False):
         """The policy observation of every env in one launch (gca_policy_observation on the current plane): `local`,
         uint8 (E, 2 radius + 1, 2 radius + 1), the classes of the cells around the bulldozer (0 other, 1 TREE, 2 FIRE, 3
         outside the grid), and `coarse`, float32 (E, 2, ceil(H / block), ceil(W / block)), the TREE and the FIRE share
         of every block x block tile. Given outputs (contiguous tensors of that dtype and shape on the env's device) are
         written in place and returned; no sync. The dousing layer is not part of it. The call is pre-bound per (current
-        plane, radius, block, form)."""
+        plane, radius, block, form).
+        retardant=True puts the dousing layer in (gca_advanced_policy_observation, one launch as well): the second
+        tensor then is `feat`, float32 (E, C2), C2 = 3 Hc Wc + S*S rounded up to even -- the coarse map flattened, the
+        share of doused cells of every tile, one flag per window cell (1.0 where the cell is in the grid and doused)
+        and a zero pad word where needed; `coarse_out` takes a tensor of that shape. It reads the env's dousing bits
+        where the packed layout keeps them, else the uint8 layer; `form` must be 0."""
         import torch
 
-        from .. import policy_obs
         from .._batched import check_tensor
 
         radius, block, form = int(radius), int(block), int(form)
@@ -883,17 +899,26 @@ class AdvancedForestFireBulldozerEnv:
             raise ValueError("observe: block must be a power of two in [1, 64]")
         if form not in (0, 1, 2):
             raise ValueError("observe: form must be 0 (by shape), 1 (generic) or 2 (rows)")
-        ls, cs = policy_obs.output_shapes(self, radius, block)
+        if retardant and form:
+            raise ValueError("observe: retardant=True picks its kernel by shape (form must be 0)")
+        ls, cs = self._obs_shapes(radius, block, retardant)
         di = self._dev_index
         local_out = torch.empty(ls, dtype=torch.uint8, device=self.device) if local_out is None else \
             check_tensor(local_out, torch.uint8, ls, di, "observe", "local_out")
         coarse_out = torch.empty(cs, dtype=torch.float32, device=self.device) if coarse_out is None else \
             check_tensor(coarse_out, torch.float32, cs, di, "observe", "coarse_out")
         cur = self.cur
-        oc = self._bound(("observe", cur, radius, block, form), lambda: BoundCall(
-            "gca_policy_observation", dev.ptr(self.grid[cur]), None, None, dev.ptr(self.pos), self.num_envs, self.nrows,
-            self.ncols, self._empty, self._tree, self._fire, radius, block, form, SLOT, SLOT, SLOT,
-            keep=(self.grid, self.pos)))
+        if retardant:
+            oc = self._bound(("observe_retardant", cur, radius, block), lambda: BoundCall(
+                "gca_advanced_policy_observation", dev.ptr(self.grid[cur]), dev.ptr(self.dousing),
+                dev.ptr(self.dous_bits), dev.ptr(self.pos), self.num_envs, self.nrows, self.ncols, self._empty,
+                self._tree, self._fire, radius, block, SLOT, SLOT, SLOT,
+                keep=(self.grid, self.dousing, self.dous_bits, self.pos)))
+        else:
+            oc = self._bound(("observe", cur, radius, block, form), lambda: BoundCall(
+                "gca_policy_observation", dev.ptr(self.grid[cur]), None, None, dev.ptr(self.pos), self.num_envs,
+                self.nrows, self.ncols, self._empty, self._tree, self._fire, radius, block, form, SLOT, SLOT, SLOT,
+                keep=(self.grid, self.pos)))
         oc(local_out.data_ptr(), coarse_out.data_ptr(), dev.raw_stream(di))
         return local_out, coarse_out
 
@@ -919,6 +944,17 @@ class AdvancedForestFireBulldozerEnv:
         E, di = self.num_envs, self._dev_index
         p = lambda t: None if t is None else t.data_ptr()
         stride = int(action.shape[1])
+        if fused and policy.retardant:
+            cur = self.cur
+            ac = self._bound(("act_retardant", cur, id(policy)), lambda: BoundCall(
+                "gca_advanced_policy_act_retardant", policy.struct, dev.ptr(self.grid[cur]), dev.ptr(self.dousing),
+                dev.ptr(self.dous_bits), dev.ptr(self.pos), dev.ptr(self.time_step), E, self.nrows, self.ncols,
+                self._empty, self._tree, self._fire, self.env_offset, SLOT, SLOT, SLOT, SLOT, SLOT, SLOT, SLOT, SLOT, SLOT,
+                keep=(self.grid, self.dousing, self.dous_bits, self.pos, self.time_step) + policy.tensors()),
+                keep=policy)
+            ac(seed64(seed), 1 if greedy else 0, action.data_ptr(), stride, p(logits), p(value), p(local), p(coarse),
+               dev.raw_stream(di))
+            return
         if fused:
             cur = self.cur
             ac = self._bound(("act", cur, id(policy)), lambda: BoundCall(
@@ -929,7 +965,7 @@ class AdvancedForestFireBulldozerEnv:
             ac(seed64(seed), 1 if greedy else 0, action.data_ptr(), stride, p(logits), p(value), p(local), p(coarse),
                dev.raw_stream(di))
             return
-        local, coarse = self.observe(policy.radius, policy.block, local, coarse)
+        local, coarse = self.observe(policy.radius, policy.block, local, coarse, retardant=policy.retardant)
         pair = action if stride == 2 else torch.empty((E, 2), dtype=torch.int32, device=self.device)
         call("gca_bulldozer_policy_act", policy.struct, policy.C, dev.ptr(local), dev.ptr(coarse),
              dev.ptr(self.time_step.to(torch.int64)), None, self.env_offset, seed64(seed), 1 if greedy else 0,
@@ -950,15 +986,16 @@ class AdvancedForestFireBulldozerEnv:
         first maximum of each head. No env state changes: the value of the state after a rollout (the bootstrap) is free
         of side effects. No sync.
         fused=False runs the two calls the fused launch is defined by, observe() and then gca_bulldozer_policy_act on
-        time_step.to(int64): the same bits, the yardstick of the tests and of scripts/bench_advanced_policy.py."""
+        time_step.to(int64): the same bits, the yardstick of the tests and of scripts/bench_advanced_policy.py.
+        A policy built with retardant=True sees the dousing layer: the launch is gca_advanced_policy_act_retardant, the
+        pair observe(retardant=True) and the network, and `coarse_out` is the feature vector (E, policy.C)."""
         import torch
 
-        from .. import policy_obs
         from .._batched import _is_kernel_tensor, check_tensor
 
         policy = self._check_policy(policy, "policy_act")
         E, di = self.num_envs, self._dev_index
-        ls, cs = policy_obs.output_shapes(self, policy.radius, policy.block)
+        ls, cs = self._obs_shapes(policy.radius, policy.block, policy.retardant)
         if action_out is None:
             action_out = torch.empty((E, 2), dtype=torch.int32, device=self.device)
         elif not (_is_kernel_tensor(action_out, torch.int32, di) and tuple(action_out.shape) in ((E, 2), (E, 3))):
@@ -978,13 +1015,11 @@ class AdvancedForestFireBulldozerEnv:
 
     def policy_record_shapes(self, policy, K):
         """{record name: (dtype, shape)} of rollout_policy(policy, K): the keys, dtypes and layout of
-        BatchedForestFireBulldozerEnv.rollout_policy's records."""
+        BatchedForestFireBulldozerEnv.rollout_policy's records; `coarse` is (K, E, C2) for a retardant policy."""
         import torch
 
-        from .. import policy_obs
-
         E, K = self.num_envs, int(K)
-        ls, cs = policy_obs.output_shapes(self, policy.radius, policy.block)
+        ls, cs = self._obs_shapes(policy.radius, policy.block, policy.retardant)
         return {"action": (torch.int32, (K, E, 2)), "logits": (torch.float32, (K, E, 11)),
                 "value": (torch.float32, (K, E)), "reward": (torch.float64, (K, E)),
                 "terminated": (torch.uint8, (K, E)), "truncated": (torch.uint8, (K, E)),

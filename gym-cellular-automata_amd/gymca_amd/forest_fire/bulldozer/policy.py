@@ -26,10 +26,25 @@ class BulldozerPolicy(PolicyBase):
     N_LOGITS = N_LOGITS
     GRAD_ENTRY = "gca_bulldozer_policy_grad"
 
+    def __init__(self, env_or_shape, radius=5, block=8, hidden=64, seed=0, device=None, retardant=False):
+        """retardant=True: the policy of the Advanced env that sees the env's retardant. Its coarse part is the feature
+        vector of AdvancedForestFireBulldozerEnv.observe(radius, block, retardant=True) (include/gca.h
+        gca_advanced_policy_observation): C = C2 = 3 Hc Wc + S*S rounded up to even -- the coarse map, the retardant
+        share of every block, the window's retardant flags -- and w_coarse is (C2, hidden). Everything else, the learner
+        included, goes through `C` unchanged. With False nothing differs, down to the drawn weights."""
+        self.retardant = bool(retardant)
+        super().__init__(env_or_shape, radius, block, hidden, seed, device)
+
+    def _coarse_len(self):
+        if not self.retardant:
+            return super()._coarse_len()
+        return (3 * self.Hc * self.Wc + self.S * self.S + 1) & ~1
+
     def forward_torch(self, local, coarse, weights=None):
         """(move_logits (..., 9), shoot_logits (..., 2), value (...)) of the same network in differentiable torch ops: an
         embedding gather over the window's classes, a sum, and two matmuls. local (..., S, S) uint8, coarse
-        (..., 2, Hc, Wc) float32 with the same leading dims (for instance the (K, E) of rollout_policy's records).
+        (..., 2, Hc, Wc) float32 -- (..., C2) for a retardant policy -- with the same leading dims (for instance the
+        (K, E) of rollout_policy's records).
         weights: a dict of the five tensors to use instead of the policy's own (a trainer's leaf tensors, which then
         receive the gradients). The summation order is torch's, not the kernels': the results agree within rounding, not
         bit for bit."""

@@ -792,6 +792,49 @@ int gca_advanced_policy_act(const gca_bulldozer_policy* policy, const uint8_t* g
                             int env_offset, uint64_t policy_seed, int greedy, int32_t* action, int action_stride,
                             float* logits, float* value, uint8_t* local_out, float* coarse_out, void* stream);
 
+/* The observation with the retardant in it. On the Advanced env the agent's second head drops retardant, which the env
+ * keeps in its `dousing` layer and not in the grid (the reference's agent sees it in its RGB frame, whose colours are
+ * indexed [kind][dousing 0/1]: advanced_bulldozer.py:1041-1093); gca_policy_observation reads the grid alone. This one
+ * replaces it for that env: `local_out` u8 [E][S][S] is gca_policy_observation's window unchanged, and feat_out f32
+ * [E][C2], C2 = 3 Hc Wc + S*S rounded up to even, is the vector the network takes in the coarse map's place:
+ *   [0, 2 Hc Wc)               gca_policy_observation's coarse map, the same values in the same order
+ *   [2 Hc Wc, 3 Hc Wc)         block (bi, bj), row-major: the number of its in-grid cells with dousing != 0, times
+ *                              1 / block^2 (exact: a count of at most 4096 times a power of two)
+ *   [3 Hc Wc, 3 Hc Wc + S*S)   window cell n = i * S + j at (pos[e][0] - radius + i, pos[e][1] - radius + j): 1.0f if the
+ *                              cell is inside the grid and dousing != 0 there, else 0.0f
+ *   one more word, 0.0f, when 3 Hc Wc + S*S is odd
+ * dousing u8 [E][H][W]. dous_bits u16 [E][H][W / 16], nullable and allowed only when W % 16 == 0 (2-B aligned): bit
+ * c % 16 of word [r][c / 16] is set iff dousing[r][c] != 0, as the env's packed layout keeps it. With dous_bits the
+ * launch takes the retardant from the bits and does not read the u8 layer; without, it reads the u8 layer. The block
+ * counts come from the bits by popcount -- a dword of a bit row holds four, two or one tile rows at block 8 / 16 / 32
+ * (W % 32 == 0, 4-B aligned bits), any other shape masks the tile's bit range out of its words -- and from the u8 layer
+ * by byte loops; the grid's two channels come as in gca_advanced_policy_act. Either output may be NULL, not both;
+ * radius, block, the codes and H * W as gca_policy_observation; C2 < 2^31. ONE launch, a 256-thread workgroup per env,
+ * no allocation, no sync, no atomics: capturable. The host build runs plain loops on `dousing`; it validates dous_bits
+ * the same way and does not read it. Pinned by tests/_retardant_obs_ref.py. */
+int gca_advanced_policy_observation(const uint8_t* grid, const uint8_t* dousing, const uint16_t* dous_bits,
+                                    const int32_t* pos, int E, int H, int W, int empty, int tree, int fire, int radius,
+                                    int block, uint8_t* local_out, float* feat_out, void* stream);
+
+/* gca_advanced_policy_act on that observation: observe and act in one launch for a policy that sees the retardant. The
+ * results are bit for bit those of
+ *   1. gca_advanced_policy_observation(grid, dousing, dous_bits, pos, E, H, W, empty, tree, fire, policy->radius,
+ *      policy->block, local, feat)
+ *   2. gca_bulldozer_policy_act(policy, C2, local, feat, steps_elapsed, NULL, env_offset, policy_seed, greedy, ...) with
+ *      steps_elapsed[e] = (int64)time_step[e]
+ * The network is "bulldozer policy" with C = C2, so policy->w_coarse is f32 [C2][Hd]; its summation order depends on
+ * (S, C, Hd) only. The draw is keyed as gca_advanced_policy_act keys it. Only action columns 0 and 1 are written;
+ * logits, value, local_out and feat_out f32 [E][C2] are nullable. No env state changes.
+ * Always ONE launch, one 256-thread workgroup per env: the feature vector is built straight into the network's LDS
+ * words, every word by one thread, and is complete at the network's first barrier. No scratch, no atomics:
+ * capturable. C2 at most 15088 (the LDS of a workgroup), checked before the launch with the other arguments, which are
+ * those of the two calls. The host build runs the two host functions. */
+int gca_advanced_policy_act_retardant(const gca_bulldozer_policy* policy, const uint8_t* grid, const uint8_t* dousing,
+                                      const uint16_t* dous_bits, const int32_t* pos, const int32_t* time_step, int E,
+                                      int H, int W, int empty, int tree, int fire, int env_offset,
+                                      uint64_t policy_seed, int greedy, int32_t* action, int action_stride,
+                                      float* logits, float* value, uint8_t* local_out, float* feat_out, void* stream);
+
 /* ------------------------------------------ PPO update (the learner's half of the reference's main loop:
  * agents/jax_ppo.py:932-984 compute_gae, :987-1043 ppo_loss and its gradient), on rollout_policy's records
  * gca_gae: reward f64 (K, E) and value f32 (K, E) as gca_helicopter_policy_rollout records them, next_value f32 (E) the

@@ -13,8 +13,10 @@ update as two graphs and replays them; the draw is keyed by the env's time_step,
 draws new actions.
 
 The defaults are the reference's PPOArgs (lr 2.5e-4, clip 0.1, 4 epochs x 4 minibatches, 128 steps); clip_vloss stays
-off, as everywhere in this project. The extension choice is not the agent's (rollout_policy's `extension`), and the
-observation does not show the retardant. Needs a HIP device."""
+off, as everywhere in this project. The extension choice is not the agent's (rollout_policy's `extension`).
+--retardant builds the policy with retardant=True: its observation then holds the env's dousing layer (the share of doused
+cells per block and a flag per window cell), so the shoot head sees where it has doused, as the reference's agent does in
+its RGB frame; without it the agent reads the grid alone. Needs a HIP device."""
 import argparse
 import os
 import sys
@@ -41,6 +43,7 @@ def main():
     ap.add_argument("--gamma", type=float, default=0.99)
     ap.add_argument("--gae-lambda", type=float, default=0.95)
     ap.add_argument("--graph", action="store_true", help="capture the rollout and one update as graphs and replay them")
+    ap.add_argument("--retardant", action="store_true", help="the policy sees the env's retardant (dousing) layer")
     args = ap.parse_args()
     import torch
 
@@ -60,7 +63,7 @@ def main():
     env = AdvancedForestFireBulldozerEnv(args.rows, args.cols, key=1, num_envs=E, device=device, observation="grid",
                                          hidden_rng="philox")
     env.reset()
-    policy = BulldozerPolicy(env, radius=5, block=8, hidden=64, seed=0)
+    policy = BulldozerPolicy(env, radius=5, block=8, hidden=64, seed=0, retardant=args.retardant)
     steps = args.epochs * args.minibatches
     opt = ppo.Adam(policy.state_dict(), lr=args.lr, anneal=(steps, args.iterations))
     N = T // args.minibatches
