@@ -356,6 +356,42 @@ static inline int gca_check_policy_grad(const GcaGradAgent& a, const gca_policy*
     return GCA_OK;
 }
 
+// The agents of the gca_*_policy_grad_vclip calls: the plain entries' checks under their own names. The plain entries'
+// workspace query serves them, so the refusal of a short workspace names that one.
+constexpr GcaGradAgent GCA_GRAD_HELI_VCLIP{"helicopter_policy_grad_vclip", "helicopter_policy_grad_workspace",
+                                           "workspace smaller than gca_helicopter_policy_grad_workspace", false, 10};
+constexpr GcaGradAgent GCA_GRAD_BDZ_VCLIP{"bulldozer_policy_grad_vclip", "bulldozer_policy_grad_workspace",
+                                          "workspace smaller than gca_bulldozer_policy_grad_workspace", true, 12};
+
+// What a _vclip call asks beyond gca_check_policy_grad (which speaks first): the recorded values, and a vstats (f32 [3],
+// nullable) that overlaps neither the other outputs nor the weights.
+static inline int gca_check_policy_grad_vclip(const GcaGradAgent& a, const gca_policy* p, int C, const void* local,
+                                              const void* coarse, const void* action, const void* old_logits,
+                                              const void* old_value, const void* advantage, const void* returns,
+                                              int64_t T, const void* idx, int N, float clip_coef,
+                                              const void* g_w_local, const void* g_w_coarse, const void* g_b1,
+                                              const void* g_w_out, const void* g_b2, const void* stats,
+                                              const void* vstats, const void* workspace, int64_t workspace_bytes,
+                                              PpoPlan* pl) {
+    if (const int st = gca_check_policy_grad(a, p, C, local, coarse, action, old_logits, advantage, returns, T, idx, N,
+                                             clip_coef, g_w_local, g_w_coarse, g_b1, g_w_out, g_b2, stats, workspace,
+                                             workspace_bytes, pl))
+        return st;
+    if (!old_value) return gca_refuse(a.who, "null record");
+    if (vstats) {
+        const int Hd = p->hidden;
+        const int64_t wo = (int64_t)Hd * a.nout * 4, b2 = a.nout * 4ll;
+        const void* ptrs[11] = {g_w_local, g_w_coarse, g_b1, g_w_out, g_b2, stats,
+                                p->w_local, p->w_coarse, p->b1, p->w_out, p->b2};
+        const int64_t sizes[11] = {pl->off_wc * 4, (int64_t)C * Hd * 4, Hd * 4ll, wo, b2, 32,
+                                   pl->off_wc * 4, (int64_t)C * Hd * 4, Hd * 4ll, wo, b2};
+        for (int j = 0; j < 11; ++j)
+            if (gca_overlap(vstats, 12, ptrs[j], sizes[j]))
+                return gca_refuse(a.who, "the outputs may alias neither each other nor the weights");
+    }
+    return GCA_OK;
+}
+
 // the host build alone can read idx (host memory there) before it indexes with it
 static inline int gca_check_policy_grad_idx(const GcaGradAgent& a, const int32_t* idx, int N, int64_t T) {
     if (idx)

@@ -26,7 +26,7 @@
 //                     observation (gca_adv_policy.hip), pinned by tests/_retardant_obs_ref.py
 //   gca_gae / gca_helicopter_policy_grad(_workspace) / gca_bulldozer_policy_grad(_workspace)  the PPO update
 //                     (gca_ppo.hip): the GAE recurrence bit for bit, the loss gradient of either head layout in double
-//                     as a second yardstick
+//                     as a second yardstick; gca_*_policy_grad_vclip the same with the reference's clipped value loss
 //   gca_adam_step(_workspace) / gca_permutation  the optimizer and the minibatch shuffle (gca_opt.hip), bit for bit
 //   gca_philox        Random123 Philox4x32-10 (KAT hook)
 //
@@ -798,17 +798,23 @@ static double lse_host(const double* l, int n) {
 
 // Both agents' gradient in plain loops over the head layout (nh heads of heads[h] logits, then the value): the network,
 // the per-head loss of gca.h and every gradient sum in double, rounded to f32 once. The workspace is checked as on the
-// device and not used.
+// device and not used. vclip (the _vclip entries, with old_value and vstats): gca.h's clipped value loss in place of
+// 0.5 (v - R)^2, with U and every comparison in double; a first pass over the minibatch forms the values and U.
 static int policy_grad_host(const GcaGradAgent& ag, int nh, const int* heads, const gca_policy* p, int C,
                             const uint8_t* local, const float* coarse, const int32_t* action, const float* old_logits,
                             const float* advantage, const float* returns, int64_t T, const int32_t* idx, int N,
                             float clip_coef, float ent_coef, float vf_coef, int norm_adv, float* g_w_local,
                             float* g_w_coarse, float* g_b1, float* g_w_out, float* g_b2, float* stats, void* workspace,
-                            int64_t workspace_bytes) {
+                            int64_t workspace_bytes, bool vclip = false, const float* old_value = nullptr,
+                            float* vstats = nullptr) {
     PpoPlan pl;
-    if (const int st = gca_check_policy_grad(ag, p, C, local, coarse, action, old_logits, advantage, returns, T, idx, N,
-                                             clip_coef, g_w_local, g_w_coarse, g_b1, g_w_out, g_b2, stats, workspace,
-                                             workspace_bytes, &pl))
+    if (const int st = vclip ? gca_check_policy_grad_vclip(ag, p, C, local, coarse, action, old_logits, old_value,
+                                                           advantage, returns, T, idx, N, clip_coef, g_w_local,
+                                                           g_w_coarse, g_b1, g_w_out, g_b2, stats, vstats, workspace,
+                                                           workspace_bytes, &pl)
+                             : gca_check_policy_grad(ag, p, C, local, coarse, action, old_logits, advantage, returns, T,
+                                                     idx, N, clip_coef, g_w_local, g_w_coarse, g_b1, g_w_out, g_b2,
+                                                     stats, workspace, workspace_bytes, &pl))
         return st;
     if (const int st = gca_check_policy_grad_idx(ag, idx, N, T)) return st;
     const int S = 2 * p->radius + 1, SS = S * S, Hd = p->hidden, NO = ag.nout, NL = NO - 1;
@@ -824,8 +830,8 @@ static int policy_grad_host(const GcaGradAgent& ag, int nh, const int* heads, co
     std::vector<double> gwl((size_t)SS * 4 * Hd, 0.0), gwc((size_t)C * Hd, 0.0), gb1(Hd, 0.0), gwo((size_t)Hd * NO, 0.0);
     std::vector<double> a(Hd), h(Hd), da(Hd), out(NO), d(NO), gb2(NO, 0.0), lo(NL), pr(NL), lp(NL);
     double st[5] = {0};
-    for (int t = 0; t < N; ++t) {
-        const size_t row = row_of(t);
+    // the network on one record row: pre-activations a, hidden h, outputs out
+    auto forward = [&](size_t row) {
         const uint8_t* loc = local + row * SS;
         const float* co = coarse + row * C;
         for (int j = 0; j < Hd; ++j) a[j] = p->b1[j];
@@ -843,6 +849,50 @@ static int policy_grad_host(const GcaGradAgent& ag, int nh, const int* heads, co
             h[j] = a[j] > 0.0 ? a[j] : 0.0;
             for (int o = 0; o < NO; ++o) out[o] += (double)p->w_out[j * NO + o] * h[j];
         }
+    };
+    // the clipped value loss's minibatch scalars (gca.h): U, then n_U and the samples outside the clip against that U
+    const double cc = (double)clip_coef;
+    double U = 0.0, share_u = 0.0;
+    struct VTerms {
+        double dcr, q;
+        bool in, u;
+    };
+    auto vterms = [&](double v, size_t row) {
+        const double vo = old_value[row], diff = v - vo;
+        VTerms t;
+        t.in = fabs(diff) <= cc;
+        t.dcr = (vo + (diff < -cc ? -cc : (diff > cc ? cc : diff))) - (double)returns[row];
+        t.q = t.dcr * t.dcr;
+        t.u = U >= t.q;
+        return t;
+    };
+    if (vclip) {
+        std::vector<double> vs(N);
+        for (int t = 0; t < N; ++t) {
+            forward(row_of(t));
+            vs[t] = out[NL];
+            const double dv = vs[t] - returns[row_of(t)];
+            U += 0.5 * dv * dv;
+        }
+        U *= inv_n;
+        int64_t nu = 0, nc = 0;
+        for (int t = 0; t < N; ++t) {
+            const VTerms vt = vterms(vs[t], row_of(t));
+            nu += vt.u ? 1 : 0;
+            nc += vt.in ? 0 : 1;
+        }
+        share_u = (double)nu / N;
+        if (vstats) {
+            vstats[0] = (float)U;
+            vstats[1] = (float)share_u;
+            vstats[2] = (float)((double)nc / N);
+        }
+    }
+    for (int t = 0; t < N; ++t) {
+        const size_t row = row_of(t);
+        const uint8_t* loc = local + row * SS;
+        const float* co = coarse + row * C;
+        forward(row);
         double adv = advantage[row];
         if (norm_adv) adv = (adv - mean) / (sd + 1e-8);
         const double lo_c = 1.0 - (double)clip_coef, hi_c = 1.0 + (double)clip_coef;
@@ -872,8 +922,14 @@ static int policy_grad_host(const GcaGradAgent& ag, int nh, const int* heads, co
             st[4] += clipped ? 1.0 : 0.0;
         }
         const double dv = out[NL] - returns[row];
-        d[NL] = (double)vf_coef * dv * inv_n;
-        st[1] += 0.5 * dv * dv;
+        if (vclip) {
+            const VTerms vt = vterms(out[NL], row);
+            d[NL] = (double)vf_coef * (0.5 * inv_n) * (share_u * dv + ((!vt.u && vt.in) ? 2.0 * vt.dcr : 0.0));
+            st[1] += 0.5 * (vt.u ? U : vt.q);
+        } else {
+            d[NL] = (double)vf_coef * dv * inv_n;
+            st[1] += 0.5 * dv * dv;
+        }
         for (int o = 0; o < NO; ++o) gb2[o] += d[o];
         for (int j = 0; j < Hd; ++j) {
             double dh = 0.0;
@@ -933,6 +989,32 @@ extern "C" int gca_bulldozer_policy_grad(const gca_bulldozer_policy* p, int C, c
     return policy_grad_host(GCA_GRAD_BDZ, 2, heads, p, C, local, coarse, action, old_logits, advantage, returns, T, idx,
                             N, clip_coef, ent_coef, vf_coef, norm_adv, g_w_local, g_w_coarse, g_b1, g_w_out, g_b2, stats,
                             workspace, workspace_bytes);
+}
+
+extern "C" int gca_helicopter_policy_grad_vclip(const gca_heli_policy* p, int C, const uint8_t* local,
+                                                const float* coarse, const int32_t* action, const float* old_logits,
+                                                const float* old_value, const float* advantage, const float* returns,
+                                                int64_t T, const int32_t* idx, int N, float clip_coef, float ent_coef,
+                                                float vf_coef, int norm_adv, float* g_w_local, float* g_w_coarse,
+                                                float* g_b1, float* g_w_out, float* g_b2, float* stats, float* vstats,
+                                                void* workspace, int64_t workspace_bytes, void*) {
+    const int heads[1] = {9};
+    return policy_grad_host(GCA_GRAD_HELI_VCLIP, 1, heads, p, C, local, coarse, action, old_logits, advantage, returns,
+                            T, idx, N, clip_coef, ent_coef, vf_coef, norm_adv, g_w_local, g_w_coarse, g_b1, g_w_out,
+                            g_b2, stats, workspace, workspace_bytes, true, old_value, vstats);
+}
+
+extern "C" int gca_bulldozer_policy_grad_vclip(const gca_bulldozer_policy* p, int C, const uint8_t* local,
+                                               const float* coarse, const int32_t* action, const float* old_logits,
+                                               const float* old_value, const float* advantage, const float* returns,
+                                               int64_t T, const int32_t* idx, int N, float clip_coef, float ent_coef,
+                                               float vf_coef, int norm_adv, float* g_w_local, float* g_w_coarse,
+                                               float* g_b1, float* g_w_out, float* g_b2, float* stats, float* vstats,
+                                               void* workspace, int64_t workspace_bytes, void*) {
+    const int heads[2] = {9, 2};
+    return policy_grad_host(GCA_GRAD_BDZ_VCLIP, 2, heads, p, C, local, coarse, action, old_logits, advantage, returns,
+                            T, idx, N, clip_coef, ent_coef, vf_coef, norm_adv, g_w_local, g_w_coarse, g_b1, g_w_out,
+                            g_b2, stats, workspace, workspace_bytes, true, old_value, vstats);
 }
 
 // ---------------------------------------------------------------- the optimizer (gca.h "optimizer")

@@ -21,6 +21,18 @@
 //           running sum per tile (the sums stay short: TS, then tiles per split, then P terms). Partials -> workspace.
 //   reduce  a thread per gradient element adds the P partials in increasing p; the last workgroup adds the tile
 //           partials (a sequential partial per thread over tiles t, t + 256, .., then a tree) into g_b2 and the stats.
+// gca_*_policy_grad_vclip (the reference's clipped value loss, gca.h) is eight launches: every sample's d loss / d v
+// depends on two minibatch-wide scalars (U and n_U): U exists only after every tile's forward, n_U only after every
+// sample has been compared with U. So fwd (instantiated with VCLIP) leaves the value column out, and four launches
+// follow it, the per-sample work in a workgroup per tile, the two scalars in one small workgroup each:
+//   vsum    one workgroup: U from fwd's tile sums -> workspace header word 2.
+//   vcount  one wave per tile: the samples with U >= q_s and those outside the clip, as integers -> tile partials.
+//   vsum    one workgroup: the two integer sums -> header words 3, 4 and vstats.
+//   vfix    one workgroup per tile: d loss / d v_s into dout's value column (which carried v_s), its term added to da
+//           last, as the plain fwd adds it, and the tile partial's v_loss and b2[value] sums in fwd's tree.
+// (One workgroup walking all N samples for U and the counts, the first shape of this, cost 560 us at N = 131072: two
+// dependent gathers per sample and nothing to hide them behind.)
+// The plain entries launch the VCLIP = false instantiation, which is the kernel they always had.
 // fmaf is written out where a fused multiply-add is wanted (the build runs with -ffp-contract=off).
 #include "gca_common.h"
 #include "gca_ppo_plan.h"
@@ -210,7 +222,11 @@ __device__ __forceinline__ PpoHeadTerms ppo_head(const PpoBatch& b, int row, con
     return PpoHeadTerms{fmax(pg1, pg2), ent, (ratio - 1.0) - logratio, clipped ? 1.0f : 0.0f};
 }
 
-template <int HD, class HL>
+// VCLIP (the _vclip entries): the value column waits for U and vfix. DO[s][NOUT - 1] carries the value v_s itself, da
+// is formed from the logit columns only, the tile partial's v_loss slot holds the tile's term of U (the plain kernel's
+// sum) and its b2[value] slot zero; vcount and vfix replace both. Everything else is the plain instantiation's, in its
+// order.
+template <int HD, class HL, bool VCLIP>
 __global__ __launch_bounds__(PPO_THREADS) void ppo_fwd_kernel(
     PpoBatch b, const float* __restrict__ w_local, const float* __restrict__ w_coarse, const float* __restrict__ b1,
     const float* __restrict__ w_out, const float* __restrict__ b2, PpoLossArgs la, const float* __restrict__ hdr,
@@ -370,9 +386,9 @@ __global__ __launch_bounds__(PPO_THREADS) void ppo_fwd_kernel(
                 t.clipped = t.clipped + u.clipped;
             }
             const double dv = (double)outs[s * OST + NL] - (double)b.returns[row];
-            d[NL] = (float)(((double)la.vf_coef * dv) * inv_n);
+            if constexpr (!VCLIP) d[NL] = (float)(((double)la.vf_coef * dv) * inv_n);  // VCLIP: stays 0 for vfix
             st[0] = (float)t.pg;
-            st[1] = (float)(0.5 * dv * dv);
+            st[1] = (float)(0.5 * dv * dv);  // VCLIP: the tile's term of U, until vfix writes the tile's v_loss
             st[2] = (float)t.ent;
             st[3] = (float)t.kl;
             st[4] = t.clipped;
@@ -382,6 +398,7 @@ __global__ __launch_bounds__(PPO_THREADS) void ppo_fwd_kernel(
             douts[s * OST + o] = d[o];
             DO[(size_t)(t0 + s) * NOUT + o] = d[o];
         }
+        if constexpr (VCLIP) DO[(size_t)(t0 + s) * NOUT + NL] = valid ? outs[s * OST + NL] : 0.0f;  // d[NL] is 0
 #pragma unroll
         for (int o = 0; o < 5; ++o) tsum[s * PPO_TP + o] = st[o];
 #pragma unroll
@@ -407,7 +424,7 @@ __global__ __launch_bounds__(PPO_THREADS) void ppo_fwd_kernel(
         const int s = sg + R * i;
         float da[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
-        for (int o = 0; o < NOUT; ++o) {
+        for (int o = 0; o < (VCLIP ? NL : NOUT); ++o) {  // VCLIP: vfix adds the value column's term, last as here
             const float dd = douts[s * OST + o];
 #pragma unroll
             for (int k = 0; k < 4; ++k) da[k] = fmaf(wr[k][o], dd, da[k]);
@@ -415,6 +432,163 @@ __global__ __launch_bounds__(PPO_THREADS) void ppo_fwd_kernel(
 #pragma unroll
         for (int k = 0; k < 4; ++k) da[k] = ((posmask >> (4 * i + k)) & 1u) ? da[k] : 0.0f;
         reinterpret_cast<float4*>(DA + (size_t)(t0 + s) * HD)[jq] = make_float4(da[0], da[1], da[2], da[3]);
+    }
+}
+
+// ------------------------------------------------------------------ vsum, vcount, vfix: the clipped value loss (gca.h)
+// One sample's terms of the clipped value loss, in double from the f32 value v, return R and recorded value vo; U is
+// the minibatch's f32 scalar, compared as (double)U. vcount and vfix call this one function on the same words, so they
+// take the same side of both kinks.
+struct PpoVTerms {
+    double dvr, dcr, q;  // v - R, vc - R, (vc - R)^2
+    bool in, u;          // |v - vo| <= c; U >= q
+};
+
+__device__ __forceinline__ PpoVTerms ppo_vterms(float v, float R, float vo, float clip_coef, float U) {
+    PpoVTerms t;
+    const double c = (double)clip_coef, diff = (double)v - (double)vo;
+    t.in = fabs(diff) <= c;
+    const double vc = (double)vo + fmin(fmax(diff, -c), c);
+    t.dvr = (double)v - (double)R;
+    t.dcr = vc - (double)R;
+    t.q = t.dcr * t.dcr;
+    t.u = (double)U >= t.q;
+    return t;
+}
+
+__device__ __forceinline__ int ppo_block_count(int v, int* red, int tid) {
+    __syncthreads();  // the previous use of red
+    red[tid] = v;
+    __syncthreads();
+    for (int s = PPO_ADV_THREADS / 2; s >= 1; s >>= 1) {
+        if (tid < s) red[tid] = red[tid] + red[tid + s];
+        __syncthreads();
+    }
+    return red[0];
+}
+
+// header words of the _vclip calls: [2] U f32, [3] n_U i32, [4] the samples outside the clip i32
+constexpr int PPO_HDR_U = 2, PPO_HDR_NU = 3, PPO_HDR_NCLIP = 4;
+constexpr int PPO_VCOUNT_THREADS = 64;  // one wave: a tile has at most 64 samples
+
+// vsum, one workgroup, over the tile partials (a sequential partial per thread over tiles t, t + 1024, .., then a tree,
+// as adv sums). COUNTS = false: U = (the sum of slot sa, fwd's tile sums of f32(0.5 (v_s - R_s)^2)) * (1 / N) -> header.
+// COUNTS = true: the integer sums of slots sa (n_U) and sb (the samples outside the clip), vcount's -> header, vstats.
+template <bool COUNTS>
+__global__ __launch_bounds__(PPO_ADV_THREADS) void ppo_vsum_kernel(const float* __restrict__ TP, int tp, int64_t ntiles,
+                                                                   int sa, int sb, float inv_n, int N,
+                                                                   float* __restrict__ hdr,
+                                                                   float* __restrict__ vstats) {
+    __shared__ float red[PPO_ADV_THREADS];
+    const int tid = threadIdx.x;
+    if constexpr (!COUNTS) {
+        float s = 0.0f;
+        for (int64_t t = tid; t < ntiles; t += PPO_ADV_THREADS) s = s + TP[(size_t)t * tp + sa];
+        const float sum = ppo_block_sum(s, red, tid);
+        if (tid == 0) hdr[PPO_HDR_U] = sum * inv_n;
+    } else {
+        const int* __restrict__ TPi = reinterpret_cast<const int*>(TP);
+        int nu = 0, nc = 0;
+        for (int64_t t = tid; t < ntiles; t += PPO_ADV_THREADS) {
+            nu += TPi[(size_t)t * tp + sa];
+            nc += TPi[(size_t)t * tp + sb];
+        }
+        nu = ppo_block_count(nu, reinterpret_cast<int*>(red), tid);
+        nc = ppo_block_count(nc, reinterpret_cast<int*>(red), tid);
+        if (tid == 0) {
+            reinterpret_cast<int*>(hdr)[PPO_HDR_NU] = nu;
+            reinterpret_cast<int*>(hdr)[PPO_HDR_NCLIP] = nc;
+            if (vstats) {
+                vstats[0] = hdr[PPO_HDR_U];
+                vstats[1] = (float)((double)nu / (double)N);
+                vstats[2] = (float)((double)nc / (double)N);
+            }
+        }
+    }
+}
+
+// vcount, one wave per tile of fwd's: the tile's samples with U >= q_s and those outside the clip, counted as integers
+// (a ballot) into the tile partial's v_loss and b2[value] slots, which vfix overwrites after vsum has read them.
+template <int TS, int NOUT, int TPF>
+__global__ __launch_bounds__(PPO_VCOUNT_THREADS) void ppo_vcount_kernel(PpoBatch b, const float* __restrict__ old_value,
+                                                                        float clip_coef, const float* __restrict__ hdr,
+                                                                        const float* __restrict__ DO,
+                                                                        float* __restrict__ TP) {
+    static_assert(TS <= PPO_VCOUNT_THREADS, "a thread per sample of the tile");
+    const int s = threadIdx.x;
+    const int64_t t = (int64_t)blockIdx.x * TS + s;
+    bool u = false, out = false;
+    if (s < TS && t < b.N) {
+        const int row = ppo_row(b, (int)t);
+        const PpoVTerms vt = ppo_vterms(DO[(size_t)t * NOUT + NOUT - 1], b.returns[row], old_value[row], clip_coef,
+                                        hdr[PPO_HDR_U]);
+        u = vt.u;
+        out = !vt.in;
+    }
+    const int nu = __popcll(__ballot(u)), nc = __popcll(__ballot(out));
+    if (s == 0) {
+        int* tp = reinterpret_cast<int*>(TP + (size_t)blockIdx.x * TPF);
+        tp[1] = nu;
+        tp[5 + NOUT - 1] = nc;
+    }
+}
+
+// vfix, one workgroup per tile of fwd's: d loss / d v_s replaces v_s in DO, its term is added to da (last, as the plain
+// fwd adds it), and the tile partial's v_loss and b2[value] sums are formed in fwd's pairwise tree over the samples.
+template <int HD, class HL>
+__global__ __launch_bounds__(PPO_THREADS) void ppo_vfix_kernel(PpoBatch b, const float* __restrict__ old_value,
+                                                               const float* __restrict__ w_out, PpoLossArgs la,
+                                                               const float* __restrict__ hdr, float* __restrict__ DA,
+                                                               const float* __restrict__ H, float* __restrict__ DO,
+                                                               float* __restrict__ TP) {
+    using Cf = PpoCfg<HD>;
+    constexpr int TS = Cf::TS, Q = Cf::Q, R = Cf::R, SPT = Cf::SPT;
+    constexpr int NOUT = HL::NOUT, NL = HL::NL, PPO_TP = HL::TP;
+    __shared__ float dvs[TS], tsum[TS * 2];
+    const int tid = threadIdx.x, jq = tid % Q, sg = tid / Q;
+    const int64_t t0 = (int64_t)blockIdx.x * TS;
+    if (tid < TS) {
+        const int s = tid;
+        float d = 0.0f, vl = 0.0f;
+        if (t0 + s < b.N) {
+            const int row = ppo_row(b, (int)(t0 + s));
+            const float U = hdr[PPO_HDR_U];
+            const double n = (double)b.N, share = (double)reinterpret_cast<const int*>(hdr)[PPO_HDR_NU] / n;
+            const PpoVTerms vt = ppo_vterms(DO[(size_t)(t0 + s) * NOUT + NL], b.returns[row], old_value[row],
+                                            la.clip_coef, U);
+            const double own = (!vt.u && vt.in) ? 2.0 * vt.dcr : 0.0;
+            d = (float)(((double)la.vf_coef * (0.5 / n)) * (share * vt.dvr + own));
+            vl = (float)(0.5 * (vt.u ? (double)U : vt.q));
+        }
+        dvs[s] = d;
+        DO[(size_t)(t0 + s) * NOUT + NL] = d;
+        tsum[2 * s] = vl;
+        tsum[2 * s + 1] = d;
+    }
+    __syncthreads();
+    for (int half = TS / 2; half >= 1; half >>= 1) {
+        if (tid < half * 2) tsum[tid] = tsum[tid] + tsum[tid + half * 2];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        TP[(size_t)blockIdx.x * PPO_TP + 1] = tsum[0];
+        TP[(size_t)blockIdx.x * PPO_TP + 5 + NL] = tsum[1];
+    }
+    float wv[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) wv[k] = w_out[(4 * jq + k) * NOUT + NL];
+#pragma unroll
+    for (int i = 0; i < SPT; ++i) {
+        const int s = sg + R * i;
+        const float dd = dvs[s];
+        const float4 h = reinterpret_cast<const float4*>(H + (size_t)(t0 + s) * HD)[jq];
+        float4* const dst = reinterpret_cast<float4*>(DA + (size_t)(t0 + s) * HD) + jq;
+        float4 da = *dst;
+        da.x = h.x > 0.0f ? fmaf(wv[0], dd, da.x) : da.x;
+        da.y = h.y > 0.0f ? fmaf(wv[1], dd, da.y) : da.y;
+        da.z = h.z > 0.0f ? fmaf(wv[2], dd, da.z) : da.z;
+        da.w = h.w > 0.0f ? fmaf(wv[3], dd, da.w) : da.w;
+        *dst = da;
     }
 }
 
@@ -588,9 +762,9 @@ extern "C" int64_t gca_bulldozer_policy_grad_workspace(const gca_bulldozer_polic
     return ppo_workspace(GCA_GRAD_BDZ, p, C, N);
 }
 
-template <int HD, class HL>
+template <int HD, class HL, bool VCLIP>
 static void ppo_launch(const PpoBatch& b, const PpoPlan& pl, const gca_policy* p, const PpoLossArgs& la,
-                       const PpoOut& out, char* ws, hipStream_t st) {
+                       const PpoOut& out, const float* old_value, float* vstats, char* ws, hipStream_t st) {
     float* hdr = reinterpret_cast<float*>(ws);
     float* DA = reinterpret_cast<float*>(ws + pl.off_da);
     float* H = reinterpret_cast<float*>(ws + pl.off_h);
@@ -598,8 +772,19 @@ static void ppo_launch(const PpoBatch& b, const PpoPlan& pl, const gca_policy* p
     float* TP = reinterpret_cast<float*>(ws + pl.off_tp);
     float* part = reinterpret_cast<float*>(ws + pl.off_part);
     hipLaunchKernelGGL(ppo_adv_kernel, dim3(1), dim3(PPO_ADV_THREADS), 0, st, b, hdr);
-    hipLaunchKernelGGL((ppo_fwd_kernel<HD, HL>), dim3((unsigned)pl.ntiles), dim3(PPO_THREADS), 0, st, b, p->w_local,
-                       p->w_coarse, p->b1, p->w_out, p->b2, la, hdr, DA, H, DO, TP);
+    hipLaunchKernelGGL((ppo_fwd_kernel<HD, HL, VCLIP>), dim3((unsigned)pl.ntiles), dim3(PPO_THREADS), 0, st, b,
+                       p->w_local, p->w_coarse, p->b1, p->w_out, p->b2, la, hdr, DA, H, DO, TP);
+    if constexpr (VCLIP) {
+        using Cf = PpoCfg<HD>;
+        hipLaunchKernelGGL(ppo_vsum_kernel<false>, dim3(1), dim3(PPO_ADV_THREADS), 0, st, TP, (int)HL::TP, pl.ntiles, 1,
+                           5 + HL::NL, la.inv_n, b.N, hdr, vstats);
+        hipLaunchKernelGGL((ppo_vcount_kernel<Cf::TS, HL::NOUT, HL::TP>), dim3((unsigned)pl.ntiles),
+                           dim3(PPO_VCOUNT_THREADS), 0, st, b, old_value, la.clip_coef, hdr, DO, TP);
+        hipLaunchKernelGGL(ppo_vsum_kernel<true>, dim3(1), dim3(PPO_ADV_THREADS), 0, st, TP, (int)HL::TP, pl.ntiles, 1,
+                           5 + HL::NL, la.inv_n, b.N, hdr, vstats);
+        hipLaunchKernelGGL((ppo_vfix_kernel<HD, HL>), dim3((unsigned)pl.ntiles), dim3(PPO_THREADS), 0, st, b, old_value,
+                           p->w_out, la, hdr, DA, H, DO, TP);
+    }
     hipLaunchKernelGGL((ppo_wgrad_kernel<HD, HL::NOUT>), dim3((unsigned)pl.nb, (unsigned)pl.P), dim3(PPO_THREADS), 0,
                        st, b, pl, DA, H, DO, part);
     const int elem_blocks = (int)((pl.GF + PPO_THREADS - 1) / PPO_THREADS);
@@ -607,20 +792,28 @@ static void ppo_launch(const PpoBatch& b, const PpoPlan& pl, const gca_policy* p
                        pl, la, part, TP, hdr, out, elem_blocks);
 }
 
-// the body of both entry points: the shared checks, then the four launches of the agent's head layout
-template <class HL>
+// the body of the four entry points: the shared checks, then the launches of the agent's head layout (four; eight with
+// VCLIP, where old_value and vstats are the _vclip entries' two further arguments)
+template <class HL, bool VCLIP>
 static int ppo_policy_grad(const GcaGradAgent& ag, const gca_policy* p, int C, const uint8_t* local,
-                           const float* coarse, const int32_t* action, const float* old_logits,
+                           const float* coarse, const int32_t* action, const float* old_logits, const float* old_value,
                            const float* advantage, const float* returns, int64_t T, const int32_t* idx, int N,
                            float clip_coef, float ent_coef, float vf_coef, int norm_adv, float* g_w_local,
-                           float* g_w_coarse, float* g_b1, float* g_w_out, float* g_b2, float* stats, void* workspace,
-                           int64_t workspace_bytes, void* stream) {
+                           float* g_w_coarse, float* g_b1, float* g_w_out, float* g_b2, float* stats, float* vstats,
+                           void* workspace, int64_t workspace_bytes, void* stream) {
     static_assert(HL::NOUT == 10 || HL::NOUT == 12, "the agents' outputs (GcaGradAgent::nout)");
     PpoPlan pl;
-    if (const int st = gca_check_policy_grad(ag, p, C, local, coarse, action, old_logits, advantage, returns, T, idx, N,
-                                             clip_coef, g_w_local, g_w_coarse, g_b1, g_w_out, g_b2, stats, workspace,
-                                             workspace_bytes, &pl))
-        return st;
+    if constexpr (VCLIP) {
+        if (const int st = gca_check_policy_grad_vclip(ag, p, C, local, coarse, action, old_logits, old_value, advantage,
+                                                       returns, T, idx, N, clip_coef, g_w_local, g_w_coarse, g_b1,
+                                                       g_w_out, g_b2, stats, vstats, workspace, workspace_bytes, &pl))
+            return st;
+    } else {
+        if (const int st = gca_check_policy_grad(ag, p, C, local, coarse, action, old_logits, advantage, returns, T, idx,
+                                                 N, clip_coef, g_w_local, g_w_coarse, g_b1, g_w_out, g_b2, stats,
+                                                 workspace, workspace_bytes, &pl))
+            return st;
+    }
     const int S = 2 * p->radius + 1, SS = S * S, Hd = p->hidden;
     PpoBatch b{local, coarse, action, old_logits, advantage, returns, idx, N, (int)T, SS, C};
     const PpoLossArgs la{clip_coef, ent_coef, vf_coef, 1.0f / (float)N, norm_adv ? 1 : 0};
@@ -628,10 +821,10 @@ static int ppo_policy_grad(const GcaGradAgent& ag, const gca_policy* p, int C, c
     hipStream_t st = (hipStream_t)stream;
     char* ws = reinterpret_cast<char*>(workspace);
     switch (Hd) {
-        case 32: ppo_launch<32, HL>(b, pl, p, la, out, ws, st); break;
-        case 64: ppo_launch<64, HL>(b, pl, p, la, out, ws, st); break;
-        case 128: ppo_launch<128, HL>(b, pl, p, la, out, ws, st); break;
-        default: ppo_launch<256, HL>(b, pl, p, la, out, ws, st); break;
+        case 32: ppo_launch<32, HL, VCLIP>(b, pl, p, la, out, old_value, vstats, ws, st); break;
+        case 64: ppo_launch<64, HL, VCLIP>(b, pl, p, la, out, old_value, vstats, ws, st); break;
+        case 128: ppo_launch<128, HL, VCLIP>(b, pl, p, la, out, old_value, vstats, ws, st); break;
+        default: ppo_launch<256, HL, VCLIP>(b, pl, p, la, out, old_value, vstats, ws, st); break;
     }
     GCA_CHECK_LAUNCH(ag.who);
     return GCA_OK;
@@ -643,9 +836,10 @@ extern "C" int gca_helicopter_policy_grad(const gca_heli_policy* p, int C, const
                                           float ent_coef, float vf_coef, int norm_adv, float* g_w_local,
                                           float* g_w_coarse, float* g_b1, float* g_w_out, float* g_b2, float* stats,
                                           void* workspace, int64_t workspace_bytes, void* stream) {
-    return ppo_policy_grad<PpoHeli>(GCA_GRAD_HELI, p, C, local, coarse, action, old_logits, advantage, returns, T, idx,
-                                    N, clip_coef, ent_coef, vf_coef, norm_adv, g_w_local, g_w_coarse, g_b1, g_w_out,
-                                    g_b2, stats, workspace, workspace_bytes, stream);
+    return ppo_policy_grad<PpoHeli, false>(GCA_GRAD_HELI, p, C, local, coarse, action, old_logits, nullptr, advantage,
+                                           returns, T, idx, N, clip_coef, ent_coef, vf_coef, norm_adv, g_w_local,
+                                           g_w_coarse, g_b1, g_w_out, g_b2, stats, nullptr, workspace, workspace_bytes,
+                                           stream);
 }
 
 extern "C" int gca_bulldozer_policy_grad(const gca_bulldozer_policy* p, int C, const uint8_t* local,
@@ -654,7 +848,34 @@ extern "C" int gca_bulldozer_policy_grad(const gca_bulldozer_policy* p, int C, c
                                          int N, float clip_coef, float ent_coef, float vf_coef, int norm_adv,
                                          float* g_w_local, float* g_w_coarse, float* g_b1, float* g_w_out, float* g_b2,
                                          float* stats, void* workspace, int64_t workspace_bytes, void* stream) {
-    return ppo_policy_grad<PpoBdz>(GCA_GRAD_BDZ, p, C, local, coarse, action, old_logits, advantage, returns, T, idx, N,
-                                   clip_coef, ent_coef, vf_coef, norm_adv, g_w_local, g_w_coarse, g_b1, g_w_out, g_b2,
-                                   stats, workspace, workspace_bytes, stream);
+    return ppo_policy_grad<PpoBdz, false>(GCA_GRAD_BDZ, p, C, local, coarse, action, old_logits, nullptr, advantage,
+                                          returns, T, idx, N, clip_coef, ent_coef, vf_coef, norm_adv, g_w_local,
+                                          g_w_coarse, g_b1, g_w_out, g_b2, stats, nullptr, workspace, workspace_bytes,
+                                          stream);
+}
+
+extern "C" int gca_helicopter_policy_grad_vclip(const gca_heli_policy* p, int C, const uint8_t* local,
+                                                const float* coarse, const int32_t* action, const float* old_logits,
+                                                const float* old_value, const float* advantage, const float* returns,
+                                                int64_t T, const int32_t* idx, int N, float clip_coef, float ent_coef,
+                                                float vf_coef, int norm_adv, float* g_w_local, float* g_w_coarse,
+                                                float* g_b1, float* g_w_out, float* g_b2, float* stats, float* vstats,
+                                                void* workspace, int64_t workspace_bytes, void* stream) {
+    return ppo_policy_grad<PpoHeli, true>(GCA_GRAD_HELI_VCLIP, p, C, local, coarse, action, old_logits, old_value,
+                                          advantage, returns, T, idx, N, clip_coef, ent_coef, vf_coef, norm_adv,
+                                          g_w_local, g_w_coarse, g_b1, g_w_out, g_b2, stats, vstats, workspace,
+                                          workspace_bytes, stream);
+}
+
+extern "C" int gca_bulldozer_policy_grad_vclip(const gca_bulldozer_policy* p, int C, const uint8_t* local,
+                                               const float* coarse, const int32_t* action, const float* old_logits,
+                                               const float* old_value, const float* advantage, const float* returns,
+                                               int64_t T, const int32_t* idx, int N, float clip_coef, float ent_coef,
+                                               float vf_coef, int norm_adv, float* g_w_local, float* g_w_coarse,
+                                               float* g_b1, float* g_w_out, float* g_b2, float* stats, float* vstats,
+                                               void* workspace, int64_t workspace_bytes, void* stream) {
+    return ppo_policy_grad<PpoBdz, true>(GCA_GRAD_BDZ_VCLIP, p, C, local, coarse, action, old_logits, old_value,
+                                         advantage, returns, T, idx, N, clip_coef, ent_coef, vf_coef, norm_adv,
+                                         g_w_local, g_w_coarse, g_b1, g_w_out, g_b2, stats, vstats, workspace,
+                                         workspace_bytes, stream);
 }

@@ -17,7 +17,9 @@ struct PpoPlan {
     int64_t off_da, off_h, off_do, off_tp, off_part, bytes;  // byte offsets inside the workspace, and its size
 };
 
-constexpr int PPO_HDR_FLOATS = 64;   // [0] the minibatch's advantage mean, [1] its standard deviation
+// [0] the minibatch's advantage mean, [1] its standard deviation; the _vclip entries: [2] U f32, [3] n_U i32, [4] the
+// samples outside the value clip i32
+constexpr int PPO_HDR_FLOATS = 64;
 constexpr int64_t PPO_PART_BYTES_MAX = 256ll << 20;
 
 // floats per tile partial: 5 statistics sums, NOUT b2 gradient sums, rounded up to a multiple of four (16 at NOUT = 10

@@ -300,6 +300,11 @@ _SIGNATURES = {
     "gca_bulldozer_policy_grad_workspace": ([POINTER(BulldozerPolicyStruct), c_int, c_int], c_int64),
     "gca_bulldozer_policy_grad": ([POINTER(BulldozerPolicyStruct), c_int, P, P, P, P, P, P, c_int64, P, c_int, c_float,
                                    c_float, c_float, c_int, P, P, P, P, P, P, P, c_int64, P], c_int),
+    # the plain entries' arguments with old_value after old_logits and vstats after stats
+    "gca_helicopter_policy_grad_vclip": ([POINTER(HeliPolicy), c_int, P, P, P, P, P, P, P, c_int64, P, c_int, c_float,
+                                          c_float, c_float, c_int, P, P, P, P, P, P, P, P, c_int64, P], c_int),
+    "gca_bulldozer_policy_grad_vclip": ([POINTER(BulldozerPolicyStruct), c_int, P, P, P, P, P, P, P, c_int64, P, c_int,
+                                         c_float, c_float, c_float, c_int, P, P, P, P, P, P, P, P, c_int64, P], c_int),
     "gca_adam_step_workspace": ([c_int64], c_int64),
     "gca_adam_step": ([POINTER(AdamTensors), P, c_float, c_float, c_float, c_float, c_float, c_int64, c_int64, P, P,
                        c_int64, P], c_int),
@@ -320,6 +325,8 @@ CPU_SYMBOLS = ("gca_last_error", "gca_version", "gca_philox", "gca_count_cells",
 CPU_BULLDOZER_POLICY_SYMBOLS = ("gca_bulldozer_policy_act", "gca_bulldozer_policy_grad_workspace",
                                 "gca_bulldozer_policy_grad", "gca_advanced_policy_act",
                                 "gca_advanced_policy_observation", "gca_advanced_policy_act_retardant")
+# both agents' learner's step with the reference's clipped value loss on host arrays
+CPU_VCLIP_SYMBOLS = ("gca_helicopter_policy_grad_vclip", "gca_bulldozer_policy_grad_vclip")
 
 _lib = None
 _lib_cpu = None
@@ -354,7 +361,7 @@ def load_cpu():
     if not os.path.exists(CPU_LIB_PATH):
         raise GCAError(f"{CPU_LIB_PATH} not found: build it with `make -C gym-cellular-automata_amd/csrc`")
     lib = ctypes.CDLL(CPU_LIB_PATH, mode=ctypes.RTLD_LOCAL)
-    for name in CPU_SYMBOLS + CPU_BULLDOZER_POLICY_SYMBOLS:
+    for name in CPU_SYMBOLS + CPU_BULLDOZER_POLICY_SYMBOLS + CPU_VCLIP_SYMBOLS:
         fn = getattr(lib, name)
         fn.argtypes, fn.restype = _SIGNATURES[name]
     _lib_cpu = lib

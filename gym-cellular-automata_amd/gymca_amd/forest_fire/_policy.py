@@ -4,8 +4,8 @@ outputs. The window's classes select rows of `w_local` (a Dense layer over the o
 coarse map goes through `w_coarse`, a relu hidden layer of width `hidden`, then N_LOGITS logits and the value. Here live
 the dims' checks, the seeded draw, the validated assignment of the five tensors, `version`, the C struct, load, the
 trunk of forward_torch and the learner's step: ppo_grad, the PPO loss gradient over a minibatch of rollout_policy's
-records in four launches, and ppo_update, the whole update (forest_fire.ppo.permutation's shuffles, then ppo_grad and
-forest_fire.ppo.Adam.step per minibatch). A subclass names its heads (HEADS, N_LOGITS), its gradient entry point
+records in four launches (eight with clip_vloss=True, the reference's clipped value loss), and ppo_update, the whole
+update (forest_fire.ppo.permutation's shuffles, then ppo_grad and forest_fire.ppo.Adam.step per minibatch). A subclass names its heads (HEADS, N_LOGITS), its gradient entry point
 (GRAD_ENTRY) and splits the outputs."""
 import ctypes
 import math
@@ -170,11 +170,16 @@ class PolicyBase:
         return ws
 
     def ppo_grad(self, records, advantage, returns, idx=None, clip_coef=0.2, ent_coef=0.01, vf_coef=0.5, norm_adv=True,
-                 grads_out=None, stats_out=None, workspace=None):
-        """(grads, stats) of the PPO clipped-surrogate loss (agents/jax_ppo.py:987-1041, clip_vloss off; per head, as
+                 grads_out=None, stats_out=None, workspace=None, clip_vloss=False, vstats_out=None):
+        """(grads, stats) of the PPO clipped-surrogate loss (agents/jax_ppo.py:987-1041; per head, as
         include/gca.h states it: with one head the usual loss, with the bulldozer's two every mean runs over the
         (sample, head) pairs) over a minibatch of rollout_policy's records, in four launches of hand-written kernels
         (gca_helicopter_policy_grad / gca_bulldozer_policy_grad).
+        clip_vloss: False (the default) takes the value loss 0.5 (v - R)^2; True the reference's clipped value loss
+        (its own default, args.ppo.clip_vloss: the batch mean of the unclipped loss BEFORE the maximum, include/gca.h),
+        in eight launches (gca_*_policy_grad_vclip). It needs records['value'], the recorded values (contiguous float32,
+        T values), which is not looked at otherwise, and returns (grads, stats, vstats): vstats float32 (3,) in the
+        order of forest_fire.ppo.VSTATS, in vstats_out if given. stats' v_loss and loss are then the clipped ones.
         records: rollout_policy's dict -- `local`, `coarse`, `action`, `logits` are read -- in (K, E, ...) or
         flattened (T, ...) form, `action` with len(HEADS) and `logits` with N_LOGITS values per row;
         advantage / returns: forest_fire.ppo.gae's float32 outputs, T values each. idx: an
@@ -192,7 +197,11 @@ class PolicyBase:
         from ._batched import _is_kernel_tensor, check_tensor
 
         di = -1 if self.device.type == "cpu" else self.device.index
-        missing = [n for n in ("local", "coarse", "action", "logits") if n not in records]
+        clip_vloss = bool(clip_vloss)
+        if vstats_out is not None and not clip_vloss:
+            raise ValueError("ppo_grad: vstats_out needs clip_vloss=True")
+        wanted = ("local", "coarse", "action", "logits") + (("value",) if clip_vloss else ())
+        missing = [n for n in wanted if n not in records]
         if missing:
             raise ValueError(f"ppo_grad: records lack {missing}")
         action = records["action"]
@@ -205,6 +214,7 @@ class PolicyBase:
                                     (records["coarse"], torch.float32, self.C, "records['coarse']"),
                                     (action, torch.int32, NH, "records['action']"),
                                     (records["logits"], torch.float32, self.N_LOGITS, "records['logits']"),
+                                    *(((records["value"], torch.float32, 1, "records['value']"),) if clip_vloss else ()),
                                     (advantage, torch.float32, 1, "advantage"), (returns, torch.float32, 1, "returns")):
             if not (_is_kernel_tensor(t, dtype, di) and t.numel() == T * per):
                 raise ValueError(f"ppo_grad: {what} must be a contiguous {str(dtype).replace('torch.', '')} tensor of "
@@ -227,7 +237,22 @@ class PolicyBase:
         ws = self._ppo_workspace(N, workspace)
         args = [t.data_ptr() for t in rec] + [T, None if idx is None else idx.data_ptr(), N, float(clip_coef),
                                               float(ent_coef), float(vf_coef), 1 if norm_adv else 0]
-        args += [grads[n].data_ptr() for n in WEIGHTS] + [stats.data_ptr(), ws.data_ptr(), ws.numel()]
+        args += [grads[n].data_ptr() for n in WEIGHTS] + [stats.data_ptr()]
+        if clip_vloss:
+            vstats = (torch.empty(3, dtype=torch.float32, device=self.device) if vstats_out is None
+                      else check_tensor(vstats_out, torch.float32, (3,), di, "ppo_grad", "vstats_out"))
+            args += [vstats.data_ptr(), ws.data_ptr(), ws.numel()]
+            if di < 0:
+                _lib.call_cpu(self.GRAD_ENTRY + "_vclip", ctypes.byref(self._struct), self.C, *args, None)
+                return grads, stats, vstats
+            pc = self.__dict__.get("_ppo_vclip_call")
+            if pc is None or pc[0] != self.version:
+                pc = (self.version, BoundCall(self.GRAD_ENTRY + "_vclip", self._struct, self.C, *([SLOT] * 24),
+                                              keep=self.tensors()))
+                object.__setattr__(self, "_ppo_vclip_call", pc)
+            pc[1](*args, dev.raw_stream(di))
+            return grads, stats, vstats
+        args += [ws.data_ptr(), ws.numel()]
         if di < 0:
             _lib.call_cpu(self.GRAD_ENTRY, ctypes.byref(self._struct), self.C, *args, None)
             return grads, stats
@@ -242,7 +267,7 @@ class PolicyBase:
 
     def ppo_update(self, opt, records, advantage, returns, epochs=4, minibatches=4, seed=0, clip_coef=0.2,
                    ent_coef=0.01, vf_coef=0.5, norm_adv=True, stats_out=None, info_out=None, perm_out=None,
-                   grads_out=None, workspace=None):
+                   grads_out=None, workspace=None, clip_vloss=False, vstats_out=None):
         """A whole PPO update on the device (the reference's update_ppo, agents/jax_ppo.py:1045-1114): ONE
         forest_fire.ppo.permutation launch draws the `epochs` shuffles of the T recorded samples (keyed by seed, the
         epoch and opt.count, the optimizer's device-resident step count), then every epoch walks its row in
@@ -252,7 +277,8 @@ class PolicyBase:
         gradient norm, learning rate). stats_out / info_out / perm_out (int32 (epochs, T)) / grads_out / workspace: the
         caller's buffers, else allocated (the workspace: the policy's own). With all of them given the call allocates
         nothing and does not sync: it can be captured as one graph, and a replay draws new shuffles because opt.count has
-        moved."""
+        moved. clip_vloss=True: ppo_grad's clipped value loss on records['value']; returns (stats, info, vstats), vstats
+        (epochs * minibatches, 3) in the order of forest_fire.ppo.VSTATS, in vstats_out if given."""
         import torch
 
         from . import ppo
@@ -284,12 +310,20 @@ class PolicyBase:
                 else check_tensor(perm_out, torch.int32, (epochs, T), di, "ppo_update", "perm_out"))
         grads = ({n: new(s, torch.float32) for n, s in self.weight_shapes().items()} if grads_out is None
                  else grads_out)
+        clip_vloss = bool(clip_vloss)
+        if vstats_out is not None and not clip_vloss:
+            raise ValueError("ppo_update: vstats_out needs clip_vloss=True")
+        vstats = None
+        if clip_vloss:
+            vstats = (new((steps, 3), torch.float32) if vstats_out is None
+                      else check_tensor(vstats_out, torch.float32, (steps, 3), di, "ppo_update", "vstats_out"))
         ppo.permutation(T, epochs, seed, counter=opt.count, out=perm)
         for e in range(epochs):
             for mb in range(minibatches):
                 i = e * minibatches + mb
                 self.ppo_grad(records, advantage, returns, perm[e, mb * N:(mb + 1) * N], clip_coef=clip_coef,
                               ent_coef=ent_coef, vf_coef=vf_coef, norm_adv=norm_adv, grads_out=grads,
-                              stats_out=stats[i], workspace=workspace)
+                              stats_out=stats[i], workspace=workspace, clip_vloss=clip_vloss,
+                              vstats_out=vstats[i] if clip_vloss else None)
                 opt.step(grads, info_out=info[i])
-        return stats, info
+        return (stats, info, vstats) if clip_vloss else (stats, info)

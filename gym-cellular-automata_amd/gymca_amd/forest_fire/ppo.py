@@ -11,6 +11,9 @@ from .._lib import call, call_cpu
 from ._batched import check_tensor
 
 STATS = ("loss", "pg_loss", "v_loss", "entropy", "approx_kl", "clip_fraction", "adv_mean", "adv_std")
+# ppo_grad(clip_vloss=True)'s further statistics (include/gca.h): U, the share of samples whose maximum is U, and the
+# share whose value left the clip range around the recorded one
+VSTATS = ("v_loss_unclipped", "u_share", "v_clip_fraction")
 
 
 def gamma_lambda(gamma, gae_lambda):

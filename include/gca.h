@@ -862,8 +862,8 @@ int gca_gae(const double* reward, const float* value, const float* next_value, c
  * log p_i. loss = mean(pg) - ent_coef mean(ent) + vf_coef mean(vl).
  * stats[8] = {loss, mean pg, mean vl, mean ent, approx_kl = mean((ratio - 1) - logratio), clip fraction = the share of
  * samples with ratio outside [1 - c, 1 + c], adv mean, adv std}.
- * The reference's clipped value loss (clip_vloss, :1022-1029) takes the batch mean BEFORE its maximum, a quirk; it is out
- * of scope here.
+ * The reference's clipped value loss (clip_vloss, :1021-1030) takes the batch mean BEFORE its maximum, a quirk; it is
+ * gca_helicopter_policy_grad_vclip / gca_bulldozer_policy_grad_vclip below.
  * Outputs: g_* f32 in the weights' own layouts, every element written (a (cell, class) row no sample selects is exactly
  * 0.0f), never read, and they may alias neither each other nor the weights. All accumulation is f32 (the scalar loss
  * chain of ONE sample -- the two logsumexps, the ratio, the entropy -- runs in double and is rounded once), no floating-point
@@ -909,6 +909,50 @@ int gca_bulldozer_policy_grad(const gca_bulldozer_policy* p, int C, const uint8_
                               float ent_coef, float vf_coef, int norm_adv, float* g_w_local, float* g_w_coarse,
                               float* g_b1, float* g_w_out, float* g_b2, float* stats, void* workspace,
                               int64_t workspace_bytes, void* stream);
+
+/* gca_helicopter_policy_grad_vclip / gca_bulldozer_policy_grad_vclip: the two calls above with the reference's clipped
+ * value loss (args.ppo.clip_vloss, its default; agents/jax_ppo.py:1021-1030) in place of vl = 0.5 (v - R)^2. Two more
+ * arguments: old_value f32 [T], the RECORDED value (rollout_policy's `value`), indexed through idx like the other
+ * records, and vstats f32 [3], nullable. Per minibatch of N samples, with v_s the value output on row s, R_s the return,
+ * vo_s the recorded value and c = clip_coef (the ratio clip's coefficient, as in the reference):
+ *   U    = 0.5 mean_s (v_s - R_s)^2                  a scalar: the reference takes the batch mean BEFORE its maximum
+ *   vc_s = vo_s + clip(v_s - vo_s, -c, +c);  q_s = (vc_s - R_s)^2           (no 0.5)
+ *   v_loss = 0.5 mean_s max(U, q_s);  loss = mean pg - ent_coef mean ent + vf_coef v_loss
+ * Every other term and statistic is the plain call's. With in_s = 1[|v_s - vo_s| <= c], u_s = 1[U >= q_s] and
+ * n_U = sum_s u_s:
+ *   d loss / d v_s = vf_coef (0.5 / N) [ (n_U / N) (v_s - R_s) + (1 - u_s) in_s 2 (vc_s - R_s) ]
+ * so every sample's gradient depends on two minibatch-wide scalars. Ties: U >= q_s goes to the U branch and
+ * |v_s - vo_s| == c to the inside (jax splits a tie's gradient evenly; ties have measure zero). With N = 1 and the
+ * sample inside this is the plain 0.5 (v - R)^2 and its gradient.
+ * stats[8] keeps its order: v_loss (index 2) and loss (index 0) are the clipped ones.
+ * vstats = {U, n_U / N, the share of samples with |v_s - vo_s| > c}; the counts are integer sums, each share the
+ * double quotient rounded to f32.
+ * Precision. One sample's chain (v_s - R_s, vc_s, q_s, the bracket above) runs in double from the f32 v_s, R_s, vo_s and
+ * is rounded to f32 once per term. Device build: U = (sum_s f32(0.5 (v_s - R_s)^2)) * f32(1 / N), an f32 sum in a fixed
+ * order (the pairwise tree over a tile's samples that the plain call's v_loss takes, then over the tiles a sequential
+ * partial per thread of one 1024-thread workgroup and a tree) and one f32 product; u_s compares (double)U with the
+ * double q_s, and both kernels that need u_s and in_s evaluate the same expression on the same words. Host build: U is
+ * the double sum times 1 / N in double, compared in double. No floating-point atomics; equal arguments give equal bits.
+ * Eight launches instead of four (the value column waits for U, and d loss / d v_s for n_U: after the forward one
+ * workgroup forms U from the tiles' sums, a wave per tile counts u_s and the samples outside the clip, one workgroup
+ * adds the counts, and a workgroup per tile writes d loss / d v_s, adds its term to d loss / d pre-activations last, as
+ * the plain call does, and forms the tile's v_loss and b2[value] sums in the plain call's tree), all on the caller's
+ * stream: capturable, no allocation, no sync. With vf_coef = 0 the five gradients and stats 1, 3, 4, 5, 6, 7 equal the plain
+ * call's on the same arguments as numbers (the value term contributes +-0, added last).
+ * The plain calls' workspace queries serve these (header words 2..4 hold U and the counts). Checks, alignment,
+ * aliasing (vstats included), idx and the host build are as for the plain calls. */
+int gca_helicopter_policy_grad_vclip(const gca_heli_policy* p, int C, const uint8_t* local, const float* coarse,
+                                     const int32_t* action, const float* old_logits, const float* old_value,
+                                     const float* advantage, const float* returns, int64_t T, const int32_t* idx, int N,
+                                     float clip_coef, float ent_coef, float vf_coef, int norm_adv, float* g_w_local,
+                                     float* g_w_coarse, float* g_b1, float* g_w_out, float* g_b2, float* stats,
+                                     float* vstats, void* workspace, int64_t workspace_bytes, void* stream);
+int gca_bulldozer_policy_grad_vclip(const gca_bulldozer_policy* p, int C, const uint8_t* local, const float* coarse,
+                                    const int32_t* action, const float* old_logits, const float* old_value,
+                                    const float* advantage, const float* returns, int64_t T, const int32_t* idx, int N,
+                                    float clip_coef, float ent_coef, float vf_coef, int norm_adv, float* g_w_local,
+                                    float* g_w_coarse, float* g_b1, float* g_w_out, float* g_b2, float* stats,
+                                    float* vstats, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------ optimizer (the rest of the reference's update_ppo, agents/jax_ppo.py:1045-1114:
  * optax.chain(clip_by_global_norm(max_norm), adam(lr, b1, b2, eps)) with linear_schedule, :677-702 and :775-783)

@@ -12,8 +12,8 @@ tensors in place. --graph captures the rollout (K must be even: the env's curren
 update as two graphs and replays them; the draw is keyed by the env's time_step, which only grows, so a replayed rollout
 draws new actions.
 
-The defaults are the reference's PPOArgs (lr 2.5e-4, clip 0.1, 4 epochs x 4 minibatches, 128 steps); clip_vloss stays
-off, as everywhere in this project. The extension choice is not the agent's (rollout_policy's `extension`).
+The defaults are the reference's PPOArgs (lr 2.5e-4, clip 0.1, 4 epochs x 4 minibatches, 128 steps) but for clip_vloss, which
+is off unless --clip-vloss asks for the reference's clipped value loss. The extension choice is not the agent's (rollout_policy's `extension`).
 --retardant builds the policy with retardant=True: its observation then holds the env's dousing layer (the share of doused
 cells per block and a flag per window cell), so the shoot head sees where it has doused, as the reference's agent does in
 its RGB frame; without it the agent reads the grid alone. Needs a HIP device."""
@@ -44,6 +44,8 @@ def main():
     ap.add_argument("--gae-lambda", type=float, default=0.95)
     ap.add_argument("--graph", action="store_true", help="capture the rollout and one update as graphs and replay them")
     ap.add_argument("--retardant", action="store_true", help="the policy sees the env's retardant (dousing) layer")
+    ap.add_argument("--clip-vloss", action="store_true",
+                    help="the reference's clipped value loss (args.ppo.clip_vloss, on by default THERE; off here)")
     args = ap.parse_args()
     import torch
 
@@ -76,6 +78,8 @@ def main():
     bufs = dict(stats_out=new((steps, 8)), info_out=new((steps, 2)), perm_out=new((args.epochs, T), torch.int32),
                 grads_out={n: torch.empty_like(getattr(policy, n)) for n in WEIGHTS},
                 workspace=torch.empty_like(policy._ppo_workspace(N, None)))
+    if args.clip_vloss:
+        bufs.update(clip_vloss=True, vstats_out=new((steps, 3)))
     rollout = lambda seed: env.rollout_policy(policy, K, seed=seed, **outs)
     update = lambda: policy.ppo_update(opt, rec, adv, ret, epochs=args.epochs, minibatches=args.minibatches, seed=7,
                                        **hyper, **bufs)
@@ -110,7 +114,9 @@ def main():
         print(f"iteration {it}: mean reward {rec['reward'].mean().item():+.5f}  "
               f"episodes ended {int(rec['terminated'].sum().item())}  "
               f"loss {s[0]:+.5f}  pg {s[1]:+.5f}  entropy {s[3]:.4f}  kl {s[4]:.2e}  clip {s[5]:.3f}  "
-              f"grad norm {info[0]:.4f}  lr {info[1]:.3e}")
+              f"grad norm {info[0]:.4f}  lr {info[1]:.3e}" +
+              ("  U {:.4f}  u-share {:.3f}  v-clip {:.3f}".format(*bufs["vstats_out"][-1].tolist()) if args.clip_vloss
+               else ""))
 
 
 if __name__ == "__main__":

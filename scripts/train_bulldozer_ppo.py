@@ -43,6 +43,8 @@ def main():
     ap.add_argument("--vf-coef", type=float, default=0.5)
     ap.add_argument("--graph", action="store_true", help="capture one update as a graph and replay it")
     ap.add_argument("--autograd", action="store_true", help="the former loop: the per-head loss through autograd")
+    ap.add_argument("--clip-vloss", action="store_true",
+                    help="the reference's clipped value loss (args.ppo.clip_vloss, on by default THERE; off here)")
     args = ap.parse_args()
     import torch
 
@@ -50,6 +52,8 @@ def main():
         sys.exit("train_bulldozer_ppo.py needs a HIP device")
     if args.graph and args.autograd:
         sys.exit("train_bulldozer_ppo.py: --graph captures the device update; it does not go with --autograd")
+    if args.clip_vloss and args.autograd:
+        sys.exit("train_bulldozer_ppo.py: --clip-vloss is the device update's; it does not go with --autograd")
     from gymca_amd.forest_fire import ppo
     from gymca_amd.forest_fire.bulldozer import BatchedForestFireBulldozerEnv, BulldozerPolicy
     from gymca_amd.forest_fire.bulldozer.policy import WEIGHTS
@@ -73,6 +77,10 @@ def main():
                 perm_out=torch.empty((args.epochs, T), dtype=torch.int32, device=device),
                 grads_out={n: torch.empty_like(getattr(policy, n)) for n in WEIGHTS},
                 workspace=torch.empty_like(policy._ppo_workspace(N, None)))
+    records = ("local", "coarse", "action", "logits")
+    if args.clip_vloss:
+        bufs.update(clip_vloss=True, vstats_out=torch.empty((steps, 3), device=device))
+        records += ("value",)
 
     def autograd_update(rec):
         """The former loop: per minibatch the per-head loss through forward_torch, backward, Adam.step."""
@@ -121,7 +129,7 @@ def main():
         else:
             if graph is None:
                 # the graph reads the records at fixed addresses: the first rollout's tensors, refilled every iteration
-                rec0 = {k: rec[k] for k in ("local", "coarse", "action", "logits")}
+                rec0 = {k: rec[k] for k in records}
                 torch.cuda.synchronize(device)
                 graph = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(graph):
@@ -134,7 +142,9 @@ def main():
         print(f"iteration {it}: mean reward {rec['reward'].mean().item():+.5f}  "
               f"episodes ended {int(terminal.sum().item())}  terminated {int(rec['terminated'].sum().item())}  "
               f"loss {s[0]:+.5f}  pg {s[1]:+.5f}  entropy {s[3]:.4f}  kl {s[4]:.2e}  clip {s[5]:.3f}  "
-              f"grad norm {info[0]:.4f}  lr {info[1]:.3e}")
+              f"grad norm {info[0]:.4f}  lr {info[1]:.3e}" +
+              ("  U {:.4f}  u-share {:.3f}  v-clip {:.3f}".format(*bufs["vstats_out"][-1].tolist()) if args.clip_vloss
+               else ""))
 
 
 if __name__ == "__main__":

@@ -31,6 +31,8 @@ def main():
     ap.add_argument("--max-grad-norm", type=float, default=0.5, help="global-norm clip; 0 turns it off")
     ap.add_argument("--anneal", action="store_true", help="the reference's linear schedule over --updates")
     ap.add_argument("--graph", action="store_true", help="capture one update as a graph and replay it")
+    ap.add_argument("--clip-vloss", action="store_true",
+                    help="the reference's clipped value loss (args.ppo.clip_vloss, on by default THERE; off here)")
     ap.add_argument("--seed", type=int, default=1)
     args = ap.parse_args()
     import torch
@@ -56,6 +58,10 @@ def main():
                 perm_out=torch.empty((args.epochs, T), dtype=torch.int32, device=device),
                 grads_out={n: torch.empty_like(getattr(pol, n)) for n in WEIGHTS},
                 workspace=torch.empty_like(pol._ppo_workspace(T // args.minibatches, None)))
+    records = ("local", "coarse", "action", "logits")
+    if args.clip_vloss:
+        bufs.update(clip_vloss=True, vstats_out=torch.empty((steps, 3), device=device))
+        records += ("value",)
     graph = rec0 = None
     for update in range(args.updates):
         rec = env.rollout_policy(pol, K, seed=args.seed + update)
@@ -68,7 +74,7 @@ def main():
         else:
             if graph is None:
                 # the graph reads the records at fixed addresses: the first rollout's tensors, refilled every update
-                rec0 = {k: rec[k] for k in ("local", "coarse", "action", "logits")}
+                rec0 = {k: rec[k] for k in records}
                 torch.cuda.synchronize(device)
                 graph = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(graph):
@@ -80,7 +86,9 @@ def main():
         s, info = bufs["stats_out"][-1].tolist(), bufs["info_out"][-1].tolist()  # the update's one sync
         print(f"update {update:3d}  mean reward {rec['reward'].mean().item():+.4f}  loss {s[0]:+.4f}  "
               f"pg {s[1]:+.5f}  v {s[2]:.4f}  entropy {s[3]:.4f}  kl {s[4]:.2e}  clip {s[5]:.3f}  "
-              f"|g| {info[0]:.3f}  lr {info[1]:.2e}")
+              f"|g| {info[0]:.3f}  lr {info[1]:.2e}" +
+              ("  U {:.4f}  u-share {:.3f}  v-clip {:.3f}".format(*bufs["vstats_out"][-1].tolist()) if args.clip_vloss
+               else ""))
 
 
 if __name__ == "__main__":
