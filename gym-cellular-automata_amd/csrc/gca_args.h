@@ -198,9 +198,10 @@ static inline int gca_check_bdz_policy(const char* who, const gca_bulldozer_poli
     return GCA_OK;
 }
 
-static inline int gca_check_bdz_policy_act(const gca_bulldozer_policy* p, int C, const void* local, const void* coarse,
-                                           const void* steps_elapsed, const void* action, int E) {
-    const char* who = "bulldozer_policy_act";
+// gca_bulldozer_policy_act's conditions under the name `who`: gca_extension_policy_act's are the same
+static inline int gca_check_bdz_policy_act_as(const char* who, const gca_bulldozer_policy* p, int C, const void* local,
+                                              const void* coarse, const void* steps_elapsed, const void* action,
+                                              int E) {
     if (const int st = gca_check_bdz_policy(who, p)) return st;
     if (!local) return gca_refuse(who, "local is null");
     if (!coarse) return gca_refuse(who, "coarse is null");
@@ -208,6 +209,55 @@ static inline int gca_check_bdz_policy_act(const gca_bulldozer_policy* p, int C,
     if (!action) return gca_refuse(who, "action is null");
     if (!(E > 0)) return gca_refuse(who, "E > 0");
     return gca_check_policy_c(who, C);
+}
+
+static inline int gca_check_bdz_policy_act(const gca_bulldozer_policy* p, int C, const void* local, const void* coarse,
+                                           const void* steps_elapsed, const void* action, int E) {
+    return gca_check_bdz_policy_act_as("bulldozer_policy_act", p, C, local, coarse, steps_elapsed, action, E);
+}
+
+// ----------------------------------------------------------------- the extension policy (gca.h "extension policy")
+static inline int gca_check_advanced_display(const gca_obs_params* p, int E, int H, int W, const void* grid,
+                                             const void* is_night, const void* choice, int choice_stride,
+                                             const void* display_out) {
+    const char* who = "advanced_display";
+    if (!p) return gca_refuse(who, "params is null");
+    if (!grid) return gca_refuse(who, "grid is null");
+    if (!is_night) return gca_refuse(who, "is_night is null");
+    if (!display_out) return gca_refuse(who, "display_out is null");
+    if (!(E > 0 && H > 0 && W > 0)) return gca_refuse(who, "E, H, W must be positive");
+    if (!((int64_t)H * W < (1 << 30))) return gca_refuse(who, "grid too large (H * W < 2^30)");
+    if (!(p->n_ext >= 0 && p->n_ext <= GCA_OBS_MAX_EXT)) return gca_refuse(who, "0..4 extension channels");
+    if (choice && !(choice_stride >= 1)) return gca_refuse(who, "choice_stride >= 1");
+    const uintptr_t g0 = (uintptr_t)grid, d0 = (uintptr_t)display_out, n = (uintptr_t)E * (uintptr_t)H * (uintptr_t)W;
+    if (g0 < d0 + n && d0 < g0 + n)
+        return gca_refuse(who, "display_out may not overlap the grid (the blur reads neighbours)");
+    return GCA_OK;
+}
+
+// gca_advanced_policy_act_display: the display's conditions, gca_advanced_policy_act's on the plane and the policy, and
+// an action of three columns
+static inline int gca_check_advanced_policy_act_display(const gca_bulldozer_policy* policy, const gca_obs_params* p,
+                                                        const void* grid, const void* pos, const void* is_night,
+                                                        const void* time_step, const void* choice, int choice_stride,
+                                                        int E, int H, int W, const void* action, int action_stride) {
+    const char* who = "advanced_policy_act_display";
+    if (const int st = gca_check_bdz_policy(who, policy)) return st;
+    if (!p) return gca_refuse(who, "params is null");
+    if (!grid) return gca_refuse(who, "grid is null");
+    if (!pos) return gca_refuse(who, "pos is null");
+    if (!is_night) return gca_refuse(who, "is_night is null");
+    if (!time_step) return gca_refuse(who, "time_step is null");
+    if (!action) return gca_refuse(who, "action is null");
+    if (!(E > 0 && H > 0 && W > 0)) return gca_refuse(who, "E, H, W must be positive");
+    if (!((int64_t)H * W < (1 << 30))) return gca_refuse(who, "grid too large (H * W < 2^30)");
+    if (((p->empty | p->tree | p->fire) & ~0xFF) != 0) return gca_refuse(who, "the codes must be u8 values");
+    if (!(p->n_ext >= 0 && p->n_ext <= GCA_OBS_MAX_EXT)) return gca_refuse(who, "0..4 extension channels");
+    if (choice && !(choice_stride >= 1)) return gca_refuse(who, "choice_stride >= 1");
+    if (!(action_stride >= 3)) return gca_refuse(who, "action_stride >= 3");
+    const int64_t Hc = (H - 1) / policy->block + 1, Wc = (W - 1) / policy->block + 1;
+    if (2 * Hc * Wc > GCA_POLICY_C_MAX) return gca_refuse(who, "C = 2 Hc Wc, at most 15088");
+    return gca_check_policy_c(who, (int)(2 * Hc * Wc));
 }
 
 // gca_advanced_policy_act: gca_policy_observation's conditions on the plane (parity NULL, both parts always built; the
@@ -295,7 +345,7 @@ static inline int gca_check_gae(const void* reward, const void* value, const voi
 }
 
 // The agent of a gca_*_policy_grad call: what heads its refusals, which policy check speaks, and the network's outputs
-// (the logits of its heads and the value; ppo_plan's NOUT). The checks below are the two agents' alike.
+// (the logits of its heads and the value; ppo_plan's NOUT). The checks below are the three agents' alike.
 struct GcaGradAgent {
     const char* who;       // heads every refusal of the call
     const char* who_ws;    // heads the workspace query's refusal
@@ -307,6 +357,8 @@ constexpr GcaGradAgent GCA_GRAD_HELI{"helicopter_policy_grad", "helicopter_polic
                                      "workspace smaller than gca_helicopter_policy_grad_workspace", false, 10};
 constexpr GcaGradAgent GCA_GRAD_BDZ{"bulldozer_policy_grad", "bulldozer_policy_grad_workspace",
                                     "workspace smaller than gca_bulldozer_policy_grad_workspace", true, 12};
+constexpr GcaGradAgent GCA_GRAD_EXT{"extension_policy_grad", "extension_policy_grad_workspace",
+                                    "workspace smaller than gca_extension_policy_grad_workspace", true, 15};
 
 // a workspace query answers -1 where this refuses
 static inline int gca_check_policy_grad_workspace(const GcaGradAgent& a, const gca_policy* p, int C, int N) {
@@ -362,6 +414,8 @@ constexpr GcaGradAgent GCA_GRAD_HELI_VCLIP{"helicopter_policy_grad_vclip", "heli
                                            "workspace smaller than gca_helicopter_policy_grad_workspace", false, 10};
 constexpr GcaGradAgent GCA_GRAD_BDZ_VCLIP{"bulldozer_policy_grad_vclip", "bulldozer_policy_grad_workspace",
                                           "workspace smaller than gca_bulldozer_policy_grad_workspace", true, 12};
+constexpr GcaGradAgent GCA_GRAD_EXT_VCLIP{"extension_policy_grad_vclip", "extension_policy_grad_workspace",
+                                          "workspace smaller than gca_extension_policy_grad_workspace", true, 15};
 
 // What a _vclip call asks beyond gca_check_policy_grad (which speaks first): the recorded values, and a vstats (f32 [3],
 // nullable) that overlaps neither the other outputs nor the weights.

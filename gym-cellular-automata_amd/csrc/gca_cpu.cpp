@@ -24,6 +24,10 @@
 //                     the bulldozer policy
 //   gca_advanced_policy_observation / gca_advanced_policy_act_retardant  the same with the env's retardant in the
 //                     observation (gca_adv_policy.hip), pinned by tests/_retardant_obs_ref.py
+//   gca_advanced_display / gca_extension_policy_act / gca_advanced_policy_act_display / gca_extension_policy_grad(..)
+//                     the extension agent (gca_adv_policy.hip, gca_ppo.hip): the displayed plane in plain loops, the
+//                     network with fifteen outputs, the one call as the three it is defined by, the three-head gradient;
+//                     pinned by tests/_extension_policy_ref.py
 //   gca_gae / gca_helicopter_policy_grad(_workspace) / gca_bulldozer_policy_grad(_workspace)  the PPO update
 //                     (gca_ppo.hip): the GAE recurrence bit for bit, the loss gradient of either head layout in double
 //                     as a second yardstick; gca_*_policy_grad_vclip the same with the reference's clipped value loss
@@ -646,6 +650,150 @@ extern "C" int gca_bulldozer_policy_act(const gca_bulldozer_policy* p, int C, co
     return GCA_OK;
 }
 
+// ---------------------------------------------------------------- the extension policy (gca.h "extension policy")
+// The bulldozer policy with fifteen outputs: move and shoot by bdz_policy_eval_host's statements on the same draw, the
+// extension by the move rule over three logits on the draw's word 2.
+static int32_t policy_pick3_host(const float* l, int greedy, uint32_t x) {
+    float m = l[0];
+    int32_t first = 0;
+    for (int i = 1; i < 3; ++i)
+        if (l[i] > m) {
+            m = l[i];
+            first = i;
+        }
+    if (greedy) return first;
+    float c[3], s = 0.0f;
+    for (int i = 0; i < 3; ++i) {
+        s = s + exp_f32_host(l[i] - m);
+        c[i] = s;
+    }
+    const float t = u01_f32_host(x) * c[2];
+    for (int i = 0; i < 2; ++i)
+        if (t < c[i]) return i;
+    return 2;
+}
+
+extern "C" int gca_extension_policy_act(const gca_bulldozer_policy* p, int C, const uint8_t* local, const float* coarse,
+                                        const int64_t* steps_elapsed, const uint32_t* episode, int env_offset,
+                                        uint64_t policy_seed, int greedy, int32_t* action, float* logits, float* value,
+                                        int E, void*) {
+    if (const int st = gca_check_bdz_policy_act_as("extension_policy_act", p, C, local, coarse, steps_elapsed, action, E))
+        return st;
+    const size_t SS = (size_t)(2 * p->radius + 1) * (2 * p->radius + 1);
+    for (int e = 0; e < E; ++e) {
+        float out[15];
+        policy_outputs_host(p, 15, C, local + e * SS, coarse + (size_t)e * C, out);
+        const u32x4 x = philox4x32_10(u32x4{(uint32_t)steps_elapsed[e], (uint32_t)(env_offset + e),
+                                            episode ? episode[e] : 0u, GCA_TAG_BPOLICY},
+                                      (uint32_t)policy_seed, (uint32_t)(policy_seed >> 32));
+        int32_t* act = action + 3 * (size_t)e;
+        act[0] = policy_move_host(out, greedy, x.x);
+        const float s0 = out[9], s1 = out[10];
+        if (greedy) {
+            act[1] = s1 > s0 ? 1 : 0;
+        } else {
+            const float ms = s1 > s0 ? s1 : s0;
+            const float c0 = exp_f32_host(s0 - ms), c1 = c0 + exp_f32_host(s1 - ms);
+            act[1] = u01_f32_host(x.y) * c1 < c0 ? 0 : 1;
+        }
+        act[2] = policy_pick3_host(out + 11, greedy, x.z);
+        if (logits) memcpy(logits + (size_t)e * 14, out, 14 * sizeof(float));
+        if (value) value[e] = out[14];
+    }
+    return GCA_OK;
+}
+
+// The displayed plane (gca.h "extension policy") in plain loops: per env the day/night, the active channels, the
+// selection scan over ROWS, then every cell's value of the channel shown.
+extern "C" int gca_advanced_display(const gca_obs_params* p, int E, int H, int W, const uint8_t* grid,
+                                    const int32_t* is_night, const int32_t* time_step, const int32_t* choice,
+                                    int choice_stride, uint8_t* display_out, void*) {
+    if (const int st = gca_check_advanced_display(p, E, H, W, grid, is_night, choice, choice_stride, display_out))
+        return st;
+    const int64_t HW = (int64_t)H * W;
+    for (int e = 0; e < E; ++e) {
+        const uint8_t* g = grid + e * HW;
+        uint8_t* out = display_out + e * HW;
+        bool night = is_night[e] != 0;
+        if (time_step && p->day_length > 0 && time_step[e] % p->day_length == 0) night = !night;
+        uint32_t on = 0u;
+        if (p->enable_extensions && p->n_choices > 0) {
+            int c = choice ? choice[(int64_t)e * choice_stride] : 0;
+            const int top = (p->n_choices < 8 ? p->n_choices : 8) - 1;
+            c = c < 0 ? 0 : (c > top ? top : c);
+            for (int i = 0; i < p->n_ext; ++i) on |= (p->ext_lookup[c][i] != 0 ? 1u : 0u) << i;
+        }
+        auto blur = [&](int r, int c) {
+            int s = 0;
+            for (int dr = -1; dr <= 1; ++dr)
+                for (int dc = -1; dc <= 1; ++dc) {
+                    const int rr = r + dr < 0 ? 0 : (r + dr > H - 1 ? H - 1 : r + dr);
+                    const int cc = c + dc < 0 ? 0 : (c + dc > W - 1 ? W - 1 : c + dc);
+                    s += g[(int64_t)rr * W + cc];
+                }
+            return (2 * s + 9) / 18;
+        };
+        auto transform = [&](int r, int c, int skip_vis, int skip_blur) {
+            int v = skip_blur ? g[(int64_t)r * W + c] : blur(r, c);
+            if (!skip_vis && v == 3 && !night) v = 0;
+            return v;
+        };
+        auto ext = [&](int i, int r, int c) {
+            return ((on >> i) & 1u) ? transform(r, c, p->ext_skip_visibility[i], p->ext_skip_blur[i]) : 0;
+        };
+        int sel = -1;
+        if (on) {
+            int fv = -1;
+            for (int r = 0; r < H && fv < 0; ++r)
+                for (int c = 0; c < W && fv < 0; ++c)
+                    for (int i = 0; i < p->n_ext; ++i)
+                        if (ext(i, r, c) > 0) fv = r;
+            if (fv >= 0) sel = fv < p->n_ext - 1 ? fv : p->n_ext - 1;
+        }
+        for (int r = 0; r < H; ++r)
+            for (int c = 0; c < W; ++c)
+                out[(int64_t)r * W + c] = (uint8_t)(sel >= 0 ? ext(sel, r, c)
+                                                            : (p->should_transform ? transform(r, c, 0, 0)
+                                                                                   : g[(int64_t)r * W + c]));
+    }
+    return GCA_OK;
+}
+
+// Observe the displayed plane and act (gca.h "extension policy") as the three host functions it is defined by. `choice`
+// may be column 2 of `action`: it is read (by the display) before any action is written.
+extern "C" int gca_advanced_policy_act_display(const gca_bulldozer_policy* policy, const gca_obs_params* p,
+                                               const uint8_t* grid, const int32_t* pos, const int32_t* is_night,
+                                               const int32_t* time_step, const int32_t* choice, int choice_stride,
+                                               int E, int H, int W, int env_offset, uint64_t policy_seed, int greedy,
+                                               int32_t* action, int action_stride, float* logits, float* value,
+                                               uint8_t* local_out, float* coarse_out, void*) {
+    if (const int st = gca_check_advanced_policy_act_display(policy, p, grid, pos, is_night, time_step, choice,
+                                                             choice_stride, E, H, W, action, action_stride))
+        return st;
+    const int B = policy->block, S = 2 * policy->radius + 1;
+    const int C = 2 * ((H + B - 1) / B) * ((W + B - 1) / B);
+    std::vector<uint8_t> plane((size_t)E * H * W);
+    if (const int st = gca_advanced_display(p, E, H, W, grid, is_night, time_step, choice, choice_stride, plane.data(),
+                                            nullptr))
+        return st;
+    std::vector<uint8_t> loc(local_out ? 0 : (size_t)E * S * S);
+    std::vector<float> coa(coarse_out ? 0 : (size_t)E * C);
+    uint8_t* loc_p = local_out ? local_out : loc.data();
+    float* coa_p = coarse_out ? coarse_out : coa.data();
+    if (const int st = gca_policy_observation(plane.data(), nullptr, nullptr, pos, E, H, W, p->empty, p->tree, p->fire,
+                                              policy->radius, B, 0, loc_p, coa_p, nullptr))
+        return st;
+    std::vector<int64_t> se((size_t)E);
+    std::vector<int32_t> act(3 * (size_t)E);
+    for (int e = 0; e < E; ++e) se[e] = (int64_t)time_step[e];
+    if (const int st = gca_extension_policy_act(policy, C, loc_p, coa_p, se.data(), nullptr, env_offset, policy_seed,
+                                                greedy, act.data(), logits, value, E, nullptr))
+        return st;
+    for (int e = 0; e < E; ++e)
+        for (int j = 0; j < 3; ++j) action[(size_t)e * action_stride + j] = act[3 * (size_t)e + j];
+    return GCA_OK;
+}
+
 // The Advanced env's observe-and-act (gca.h "advanced policy") as the two host functions it is defined by: the
 // observation of the one plane, then the bulldozer policy on the widened time_step; a record the caller does not keep
 // lives in a vector.
@@ -1013,6 +1161,35 @@ extern "C" int gca_bulldozer_policy_grad_vclip(const gca_bulldozer_policy* p, in
                                                void* workspace, int64_t workspace_bytes, void*) {
     const int heads[2] = {9, 2};
     return policy_grad_host(GCA_GRAD_BDZ_VCLIP, 2, heads, p, C, local, coarse, action, old_logits, advantage, returns,
+                            T, idx, N, clip_coef, ent_coef, vf_coef, norm_adv, g_w_local, g_w_coarse, g_b1, g_w_out,
+                            g_b2, stats, workspace, workspace_bytes, true, old_value, vstats);
+}
+
+extern "C" int64_t gca_extension_policy_grad_workspace(const gca_bulldozer_policy* p, int C, int N) {
+    return policy_grad_workspace_host(GCA_GRAD_EXT, p, C, N);
+}
+
+extern "C" int gca_extension_policy_grad(const gca_bulldozer_policy* p, int C, const uint8_t* local,
+                                         const float* coarse, const int32_t* action, const float* old_logits,
+                                         const float* advantage, const float* returns, int64_t T, const int32_t* idx,
+                                         int N, float clip_coef, float ent_coef, float vf_coef, int norm_adv,
+                                         float* g_w_local, float* g_w_coarse, float* g_b1, float* g_w_out, float* g_b2,
+                                         float* stats, void* workspace, int64_t workspace_bytes, void*) {
+    const int heads[3] = {9, 2, 3};
+    return policy_grad_host(GCA_GRAD_EXT, 3, heads, p, C, local, coarse, action, old_logits, advantage, returns, T, idx,
+                            N, clip_coef, ent_coef, vf_coef, norm_adv, g_w_local, g_w_coarse, g_b1, g_w_out, g_b2, stats,
+                            workspace, workspace_bytes);
+}
+
+extern "C" int gca_extension_policy_grad_vclip(const gca_bulldozer_policy* p, int C, const uint8_t* local,
+                                               const float* coarse, const int32_t* action, const float* old_logits,
+                                               const float* old_value, const float* advantage, const float* returns,
+                                               int64_t T, const int32_t* idx, int N, float clip_coef, float ent_coef,
+                                               float vf_coef, int norm_adv, float* g_w_local, float* g_w_coarse,
+                                               float* g_b1, float* g_w_out, float* g_b2, float* stats, float* vstats,
+                                               void* workspace, int64_t workspace_bytes, void*) {
+    const int heads[3] = {9, 2, 3};
+    return policy_grad_host(GCA_GRAD_EXT_VCLIP, 3, heads, p, C, local, coarse, action, old_logits, advantage, returns,
                             T, idx, N, clip_coef, ent_coef, vf_coef, norm_adv, g_w_local, g_w_coarse, g_b1, g_w_out,
                             g_b2, stats, workspace, workspace_bytes, true, old_value, vstats);
 }

@@ -23,6 +23,7 @@
 //   S < 5000, so the integer rounding floor((2S + 9) / 18) is the reference's result);
 //   vis(v) = (v == 3 && !is_night) ? 0 : v   (the reference's literal 3, extension_utils.py:93).
 #include "gca_common.h"
+#include "gca_obs_dev.h"  // the cell transforms and the display selection, shared with gca_adv_policy.hip
 
 // Measured choices (the A/B variants were removed after the measurement):
 //   wave-local RGB transposition (each wave stores its own 3 KiB, no barriers per round; r01p: 0.713 vs 0.722 ms for
@@ -46,35 +47,6 @@ __device__ __forceinline__ int blur_lds(const uint8_t* __restrict__ T, int W, in
     }
     return (2 * s + 9) / 18;
 }
-// the same from global memory (display selection scan)
-__device__ __forceinline__ int blur_at(const uint8_t* __restrict__ g, int H, int W, int r, int c) {
-    int s = 0;
-#pragma unroll
-    for (int dr = -1; dr <= 1; ++dr) {
-        const int rr = min(max(r + dr, 0), H - 1);
-#pragma unroll
-        for (int dc = -1; dc <= 1; ++dc) s += g[(int64_t)rr * W + min(max(c + dc, 0), W - 1)];
-    }
-    return (2 * s + 9) / 18;
-}
-
-__device__ __forceinline__ int transform(int raw, int blurred, bool night, int skip_vis, int skip_blur) {
-    int v = skip_blur ? raw : blurred;
-    if (!skip_vis && v == 3 && !night) v = 0;
-    return v;
-}
-
-struct ObsCfg {
-    bool need_blur;  // some channel in use blurs
-    uint32_t on;     // active extension channels
-    bool night;      // pre-step day/night
-};
-
-// base channel + active extension channels of one cell from its raw value and blur
-__device__ __forceinline__ int ext_value(const gca_obs_params& p, const ObsCfg& k, int i, int raw, int bl) {
-    return ((k.on >> i) & 1u) ? transform(raw, bl, k.night, p.ext_skip_visibility[i], p.ext_skip_blur[i]) : 0;
-}
-
 __device__ __forceinline__ int colour_kind(const gca_obs_params& p, int v, bool at_pos) {
     return at_pos ? 3 : (v == p.tree ? 1 : (v == p.fire ? 2 : 0));
 }
@@ -123,14 +95,11 @@ __global__ __launch_bounds__(256) void adv_observation_kernel(gca_obs_params p, 
     const uint8_t* du = dousing ? dousing + e * HW : nullptr;
     ObsCfg k;
     // the observation uses the PRE-step is_night; the env step toggled it when time_step % day_length == 0
-    k.night = is_night[e] != 0;
-    if (time_step && p.day_length > 0 && time_step[e] % p.day_length == 0) k.night = !k.night;
+    k.night = obs_night(p, is_night, time_step, e);
     const int pr = pos[2 * e], pc = pos[2 * e + 1];
     k.on = 0u;
-    if (mode == 0 && p.enable_extensions && action && action_stride >= 3 && p.n_choices > 0) {
-        const int choice = min(max(action[(int64_t)e * action_stride + 2], 0), min(p.n_choices, 8) - 1);
-        for (int i = 0; i < p.n_ext; ++i) k.on |= (p.ext_lookup[choice][i] != 0 ? 1u : 0u) << i;
-    }
+    if (mode == 0 && p.enable_extensions && action && action_stride >= 3 && p.n_choices > 0)
+        k.on = obs_channels_on(p, action[(int64_t)e * action_stride + 2]);
     k.need_blur = mode == 0 && p.should_transform != 0;
     for (int i = 0; i < p.n_ext; ++i) k.need_blur |= ((k.on >> i) & 1u) && !p.ext_skip_blur[i];
     const int nch = 3 + p.n_ext;
@@ -166,31 +135,7 @@ __global__ __launch_bounds__(256) void adv_observation_kernel(gca_obs_params p, 
     int sel = -1;     // mode 0: -1 = base channel, else the extension channel shown everywhere
     int col_sel = 0;  // mode 1: column of the raw grid shown
     if (mode == 0 && k.on) {
-        bool scan_blur = false;
-        for (int i = 0; i < p.n_ext; ++i) scan_blur |= ((k.on >> i) & 1u) && !p.ext_skip_blur[i];
-        int fv = -1;
-        for (int r = 0; r < H && fv < 0; ++r) {
-            int any = 0;
-            if ((W & 3) == 0) {
-                for (int c4 = 4 * lane; c4 < W; c4 += 256) {
-                    const uint32_t w = *reinterpret_cast<const uint32_t*>(g + (int64_t)r * W + c4);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const int raw = (int)((w >> (8 * j)) & 0xFFu);
-                        const int bl = scan_blur ? blur_at(g, H, W, r, c4 + j) : raw;
-                        for (int i = 0; i < p.n_ext; ++i) any |= ext_value(p, k, i, raw, bl) > 0;
-                    }
-                }
-            } else {
-                for (int c = lane; c < W; c += 64) {
-                    const int raw = g[(int64_t)r * W + c];
-                    const int bl = scan_blur ? blur_at(g, H, W, r, c) : raw;
-                    for (int i = 0; i < p.n_ext; ++i) any |= ext_value(p, k, i, raw, bl) > 0;
-                }
-            }
-            if (__ballot(any) != 0ull) fv = r;
-        }
-        if (fv >= 0) sel = min(fv, p.n_ext - 1);
+        sel = obs_display_select(p, k, g, H, W, lane);
     } else if (mode == 1 && W > 3) {
         int fv = -1;
         for (int r = 0; r < H && fv < 0; ++r) {

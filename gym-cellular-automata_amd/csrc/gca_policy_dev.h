@@ -1,9 +1,10 @@
 // gca_policy_dev.h — the policy network of both agents (include/gca.h "helicopter policy", "bulldozer policy") as device
 // functions of ONE workgroup per env, written once: the weights' view, the LDS layout, the network from the observation
-// to its NOUT outputs (policy_outputs<NOUT, NT>: 10 for the helicopter, 12 for the bulldozer) and the two agents'
-// samplers. The stand-alone act kernels and the resident policy rollouts (gca_heli.hip, gca_windy.hip) all evaluate the
-// network through policy_outputs, with the same instructions in the same order: a rollout is bit for bit
-// K x (observe, act, step), and an output column is the same sum whichever agent owns it.
+// to its NOUT outputs (policy_outputs<NOUT, NT>: 10 for the helicopter, 12 for the bulldozer, 15 for the bulldozer with
+// the extension head) and the agents' samplers. The stand-alone act kernels and the resident policy rollouts
+// (gca_heli.hip, gca_windy.hip) all evaluate the network through policy_outputs, with the same instructions in the same
+// order: a rollout is bit for bit K x (observe, act, step), and an output column is the same sum whichever agent owns
+// it.
 //
 // The summation order is the one written down in gca.h; here is how the workgroup realises it. The layout is that of
 // 256 float4 "virtual threads"; the workgroup is either exactly those 256 threads (NT = 256: the two act kernels and
@@ -15,11 +16,12 @@
 //           and g = vt / (Hd / 4) the group of G = 1024 / Hd. It adds the terms n = g, g + G, ... in that order onto
 //           0.0f, four rows in flight, and writes part[g][4 q ..]. Real thread tid runs vt = tid, tid + nt, ... < 256.
 //   relu    unit j = tid, tid + nt, ... < Hd: h_j = relu(b1[j] + p_0[j] + .. + p_{G-1}[j]), left to right, to LDS.
-//   heads   virtual lane t < 192 is lane r = t % 16 of output o = t / 16: it adds w_out[j][o] * h_j for j = r, r + 16,
+//   heads   virtual lane t < policy_head_lanes(NOUT) (16 NOUT rounded up to whole waves: 192 for 10 and 12 outputs,
+//           256 for 15) is lane r = t % 16 of output o = t / 16: it adds w_out[j][o] * h_j for j = r, r + 16,
 //           ... onto 0.0f in that order, and the 16 lanes of an output meet in the xor butterfly 8, 4, 2, 1 (f32
-//           addition commutes, so every lane holds the tree's value). 192 = 3 * 64 and nt is a multiple of 64, so a
+//           addition commutes, so every lane holds the tree's value). The lane count and nt are multiples of 64, so a
 //           wave runs an iteration with all 64 lanes or not at all: every shuffle finds its partner. With NOUT = 10
-//           lanes 160..191 compute a clamped duplicate of output 9 and store nothing.
+//           lanes 160..191 compute a clamped duplicate of output 9 and store nothing; with 15, lanes 240..255 do.
 //   sample  every thread reads the outputs back and samples redundantly: the action is known to all threads without
 //           another barrier (the rollouts carry the env's state in every thread).
 // Four barriers, each outside every condition (the loops' trip counts differ between threads, the barriers sit between
@@ -35,9 +37,11 @@
 
 constexpr int POL_VT = 256;            // virtual threads of the hidden layer; the act kernels' workgroup
 constexpr int POL_PART = 4 * POL_VT;   // floats of the partials: G * Hd = 1024 for every Hd
-constexpr int POL_HEADS = 192;         // virtual lanes of the heads: 16 per output, whole waves
 constexpr int HELI_POL_NOUT = 10;      // 9 action logits and the value
 constexpr int BDZ_POL_NOUT = 12;       // 9 move logits, 2 shoot logits and the value
+constexpr int EXT_POL_NOUT = 15;       // 9 move logits, 2 shoot logits, 3 extension logits and the value
+// virtual lanes of the heads: 16 per output, rounded up to whole waves (192 for 10 and 12 outputs, 256 for 15)
+__host__ __device__ constexpr int policy_head_lanes(int NOUT) { return (16 * NOUT + 63) & ~63; }
 
 struct PolicyW {
     const float* __restrict__ w_local;   // [S*S][4][Hd], 16-B aligned
@@ -95,7 +99,8 @@ template <int NOUT, int NT, class ClassAt, class Record>
 __device__ __forceinline__ void policy_outputs(const PolicyW& w, const float* cs, float* part, float* hs, float* outs,
                                                int tid, int nt, float* logits_row, float* value_ptr, ClassAt class_at,
                                                Record record, float (&o)[NOUT]) {
-    static_assert(16 * NOUT <= POL_HEADS && POL_HEADS % 64 == 0 && (NT == 0 || NT == POL_VT), "whole waves");
+    constexpr int HEADS = policy_head_lanes(NOUT);
+    static_assert(NOUT <= 16 && HEADS <= POL_VT && HEADS % 64 == 0 && (NT == 0 || NT == POL_VT), "whole waves");
     __syncthreads();  // A
     const int Hd = w.Hd, lgQ = w.lgHd - 2;  // 2^lgQ = Hd / 4 virtual threads per weight row
     const int G = POL_PART >> w.lgHd;
@@ -142,7 +147,7 @@ __device__ __forceinline__ void policy_outputs(const PolicyW& w, const float* cs
         hs[j] = h > 0.0f ? h : 0.0f;
     });
     __syncthreads();  // C
-    policy_each<NT>(tid, nt, POL_HEADS, [&](int t) {  // whole waves (see above)
+    policy_each<NT>(tid, nt, HEADS, [&](int t) {  // whole waves (see above)
         const int oo = min(t >> 4, NOUT - 1), r = t & 15;
         float qs = 0.0f;
         for (int jj = r; jj < Hd; jj += 16) qs = qs + w.w_out[jj * NOUT + oo] * hs[jj];
@@ -194,8 +199,25 @@ __device__ __forceinline__ int32_t heli_policy_sample(const float (&o)[HELI_POL_
 // ---- the bulldozer's sampler. (move, shoot) from the twelve outputs (gca.h "bulldozer policy"). Comparisons only, no
 // fmax: NaN logits give a move in [0, 8] and a shoot in {0, 1}. Plain loops, the same in every thread. The draw is
 // keyed (steps_elapsed, env, episode, BPOLICY).
-__device__ __forceinline__ void bdz_policy_sample(const float (&o)[BDZ_POL_NOUT], const PolicyW& w, uint32_t step,
-                                                  uint32_t env_id, uint32_t ep, int32_t& move, int32_t& shoot) {
+// With fifteen outputs (gca.h "extension policy") the same draw's word 2 picks the extension from o[11..13] by the move
+// rule over three logits; move and shoot are computed by the very same statements, so equal logits and an equal seed
+// give the two-head agent's move and shoot.
+template <int NOUT>
+__device__ __forceinline__ void bdz_policy_sample(const float (&o)[NOUT], const PolicyW& w, uint32_t step,
+                                                  uint32_t env_id, uint32_t ep, int32_t& move, int32_t& shoot,
+                                                  int32_t* ext = nullptr) {
+    static_assert(NOUT == BDZ_POL_NOUT || NOUT == EXT_POL_NOUT, "the bulldozer's two or three heads");
+    float em = 0.0f;
+    int32_t efirst = 0;
+    if constexpr (NOUT == EXT_POL_NOUT) {
+        em = o[11];
+#pragma unroll
+        for (int i = 1; i < 3; ++i)
+            if (o[11 + i] > em) {
+                em = o[11 + i];
+                efirst = i;
+            }
+    }
     float m = o[0];
     int32_t first = 0;
 #pragma unroll
@@ -208,6 +230,7 @@ __device__ __forceinline__ void bdz_policy_sample(const float (&o)[BDZ_POL_NOUT]
     if (w.greedy) {
         move = first;
         shoot = s1 > s0 ? 1 : 0;
+        if constexpr (NOUT == EXT_POL_NOUT) *ext = efirst;
         return;
     }
     float c[9], s = 0.0f;
@@ -226,4 +249,18 @@ __device__ __forceinline__ void bdz_policy_sample(const float (&o)[BDZ_POL_NOUT]
     const float ms = s1 > s0 ? s1 : s0;
     const float c0 = exp_f32(s0 - ms), c1 = c0 + exp_f32(s1 - ms);
     shoot = u01_f32(x.y) * c1 < c0 ? 0 : 1;
+    if constexpr (NOUT == EXT_POL_NOUT) {
+        float ce[3], se = 0.0f;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            se = se + exp_f32(o[11 + i] - em);
+            ce[i] = se;
+        }
+        const float te = u01_f32(x.z) * ce[2];
+        int32_t ev = 2;
+#pragma unroll
+        for (int i = 1; i >= 0; --i)
+            if (te < ce[i]) ev = i;
+        *ext = ev;
+    }
 }

@@ -2,7 +2,8 @@
 // generalised advantage estimate in one launch, and gca_helicopter_policy_grad / gca_bulldozer_policy_grad, the PPO
 // clipped-surrogate loss (per head), its statistics and its gradient with respect to the five policy tensors over a
 // minibatch of rollout_policy's records. The kernels are written over a compile-time head layout PpoHeads<N0, N1>:
-// (9) for the helicopter, NOUT = 10 outputs; (9, 2) for the bulldozer, NOUT = 12; the value is column NOUT - 1.
+// (9) for the helicopter, NOUT = 10 outputs; (9, 2) for the bulldozer, NOUT = 12; (9, 2, 3) for the bulldozer with the
+// extension head (gca_extension_policy_grad), NOUT = 15; the value is column NOUT - 1.
 //
 // A policy_grad call is four launches on the caller's stream, all sums in a fixed order (no atomics):
 //   adv     one workgroup: mean and population standard deviation of the minibatch's advantages (two passes, a
@@ -143,12 +144,14 @@ struct PpoLossArgs {
     int norm_adv;
 };
 
-// The head layout: N0 logits of the first head, N1 of the second (0: one head), then the value.
-template <int N0_, int N1_>
+// The head layout: N0 logits of the first head, N1 of the second (0: one head), N2 of the third (0: two heads), then
+// the value.
+template <int N0_, int N1_, int N2_ = 0>
 struct PpoHeads {
-    static constexpr int N0 = N0_, N1 = N1_;
-    static constexpr int NH = N1 > 0 ? 2 : 1;  // heads
-    static constexpr int NL = N0 + N1;         // logits = the width of a record's old_logits
+    static constexpr int N0 = N0_, N1 = N1_, N2 = N2_;
+    static_assert(N1 > 0 || N2 == 0, "a third head follows a second");
+    static constexpr int NH = N2 > 0 ? 3 : (N1 > 0 ? 2 : 1);  // heads
+    static constexpr int NL = N0 + N1 + N2;    // logits = the width of a record's old_logits
     static constexpr int NOUT = NL + 1;        // outputs (ppo_plan's NOUT)
     static constexpr int OST = NOUT + 1;       // row stride of a tile's outputs in LDS
     static constexpr int TP = ppo_tp(NOUT);    // floats of a tile partial
@@ -239,7 +242,7 @@ __global__ __launch_bounds__(PPO_THREADS) void ppo_fwd_kernel(
     __shared__ float outs[TS * OST], douts[TS * OST], tsum[TS * PPO_TP];
     __shared__ int rows[TS];
     static_assert((Cf::UNI + HD * NOUT + HL::WO + 2 * TS * OST + TS * PPO_TP + TS) * 4 <= 64 * 1024,
-                  "the forward kernel's static LDS (55344 B at NOUT = 12, HD = 256)");
+                  "the forward kernel's static LDS (55344 B at NOUT = 12, 59200 B at NOUT = 15; HD = 256)");
     float* const wbuf = uni;
     float* const xs = uni + Cf::WBUF;
     uint8_t* const clsb = reinterpret_cast<uint8_t*>(xs);  // TS * CH <= 2048 bytes
@@ -377,9 +380,18 @@ __global__ __launch_bounds__(PPO_THREADS) void ppo_fwd_kernel(
             const double inv_n = 1.0 / (double)b.N, inv_nh = NH == 1 ? inv_n : 1.0 / ((double)b.N * (double)NH);
             const float* __restrict__ old = b.old_logits + (size_t)row * NL;
             PpoHeadTerms t = ppo_head<HL::N0>(b, row, hdr, outs + s * OST, old, b.action[(size_t)row * NH], la, inv_nh, d);
-            if constexpr (NH == 2) {
+            if constexpr (NH >= 2) {
                 const PpoHeadTerms u = ppo_head<HL::N1>(b, row, hdr, outs + s * OST + HL::N0, old + HL::N0,
                                                         b.action[(size_t)row * NH + 1], la, inv_nh, d + HL::N0);
+                t.pg = t.pg + u.pg;
+                t.ent = t.ent + u.ent;
+                t.kl = t.kl + u.kl;
+                t.clipped = t.clipped + u.clipped;
+            }
+            if constexpr (NH == 3) {
+                constexpr int O2 = HL::N0 + HL::N1;
+                const PpoHeadTerms u = ppo_head<HL::N2>(b, row, hdr, outs + s * OST + O2, old + O2,
+                                                        b.action[(size_t)row * NH + 2], la, inv_nh, d + O2);
                 t.pg = t.pg + u.pg;
                 t.ent = t.ent + u.ent;
                 t.kl = t.kl + u.kl;
@@ -730,7 +742,7 @@ __global__ __launch_bounds__(PPO_THREADS) void ppo_reduce_kernel(PpoPlan pl, Ppo
     if (tid < NOUT) out.g_b2[tid] = red[5 + tid];
     if (tid == 0) {
         // pg, the entropy, approx_kl and the clip fraction are means over the N * NH (sample, head) pairs (1 / NH is
-        // exact for one and two heads), the value loss over the N samples
+        // exact for one and two heads, one rounded division for three), the value loss over the N samples
         const float inv_nh = NH == 1 ? la.inv_n : la.inv_n / (float)NH;
         const float pg = red[0] * inv_nh, vl = red[1] * la.inv_n, ent = red[2] * inv_nh;
         out.stats[0] = (pg - la.ent_coef * ent) + la.vf_coef * vl;
@@ -747,6 +759,7 @@ __global__ __launch_bounds__(PPO_THREADS) void ppo_reduce_kernel(PpoPlan pl, Ppo
 // ------------------------------------------------------------------ host side
 using PpoHeli = PpoHeads<9, 0>;
 using PpoBdz = PpoHeads<9, 2>;
+using PpoExt = PpoHeads<9, 2, 3>;
 
 static int64_t ppo_workspace(const GcaGradAgent& ag, const gca_policy* p, int C, int N) {
     if (gca_check_policy_grad_workspace(ag, p, C, N)) return -1;
@@ -760,6 +773,10 @@ extern "C" int64_t gca_helicopter_policy_grad_workspace(const gca_heli_policy* p
 
 extern "C" int64_t gca_bulldozer_policy_grad_workspace(const gca_bulldozer_policy* p, int C, int N) {
     return ppo_workspace(GCA_GRAD_BDZ, p, C, N);
+}
+
+extern "C" int64_t gca_extension_policy_grad_workspace(const gca_bulldozer_policy* p, int C, int N) {
+    return ppo_workspace(GCA_GRAD_EXT, p, C, N);
 }
 
 template <int HD, class HL, bool VCLIP>
@@ -801,7 +818,7 @@ static int ppo_policy_grad(const GcaGradAgent& ag, const gca_policy* p, int C, c
                            float clip_coef, float ent_coef, float vf_coef, int norm_adv, float* g_w_local,
                            float* g_w_coarse, float* g_b1, float* g_w_out, float* g_b2, float* stats, float* vstats,
                            void* workspace, int64_t workspace_bytes, void* stream) {
-    static_assert(HL::NOUT == 10 || HL::NOUT == 12, "the agents' outputs (GcaGradAgent::nout)");
+    static_assert(HL::NOUT == 10 || HL::NOUT == 12 || HL::NOUT == 15, "the agents' outputs (GcaGradAgent::nout)");
     PpoPlan pl;
     if constexpr (VCLIP) {
         if (const int st = gca_check_policy_grad_vclip(ag, p, C, local, coarse, action, old_logits, old_value, advantage,
@@ -875,6 +892,31 @@ extern "C" int gca_bulldozer_policy_grad_vclip(const gca_bulldozer_policy* p, in
                                                float* g_b1, float* g_w_out, float* g_b2, float* stats, float* vstats,
                                                void* workspace, int64_t workspace_bytes, void* stream) {
     return ppo_policy_grad<PpoBdz, true>(GCA_GRAD_BDZ_VCLIP, p, C, local, coarse, action, old_logits, old_value,
+                                         advantage, returns, T, idx, N, clip_coef, ent_coef, vf_coef, norm_adv,
+                                         g_w_local, g_w_coarse, g_b1, g_w_out, g_b2, stats, vstats, workspace,
+                                         workspace_bytes, stream);
+}
+
+extern "C" int gca_extension_policy_grad(const gca_bulldozer_policy* p, int C, const uint8_t* local,
+                                         const float* coarse, const int32_t* action, const float* old_logits,
+                                         const float* advantage, const float* returns, int64_t T, const int32_t* idx,
+                                         int N, float clip_coef, float ent_coef, float vf_coef, int norm_adv,
+                                         float* g_w_local, float* g_w_coarse, float* g_b1, float* g_w_out, float* g_b2,
+                                         float* stats, void* workspace, int64_t workspace_bytes, void* stream) {
+    return ppo_policy_grad<PpoExt, false>(GCA_GRAD_EXT, p, C, local, coarse, action, old_logits, nullptr, advantage,
+                                          returns, T, idx, N, clip_coef, ent_coef, vf_coef, norm_adv, g_w_local,
+                                          g_w_coarse, g_b1, g_w_out, g_b2, stats, nullptr, workspace, workspace_bytes,
+                                          stream);
+}
+
+extern "C" int gca_extension_policy_grad_vclip(const gca_bulldozer_policy* p, int C, const uint8_t* local,
+                                               const float* coarse, const int32_t* action, const float* old_logits,
+                                               const float* old_value, const float* advantage, const float* returns,
+                                               int64_t T, const int32_t* idx, int N, float clip_coef, float ent_coef,
+                                               float vf_coef, int norm_adv, float* g_w_local, float* g_w_coarse,
+                                               float* g_b1, float* g_w_out, float* g_b2, float* stats, float* vstats,
+                                               void* workspace, int64_t workspace_bytes, void* stream) {
+    return ppo_policy_grad<PpoExt, true>(GCA_GRAD_EXT_VCLIP, p, C, local, coarse, action, old_logits, old_value,
                                          advantage, returns, T, idx, N, clip_coef, ent_coef, vf_coef, norm_adv,
                                          g_w_local, g_w_coarse, g_b1, g_w_out, g_b2, stats, vstats, workspace,
                                          workspace_bytes, stream);

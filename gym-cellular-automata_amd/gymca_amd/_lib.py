@@ -293,6 +293,16 @@ _SIGNATURES = {
                                         c_int),
     "gca_advanced_policy_act_retardant": ([POINTER(BulldozerPolicyStruct), P, P, P, P, P, c_int, c_int, c_int, c_int,
                                            c_int, c_int, c_int, c_uint64, c_int, P, c_int, P, P, P, P, P], c_int),
+    "gca_advanced_display": ([POINTER(ObsParams), c_int, c_int, c_int, P, P, P, P, c_int, P, P], c_int),
+    "gca_extension_policy_act": ([POINTER(BulldozerPolicyStruct), c_int, P, P, P, P, c_int, c_uint64, c_int, P, P, P,
+                                  c_int, P], c_int),
+    "gca_advanced_policy_act_display": ([POINTER(BulldozerPolicyStruct), POINTER(ObsParams), P, P, P, P, P, c_int,
+                                         c_int, c_int, c_int, c_int, c_uint64, c_int, P, c_int, P, P, P, P, P], c_int),
+    "gca_extension_policy_grad_workspace": ([POINTER(BulldozerPolicyStruct), c_int, c_int], c_int64),
+    "gca_extension_policy_grad": ([POINTER(BulldozerPolicyStruct), c_int, P, P, P, P, P, P, c_int64, P, c_int, c_float,
+                                   c_float, c_float, c_int, P, P, P, P, P, P, P, c_int64, P], c_int),
+    "gca_extension_policy_grad_vclip": ([POINTER(BulldozerPolicyStruct), c_int, P, P, P, P, P, P, P, c_int64, P, c_int,
+                                         c_float, c_float, c_float, c_int, P, P, P, P, P, P, P, P, c_int64, P], c_int),
     "gca_gae": ([P, P, P, P, c_float, c_float, c_int, c_int, P, P, P], c_int),
     "gca_helicopter_policy_grad_workspace": ([POINTER(HeliPolicy), c_int, c_int], c_int64),
     "gca_helicopter_policy_grad": ([POINTER(HeliPolicy), c_int, P, P, P, P, P, P, c_int64, P, c_int, c_float, c_float,
@@ -327,6 +337,10 @@ CPU_BULLDOZER_POLICY_SYMBOLS = ("gca_bulldozer_policy_act", "gca_bulldozer_polic
                                 "gca_advanced_policy_observation", "gca_advanced_policy_act_retardant")
 # both agents' learner's step with the reference's clipped value loss on host arrays
 CPU_VCLIP_SYMBOLS = ("gca_helicopter_policy_grad_vclip", "gca_bulldozer_policy_grad_vclip")
+# the extension policy (the bulldozer's three heads on the Advanced env's displayed plane) on host arrays
+CPU_EXTENSION_POLICY_SYMBOLS = ("gca_advanced_display", "gca_extension_policy_act", "gca_advanced_policy_act_display",
+                                "gca_extension_policy_grad_workspace", "gca_extension_policy_grad",
+                                "gca_extension_policy_grad_vclip")
 
 _lib = None
 _lib_cpu = None
@@ -361,7 +375,7 @@ def load_cpu():
     if not os.path.exists(CPU_LIB_PATH):
         raise GCAError(f"{CPU_LIB_PATH} not found: build it with `make -C gym-cellular-automata_amd/csrc`")
     lib = ctypes.CDLL(CPU_LIB_PATH, mode=ctypes.RTLD_LOCAL)
-    for name in CPU_SYMBOLS + CPU_BULLDOZER_POLICY_SYMBOLS + CPU_VCLIP_SYMBOLS:
+    for name in CPU_SYMBOLS + CPU_BULLDOZER_POLICY_SYMBOLS + CPU_VCLIP_SYMBOLS + CPU_EXTENSION_POLICY_SYMBOLS:
         fn = getattr(lib, name)
         fn.argtypes, fn.restype = _SIGNATURES[name]
     _lib_cpu = lib

@@ -144,6 +144,10 @@ class BatchedEnvBase:
     def _check_policy(self, policy, who):
         if not isinstance(policy, self._POLICY_CLASS):
             raise ValueError(f"{who}: policy must be a {self._POLICY_CLASS.__name__}")
+        if len(policy.HEADS) != len(self._POLICY_CLASS.HEADS):
+            raise ValueError(f"{who}: a {type(policy).__name__} has {len(policy.HEADS)} heads; this env takes a "
+                             f"{self._POLICY_CLASS.__name__} (the extension head belongs to "
+                             "AdvancedForestFireBulldozerEnv(enable_extensions=True))")
         if getattr(policy, "retardant", False):
             raise ValueError(f"{who}: the policy was built with retardant=True, and this env has no retardant layer to "
                              "observe (only AdvancedForestFireBulldozerEnv keeps one)")

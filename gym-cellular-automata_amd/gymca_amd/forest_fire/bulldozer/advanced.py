@@ -301,6 +301,7 @@ class AdvancedForestFireBulldozerEnv:
 
         E, H, W = self.num_envs, self.nrows, self.ncols
         st = dev.stream_ptr(self.device)
+        self._last_action = None  # the displayed plane's choice before an env's first step is 0
         # grid iid over {EMPTY, TREE} (p_empty, p_tree), two fires with age (N + N//2) * 2 (:650-688)
         cdf = torch.tensor([self._p_empty_init, self._p_empty_init + self._p_tree_init, 1.0], dtype=torch.float32,
                            device=self.device)
@@ -763,6 +764,8 @@ class AdvancedForestFireBulldozerEnv:
         """Gymnasium-style step of every env: action (E, 2) or (E, 3) ints (move, shoot[, extension choice]),
         device tensor or numpy. Returns (obs, reward, terminated, truncated, info) like stateless_step."""
         full = self._full_action(action)
+        # the extension choice the next displayed plane is shaped by (display(), host bookkeeping only)
+        self._last_action = full if full.shape[1] >= 3 else None
         fused = self.fused_observation
         self.ca_step(render=fused, action=full)
         self.post_step(full[:, :2].contiguous(), stats=True)
@@ -836,9 +839,11 @@ class AdvancedForestFireBulldozerEnv:
 
     # ------------------------------------------------------------------ the agent: observe, policy_act, rollout_policy
     # (the other batched envs call it act(); here `act` is the tile activity map of the tiled step)
-    # The bulldozer agent of the batched Windy env (BulldozerPolicy, forest_fire.ppo) on this env. Out of scope: a third
-    # head for the extension choice (the network holds at most 12 outputs; rollout_policy takes a constant `extension`;
-    # the extensions change the RGB frame, and this agent reads the true grid) and K steps in one launch (the CA step is
+    # The bulldozer agent of the batched Windy env (BulldozerPolicy, forest_fire.ppo) on this env: it reads the true grid,
+    # and rollout_policy gives the env a constant `extension`. With enable_extensions an ExtensionBulldozerPolicy is the
+    # agent the reference trains: a third head picks the extension, and the agent observes the displayed plane
+    # (display(): what the RGB frame colours), shaped by its own previous choice. Out of scope: the reference's CNN over
+    # the RGB frame itself, the retardant and the display in one observation, and K steps in one launch (the CA step is
     # HBM traffic, not launch-bound: DESIGN.md).
     # ModifyJax writes the retardant into `dousing`, not into the grid: a BulldozerPolicy(retardant=True) sees it through
     # the feature vector of observe(retardant=True), which takes the coarse map's place in every call and record below.
@@ -876,7 +881,56 @@ class AdvancedForestFireBulldozerEnv:
             cs = (self.num_envs, (3 * cs[2] * cs[3] + ls[1] * ls[2] + 1) & ~1)
         return ls, cs
 
-    def observe(self, radius=16, block=16, local_out=None, coarse_out=None, form=0, retardant=False):
+    # ---- the displayed plane (the extension agent's observation)
+    # Which choice shapes it: the one the RGB frame would show, the third column of the action of the env's previous
+    # step. step() remembers that action tensor (host bookkeeping, no launch: a caller who overwrites the tensor it passed
+    # to step() changes the choice with it); conditional_reset keeps it, as the reference rebuilds the re-injected envs'
+    # frame with the step's action; reset() forgets it, and the choice before an env's first step is 0. The reference's
+    # first frame after reset() is the transposed mode-1 oddity (gca_adv_observation mode 1): deliberately NOT what the
+    # agent sees here -- it sees the display of the initial grid under choice 0.
+    def _need_extensions(self, who):
+        if not self.enable_extensions:
+            raise ValueError(f"{who}: the env was built with enable_extensions=False (the displayed plane and the "
+                             "extension head need enable_extensions=True)")
+
+    def _choice_arg(self, choice, who):
+        """(tensor kept alive | None, address | None, stride in int32 words) of a `choice` argument: None = the third
+        column of the previous step's action (0 before the first step), else an int32 (E,) device tensor of any stride,
+        for instance a column of an (E, 3) action tensor."""
+        import torch
+
+        if choice is None:
+            last = self.__dict__.get("_last_action")
+            if last is None:
+                return None, None, 0
+            return last, last.data_ptr() + 8, int(last.stride(0))
+        if not (type(choice) is torch.Tensor and choice.dtype is torch.int32 and choice.device == self.device
+                and tuple(choice.shape) == (self.num_envs,) and choice.stride(0) >= 1):
+            raise ValueError(f"{who}: choice must be an int32 ({self.num_envs},) tensor on the env's device (a column of "
+                             "an action tensor will do)")
+        return choice, choice.data_ptr(), int(choice.stride(0))
+
+    def display(self, out=None, choice=None):
+        """The displayed plane of every env, uint8 (E, H, W), in one launch (gca_advanced_display): the values the step's
+        RGB frame colours -- the blurred, visibility-filtered grid, or the extension channel that `choice` switches on,
+        with the reference's row-for-channel selection -- before the colour lookup, without dousing and position.
+        choice: None = the third column of the previous step's action (0 after reset()), or an int32 (E,) tensor.
+        Needs enable_extensions=True. No sync."""
+        import torch
+
+        from .._batched import check_tensor
+
+        self._need_extensions("display")
+        E, H, W = self.num_envs, self.nrows, self.ncols
+        out = torch.empty((E, H, W), dtype=torch.uint8, device=self.device) if out is None else \
+            check_tensor(out, torch.uint8, (E, H, W), self._dev_index, "display", "out")
+        _, cp, cstride = self._choice_arg(choice, "display")
+        call("gca_advanced_display", self.obs_params, E, H, W, dev.ptr(self.grid[self.cur]), dev.ptr(self.is_night),
+             dev.ptr(self.time_step), cp, cstride, dev.ptr(out), dev.stream_ptr(self.device))
+        return out
+
+    def observe(self, radius=16, block=16, local_out=None, coarse_out=None, form=0, retardant=False, display=False,
+                choice=None):
         """The policy observation of every env in one launch (gca_policy_observation on the current plane): `local`,
         uint8 (E, 2 radius + 1, 2 radius + 1), the classes of the cells around the bulldozer (0 other, 1 TREE, 2 FIRE, 3
         outside the grid), and `coarse`, float32 (E, 2, ceil(H / block), ceil(W / block)), the TREE and the FIRE share
@@ -887,11 +941,19 @@ class AdvancedForestFireBulldozerEnv:
         tensor then is `feat`, float32 (E, C2), C2 = 3 Hc Wc + S*S rounded up to even -- the coarse map flattened, the
         share of doused cells of every tile, one flag per window cell (1.0 where the cell is in the grid and doused)
         and a zero pad word where needed; `coarse_out` takes a tensor of that shape. It reads the env's dousing bits
-        where the packed layout keeps them, else the uint8 layer; `form` must be 0."""
+        where the packed layout keeps them, else the uint8 layer; `form` must be 0.
+        display=True (enable_extensions only): the same two tensors taken from the DISPLAYED plane, display(choice=choice),
+        in two launches (the plane goes to a scratch tensor the env keeps); not together with retardant."""
         import torch
 
         from .._batched import check_tensor
 
+        if display:
+            self._need_extensions("observe")
+            if retardant:
+                raise ValueError("observe: display=True and retardant=True are not combined")
+        elif choice is not None:
+            raise ValueError("observe: choice needs display=True")
         radius, block, form = int(radius), int(block), int(form)
         if not 0 <= radius <= 31:
             raise ValueError("observe: radius must be in [0, 31]")
@@ -908,6 +970,16 @@ class AdvancedForestFireBulldozerEnv:
         coarse_out = torch.empty(cs, dtype=torch.float32, device=self.device) if coarse_out is None else \
             check_tensor(coarse_out, torch.float32, cs, di, "observe", "coarse_out")
         cur = self.cur
+        if display:
+            plane = self.__dict__.get("_display_plane")
+            if plane is None:
+                plane = self._display_plane = torch.empty((self.num_envs, self.nrows, self.ncols), dtype=torch.uint8,
+                                                          device=self.device)
+            self.display(plane, choice)
+            call("gca_policy_observation", dev.ptr(plane), None, None, dev.ptr(self.pos), self.num_envs, self.nrows,
+                 self.ncols, self._empty, self._tree, self._fire, radius, block, form, dev.ptr(local_out),
+                 dev.ptr(coarse_out), dev.raw_stream(di))
+            return local_out, coarse_out
         if retardant:
             oc = self._bound(("observe_retardant", cur, radius, block), lambda: BoundCall(
                 "gca_advanced_policy_observation", dev.ptr(self.grid[cur]), dev.ptr(self.dousing),
@@ -932,15 +1004,58 @@ class AdvancedForestFireBulldozerEnv:
                              f"{(self.nrows, self.ncols)}")
         if policy.device != self.device:
             raise ValueError(f"{who}: the policy lives on {policy.device}, the env on {self.device}")
+        if self._is_ext(policy):
+            self._need_extensions(f"{who} with an ExtensionBulldozerPolicy")
         return policy
 
-    def _act(self, policy, seed, greedy, action, logits, value, local, coarse, fused):
+    @staticmethod
+    def _is_ext(policy):
+        from .policy import ExtensionBulldozerPolicy
+
+        return isinstance(policy, ExtensionBulldozerPolicy)
+
+    # policy_act(fused=None) of an ExtensionBulldozerPolicy: the fused launch. The rule: it is the default only while
+    # scripts/bench_advanced_policy_display.py (profiles/advanced_policy_display.json, `fused_default`) shows every fused
+    # round below every triple round at both shapes in the mixed case. Measured on an MI355X: 165 against 706 us at
+    # 4096 x 256^2 and 160 against 724 us at 1024 x 512^2 (medians of 5 rounds, no records).
+    _DISPLAY_FUSED_DEFAULT = True
+
+    def _act_display(self, policy, seed, greedy, action, logits, value, local, coarse, fused, choice):
+        """policy_act() of an ExtensionBulldozerPolicy after its checks: `action` a contiguous int32 (E, 3) tensor,
+        `choice` as _choice_arg takes it."""
+        import torch
+
+        from .._batched import seed64
+
+        E, di = self.num_envs, self._dev_index
+        p = lambda t: None if t is None else t.data_ptr()
+        keep_choice, cp, cstride = self._choice_arg(choice, "policy_act")
+        if fused:
+            cur = self.cur
+            ac = self._bound(("act_display", cur, id(policy)), lambda: BoundCall(
+                "gca_advanced_policy_act_display", policy.struct, self.obs_params, dev.ptr(self.grid[cur]),
+                dev.ptr(self.pos), dev.ptr(self.is_night), dev.ptr(self.time_step), SLOT, SLOT, E, self.nrows,
+                self.ncols, self.env_offset, SLOT, SLOT, SLOT, SLOT, SLOT, SLOT, SLOT, SLOT, SLOT,
+                keep=(self.grid, self.pos, self.is_night, self.time_step) + policy.tensors()), keep=policy)
+            ac(cp, cstride, seed64(seed), 1 if greedy else 0, action.data_ptr(), 3, p(logits), p(value), p(local),
+               p(coarse), dev.raw_stream(di))
+            return
+        # the triple: the display reads the choice in a launch of its own before the network's launch writes the action,
+        # so a choice that is a column of `action` is ordered by the stream
+        local, coarse = self.observe(policy.radius, policy.block, local, coarse, display=True, choice=choice)
+        call("gca_extension_policy_act", policy.struct, policy.C, dev.ptr(local), dev.ptr(coarse),
+             dev.ptr(self.time_step.to(torch.int64)), None, self.env_offset, seed64(seed), 1 if greedy else 0,
+             dev.ptr(action), p(logits), p(value), E, dev.raw_stream(di))
+
+    def _act(self, policy, seed, greedy, action, logits, value, local, coarse, fused, choice=None):
         """policy_act() after its checks: `action` a contiguous int32 (E, 2) or (E, 3) tensor, the others tensors or None (the
         fused launch takes NULL for them; the pair allocates what it needs)."""
         import torch
 
         from .._batched import seed64
 
+        if self._is_ext(policy):
+            return self._act_display(policy, seed, greedy, action, logits, value, local, coarse, fused, choice)
         E, di = self.num_envs, self._dev_index
         p = lambda t: None if t is None else t.data_ptr()
         stride = int(action.shape[1])
@@ -974,7 +1089,7 @@ class AdvancedForestFireBulldozerEnv:
             action[:, :2].copy_(pair)
 
     def policy_act(self, policy, seed=0, greedy=False, action_out=None, logits_out=None, value_out=None,
-                   local_out=None, coarse_out=None, fused=True):
+                   local_out=None, coarse_out=None, fused=None, choice=None):
         """The policy's (move, shoot) for every env on the env's current state, observation and network in ONE launch
         (gca_advanced_policy_act: the coarse map is counted into the workgroup's LDS and never written out unless
         `coarse_out` asks for it). policy: a BulldozerPolicy built for this grid shape on this device. Returns (action
@@ -988,46 +1103,67 @@ class AdvancedForestFireBulldozerEnv:
         fused=False runs the two calls the fused launch is defined by, observe() and then gca_bulldozer_policy_act on
         time_step.to(int64): the same bits, the yardstick of the tests and of scripts/bench_advanced_policy.py.
         A policy built with retardant=True sees the dousing layer: the launch is gca_advanced_policy_act_retardant, the
-        pair observe(retardant=True) and the network, and `coarse_out` is the feature vector (E, policy.C)."""
+        pair observe(retardant=True) and the network, and `coarse_out` is the feature vector (E, policy.C).
+        An ExtensionBulldozerPolicy (enable_extensions=True only) observes the DISPLAYED plane and has a third head:
+        action is (E, 3) = (move, shoot, extension), logits (E, 14), all three columns written; the launch is
+        gca_advanced_policy_act_display, and fused=False the triple display() -> gca_policy_observation ->
+        gca_extension_policy_act, the same bits. `choice` (that policy only): the extension choice that shapes the
+        display, None = the third column of the previous step's action (0 after reset()), or an int32 (E,) tensor, which
+        may be column 2 of `action_out` itself (every env's choice is read before its action is written).
+        fused=None: the fused launch (for an ExtensionBulldozerPolicy: _DISPLAY_FUSED_DEFAULT, the fused launch by the
+        measurement of scripts/bench_advanced_policy_display.py)."""
         import torch
 
         from .._batched import _is_kernel_tensor, check_tensor
 
         policy = self._check_policy(policy, "policy_act")
+        ext = self._is_ext(policy)
+        if choice is not None and not ext:
+            raise ValueError("policy_act: choice needs an ExtensionBulldozerPolicy")
         E, di = self.num_envs, self._dev_index
+        if fused is None:
+            fused = self._DISPLAY_FUSED_DEFAULT if ext else True
+        n_logits = policy.N_LOGITS
         ls, cs = self._obs_shapes(policy.radius, policy.block, policy.retardant)
         if action_out is None:
-            action_out = torch.empty((E, 2), dtype=torch.int32, device=self.device)
+            action_out = torch.empty((E, 3 if ext else 2), dtype=torch.int32, device=self.device)
+        elif ext:
+            check_tensor(action_out, torch.int32, (E, 3), di, "policy_act", "action_out")
         elif not (_is_kernel_tensor(action_out, torch.int32, di) and tuple(action_out.shape) in ((E, 2), (E, 3))):
             raise ValueError(f"policy_act: action_out must be a contiguous int32 ({E}, 2) or ({E}, 3) tensor on the env's "
                              "device")
         new = lambda dtype, shape: torch.empty(shape, dtype=dtype, device=self.device)
-        logits_out = new(torch.float32, (E, 11)) if logits_out is None else \
-            check_tensor(logits_out, torch.float32, (E, 11), di, "policy_act", "logits_out")
+        logits_out = new(torch.float32, (E, n_logits)) if logits_out is None else \
+            check_tensor(logits_out, torch.float32, (E, n_logits), di, "policy_act", "logits_out")
         value_out = new(torch.float32, (E,)) if value_out is None else \
             check_tensor(value_out, torch.float32, (E,), di, "policy_act", "value_out")
         if local_out is not None:
             check_tensor(local_out, torch.uint8, ls, di, "policy_act", "local_out")
         if coarse_out is not None:
             check_tensor(coarse_out, torch.float32, cs, di, "policy_act", "coarse_out")
-        self._act(policy, seed, greedy, action_out, logits_out, value_out, local_out, coarse_out, fused)
+        self._act(policy, seed, greedy, action_out, logits_out, value_out, local_out, coarse_out, fused, choice)
         return action_out, logits_out, value_out
 
     def policy_record_shapes(self, policy, K):
         """{record name: (dtype, shape)} of rollout_policy(policy, K): the keys, dtypes and layout of
-        BatchedForestFireBulldozerEnv.rollout_policy's records; `coarse` is (K, E, C2) for a retardant policy."""
+        BatchedForestFireBulldozerEnv.rollout_policy's records; `coarse` is (K, E, C2) for a retardant policy. `action`
+        and `logits` follow the policy's heads: (K, E, 3) and (K, E, 14) for an ExtensionBulldozerPolicy, which also has
+        the opt-in record `is_night` uint8 (K, E)."""
         import torch
 
         E, K = self.num_envs, int(K)
         ls, cs = self._obs_shapes(policy.radius, policy.block, policy.retardant)
-        return {"action": (torch.int32, (K, E, 2)), "logits": (torch.float32, (K, E, 11)),
+        spec = {"action": (torch.int32, (K, E, len(policy.HEADS))), "logits": (torch.float32, (K, E, policy.N_LOGITS)),
                 "value": (torch.float32, (K, E)), "reward": (torch.float64, (K, E)),
                 "terminated": (torch.uint8, (K, E)), "truncated": (torch.uint8, (K, E)),
                 "local": (torch.uint8, (K,) + ls), "coarse": (torch.float32, (K,) + cs)}
+        if self._is_ext(policy):
+            spec["is_night"] = (torch.uint8, (K, E))
+        return spec
 
     def rollout_policy(self, policy, K, seed=0, greedy=False, autoreset=True, extension=0, record=_POLICY_RECORDS,
                        action_out=None, logits_out=None, value_out=None, reward_out=None, terminated_out=None,
-                       truncated_out=None, local_out=None, coarse_out=None):
+                       truncated_out=None, local_out=None, coarse_out=None, is_night_out=None):
         """K closed-loop env steps of every env: bit for bit the loop, for k = 0 .. K - 1, of
             policy_act(policy, seed, greedy) into row k  ->  step(action)  ->  row k of reward and terminated
             ->  conditional_reset() when `autoreset`
@@ -1042,12 +1178,27 @@ class AdvancedForestFireBulldozerEnv:
         that constant for every env and step; the record keeps (move, shoot). Given outputs must be contiguous tensors of
         policy_record_shapes(policy, K) on the env's device; with every one given the call issues launches only and
         does not sync. It can be captured in a graph for an EVEN K only: the plane the step reads (`cur`) is host state
-        that alternates per step, and a replay must find it where the capture did; an odd K under capture raises."""
+        that alternates per step, and a replay must find it where the capture did; an odd K under capture raises.
+        An ExtensionBulldozerPolicy (enable_extensions=True only): the loop is policy_act(choice = the previous step's
+        action[:, 2]) -> step(action) -> conditional_reset(); the env's step takes the policy's own third column, so
+        `extension` must stay at its default; action is (K, E, 3) and logits (K, E, 14). The env keeps the action in a
+        persistent (E, 3) tensor whose third column is the next step's choice (conditional_reset keeps it; after reset()
+        it starts at 0). Right after reset(), or after a step() with the caller's own action, the rollout first brings that
+        column up to date (zero, or a copy), which it decides from host state: a graph capture therefore needs a preceding
+        eager rollout_policy on this env, and raises without one. The opt-in record `is_night` uint8 (K, E), the env's is_night before step k, is written only when
+        it is named in `record` or is_night_out is given (the reference's extensions/day_correct_rate compares it with
+        action[..., 2])."""
         import torch
 
         from .._batched import check_tensor
 
         policy = self._check_policy(policy, "rollout_policy")
+        is_ext = self._is_ext(policy)
+        if is_ext and int(extension) != 0:
+            raise ValueError("rollout_policy: an ExtensionBulldozerPolicy chooses the extension itself (extension must "
+                             "stay at its default)")
+        if is_night_out is not None and not is_ext:
+            raise ValueError("rollout_policy: is_night_out needs an ExtensionBulldozerPolicy")
         K = int(K)
         if K < 0:
             raise ValueError("rollout_policy: K >= 0")
@@ -1060,8 +1211,10 @@ class AdvancedForestFireBulldozerEnv:
             raise ValueError(f"rollout_policy: unknown records {unknown}; choose from {self._POLICY_RECORDS}")
         given = {"action": action_out, "logits": logits_out, "value": value_out, "reward": reward_out,
                  "terminated": terminated_out, "truncated": truncated_out, "local": local_out, "coarse": coarse_out}
+        if is_ext:
+            given["is_night"] = is_night_out
         recs = {}
-        for name in self._POLICY_RECORDS:
+        for name in self._POLICY_RECORDS + (("is_night",) if is_ext else ()):
             dtype, shape = spec[name]
             if given[name] is not None:
                 recs[name] = check_tensor(given[name], dtype, shape, di, "rollout_policy", f"{name}_out")
@@ -1074,6 +1227,8 @@ class AdvancedForestFireBulldozerEnv:
         row = lambda name, k: recs[name][k] if name in recs else None
         ext = self.enable_extensions
         a = None
+        if is_ext:
+            return self._rollout_display(policy, K, seed, greedy, autoreset, recs, row)
         if ext or "action" not in recs:
             # the env's own action: (move, shoot, extension) with extensions, else where no record keeps the pair
             a = self.__dict__.get("_agent_action")
@@ -1088,6 +1243,43 @@ class AdvancedForestFireBulldozerEnv:
             if ext and "action" in recs:
                 recs["action"][k].copy_(ak[:, :2])
             self.step(ak)
+            if "reward" in recs:
+                recs["reward"][k].copy_(self.reward)
+            if "terminated" in recs:
+                recs["terminated"][k].copy_(self.done)
+            if autoreset:
+                self.conditional_reset()
+        return recs
+
+    def _rollout_display(self, policy, K, seed, greedy, autoreset, recs, row):
+        """rollout_policy's loop for an ExtensionBulldozerPolicy. The env's persistent (E, 3) action tensor `a` is both
+        what the policy writes and, through its third column, the choice that shapes the next step's display: the launch
+        reads env e's choice before it writes env e's action."""
+        import torch
+
+        E = self.num_envs
+        a = self.__dict__.get("_display_action")
+        if a is None:
+            a = self._display_action = torch.zeros((E, 3), dtype=torch.int32, device=self.device)
+        last = self.__dict__.get("_last_action")
+        if last is None or last.data_ptr() != a.data_ptr():
+            # whether and what to enqueue here is decided from host state: captured, it would be replayed on every
+            # replay (each one starting from choice 0, or from a stale tensor), which eager execution does not do
+            if torch.cuda.is_current_stream_capturing():
+                raise ValueError("rollout_policy: a graph capture with an ExtensionBulldozerPolicy needs a preceding "
+                                 "eager rollout_policy since the last reset() and the caller's last step()")
+            if last is None:
+                a[:, 2].zero_()  # after reset(): the choice before the first step is 0
+            else:
+                a[:, 2].copy_(last[:, 2])  # the caller stepped the env with an action of its own
+        for k in range(K):
+            if "is_night" in recs:
+                recs["is_night"][k].copy_(self.is_night)
+            self._act_display(policy, seed, greedy, a, row("logits", k), row("value", k), row("local", k),
+                              row("coarse", k), self._DISPLAY_FUSED_DEFAULT, a[:, 2])
+            if "action" in recs:
+                recs["action"][k].copy_(a)
+            self.step(a)
             if "reward" in recs:
                 recs["reward"][k].copy_(self.reward)
             if "terminated" in recs:

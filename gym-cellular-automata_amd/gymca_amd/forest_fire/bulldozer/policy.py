@@ -51,3 +51,34 @@ class BulldozerPolicy(PolicyBase):
         out, lead = self._forward_torch(local, coarse, weights)
         return (out[:, :N_MOVE].reshape(lead + (N_MOVE,)), out[:, N_MOVE:N_LOGITS].reshape(lead + (N_SHOOT,)),
                 out[:, N_LOGITS].reshape(lead))
+
+
+N_EXTENSION = 3
+
+
+class ExtensionBulldozerPolicy(BulldozerPolicy):
+    """The three-headed agent the reference trains on the Advanced bulldozer env (Actor(action_dims=[9, 2],
+    choose_k=[(2, 1)]), agents/jax_ppo.py:305-356, 708-710): the bulldozer policy's network with fifteen outputs -- nine
+    move logits, two shoot logits, three extension logits and the value (include/gca.h "extension policy"). On an
+    AdvancedForestFireBulldozerEnv(enable_extensions=True) it observes the DISPLAYED plane (env.display(): the blurred,
+    visibility-filtered grid, or the extension channel its own previous choice switched on), not the true grid, and its
+    third action column is the env's extension choice. A record's `action` holds T x 3 int32 values and its `logits`
+    T x 14 float32 values; ppo_grad / ppo_update are PolicyBase's over gca_extension_policy_grad, every mean over the
+    (sample, head) pairs of three heads. The retardant observation cannot be combined with the display yet."""
+    HEADS = (N_MOVE, N_SHOOT, N_EXTENSION)
+    N_LOGITS = N_MOVE + N_SHOOT + N_EXTENSION
+    GRAD_ENTRY = "gca_extension_policy_grad"
+
+    def __init__(self, env_or_shape, radius=5, block=8, hidden=64, seed=0, device=None, retardant=False):
+        if retardant:
+            raise ValueError("ExtensionBulldozerPolicy: retardant=True is not supported (the retardant observation and "
+                             "the displayed plane are not combined in one observation)")
+        super().__init__(env_or_shape, radius, block, hidden, seed, device)
+
+    def forward_torch(self, local, coarse, weights=None):
+        """(move_logits (..., 9), shoot_logits (..., 2), extension_logits (..., 3), value (...)) of the same network in
+        differentiable torch ops; see BulldozerPolicy.forward_torch."""
+        out, lead = self._forward_torch(local, coarse, weights)
+        a, b, c = N_MOVE, N_MOVE + N_SHOOT, self.N_LOGITS
+        return (out[:, :a].reshape(lead + (N_MOVE,)), out[:, a:b].reshape(lead + (N_SHOOT,)),
+                out[:, b:c].reshape(lead + (N_EXTENSION,)), out[:, c].reshape(lead))

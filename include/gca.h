@@ -835,6 +835,82 @@ int gca_advanced_policy_act_retardant(const gca_bulldozer_policy* policy, const 
                                       uint64_t policy_seed, int greedy, int32_t* action, int action_stride,
                                       float* logits, float* value, uint8_t* local_out, float* feat_out, void* stream);
 
+/* ------------------------------------------ extension policy (the three-headed agent the reference trains on the
+ * Advanced bulldozer env: Actor(action_dims=[9, 2], choose_k=[(2, 1)]), agents/jax_ppo.py:305-356, 708-710; it observes
+ * the frame of build_observation_on_extensions, advanced_bulldozer.py:988-1033, not the true grid)
+ *
+ * gca_advanced_display: for every env the u8 value plane that gca_adv_observation mode 0 colours -- display_grid of
+ * grid_to_rgb_with_extensions before the colour lookup, with no dousing and no position. grid u8 [E][H][W], is_night i32
+ * [E]; time_step i32 [E], nullable: when given, the pre-step day/night is recovered as gca_adv_observation recovers it
+ * (is_night flipped where time_step % day_length == 0), when NULL is_night is used as it is. choice i32, env e's at
+ * choice[e * choice_stride], nullable (NULL: 0 for every env), clamped to [0, n_choices - 1]: ext_lookup[choice] names the
+ * active extension channels (none unless enable_extensions). display_out u8 [E][H][W]; its E H W bytes may not overlap the
+ * grid's anywhere (the blur reads neighbours; an overlap is an argument error). Every quirk of the
+ * frame is kept: blur = floor((2 S + 9) / 18) of the edge-padded 3 x 3 sum S; visibility turns the literal value 3 into 0
+ * by day; the first ROW of the channel-last stack holding a positive extension value gives, clamped to n_ext - 1, the
+ * CHANNEL displayed everywhere (a switched-off channel is all zeros); with no positive extension value the base channel
+ * is displayed (the transformed grid with should_transform, else the grid). One launch, no allocation, no sync:
+ * capturable. The host build runs plain loops. Pinned by tests/_extension_policy_ref.py against oracle/observation.py. */
+int gca_advanced_display(const gca_obs_params* p, int E, int H, int W, const uint8_t* grid, const int32_t* is_night,
+                         const int32_t* time_step, const int32_t* choice, int choice_stride, uint8_t* display_out,
+                         void* stream);
+
+/* gca_extension_policy_act: the "bulldozer policy" above with FIFTEEN outputs: out[0..8] the move logits, out[9..10] the
+ * shoot logits, out[11..13] the extension logits, out[14] the value; w_out f32 [Hd][15], b2 f32 [15]. Inputs, hidden
+ * layer and summation order are unchanged (the heads take 16 * 15 = 240 of 256 lanes). The draw is the bulldozer's,
+ * Philox(((uint32)steps_elapsed[e], env_offset + e, episode ? episode[e] : 0, GCA_TAG_BPOLICY), policy_seed): word 0
+ * draws the move and word 1 the shoot by the rules above, so a seed gives the two-head agent's move and shoot for equal
+ * logits; word 2 draws the extension by the move rule over three logits: m the first maximum of e_0..e_2, p_i =
+ * exp_f32(e_i - m), c_i = c_{i-1} + p_i, u = u01_f32(x.z), the first i with u * c_2 < c_i, else 2. greedy != 0: the first
+ * maximum of each head, nothing drawn. Non-finite weights still give an extension in [0, 2].
+ * action i32 [E][3] (move, shoot, extension), logits f32 [E][14] (nullable), value f32 [E] (nullable); the other
+ * arguments and checks are gca_bulldozer_policy_act's. ONE launch, a workgroup per env; the host build runs plain loops
+ * in the same order and agrees bit for bit. */
+int gca_extension_policy_act(const gca_bulldozer_policy* p, int C, const uint8_t* local, const float* coarse,
+                             const int64_t* steps_elapsed, const uint32_t* episode, int env_offset,
+                             uint64_t policy_seed, int greedy, int32_t* action, float* logits, float* value, int E,
+                             void* stream);
+
+/* gca_advanced_policy_act_display: observe the DISPLAYED plane and act, in ONE launch. Bit for bit three calls in
+ * sequence:
+ *   1. gca_advanced_display(p, E, H, W, grid, is_night, time_step, choice, choice_stride, plane)
+ *   2. gca_policy_observation(plane, NULL, NULL, pos, E, H, W, p->empty, p->tree, p->fire, policy->radius,
+ *      policy->block, 0, local, coarse)
+ *   3. gca_extension_policy_act(policy, C, local, coarse, steps_elapsed, NULL, env_offset, policy_seed, greedy, ...) with
+ *      steps_elapsed[e] = (int64)time_step[e] and C = 2 Hc Wc of (H, W, policy->block).
+ * The displayed plane never exists: one 256-thread workgroup per env counts the TREE / FIRE shares of the displayed
+ * values straight into the network's LDS words and computes the window's classes from the plane, the blur on the fly.
+ * action i32 [E][action_stride], action_stride >= 3: columns 0, 1 and 2 are written. logits f32 [E][14], value f32 [E],
+ * local_out u8 [E][S][S] and coarse_out f32 [E][C] are nullable; the last two record what the network saw. time_step is
+ * required (it keys the draw, as in gca_advanced_policy_act). `choice` MAY point at column 2 of the same `action` rows
+ * (choice_stride = action_stride): workgroup e reads env e's choice, and no other env's, before any of its threads
+ * writes env e's action (the network's first barrier lies between). No env state changes. No scratch, no allocation, no
+ * sync, no atomics: capturable. The host build runs the three host functions. */
+int gca_advanced_policy_act_display(const gca_bulldozer_policy* policy, const gca_obs_params* p, const uint8_t* grid,
+                                    const int32_t* pos, const int32_t* is_night, const int32_t* time_step,
+                                    const int32_t* choice, int choice_stride, int E, int H, int W, int env_offset,
+                                    uint64_t policy_seed, int greedy, int32_t* action, int action_stride,
+                                    float* logits, float* value, uint8_t* local_out, float* coarse_out, void* stream);
+
+/* gca_extension_policy_grad(_workspace, _vclip): gca_bulldozer_policy_grad for the three heads (9, 2, 3): action i32
+ * [T][3], old_logits f32 [T][14], fifteen outputs, the value in column 14, NH = 3. Every mean of pg, entropy, approx_kl
+ * and the clip fraction runs over the N x 3 (sample, head) pairs -- the reference stacks the per-head log-probabilities
+ * and entropies and never sums over heads (jax_ppo.py:913-926) -- and everything else said of the two-head calls below
+ * ("PPO update") holds, with gca_extension_policy_grad_workspace. */
+int64_t gca_extension_policy_grad_workspace(const gca_bulldozer_policy* p, int C, int N);
+int gca_extension_policy_grad(const gca_bulldozer_policy* p, int C, const uint8_t* local, const float* coarse,
+                              const int32_t* action, const float* old_logits, const float* advantage,
+                              const float* returns, int64_t T, const int32_t* idx, int N, float clip_coef,
+                              float ent_coef, float vf_coef, int norm_adv, float* g_w_local, float* g_w_coarse,
+                              float* g_b1, float* g_w_out, float* g_b2, float* stats, void* workspace,
+                              int64_t workspace_bytes, void* stream);
+int gca_extension_policy_grad_vclip(const gca_bulldozer_policy* p, int C, const uint8_t* local, const float* coarse,
+                                    const int32_t* action, const float* old_logits, const float* old_value,
+                                    const float* advantage, const float* returns, int64_t T, const int32_t* idx, int N,
+                                    float clip_coef, float ent_coef, float vf_coef, int norm_adv, float* g_w_local,
+                                    float* g_w_coarse, float* g_b1, float* g_w_out, float* g_b2, float* stats,
+                                    float* vstats, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ------------------------------------------ PPO update (the learner's half of the reference's main loop:
  * agents/jax_ppo.py:932-984 compute_gae, :987-1043 ppo_loss and its gradient), on rollout_policy's records
  * gca_gae: reward f64 (K, E) and value f32 (K, E) as gca_helicopter_policy_rollout records them, next_value f32 (E) the

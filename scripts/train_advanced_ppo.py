@@ -13,7 +13,12 @@ update as two graphs and replays them; the draw is keyed by the env's time_step,
 draws new actions.
 
 The defaults are the reference's PPOArgs (lr 2.5e-4, clip 0.1, 4 epochs x 4 minibatches, 128 steps) but for clip_vloss, which
-is off unless --clip-vloss asks for the reference's clipped value loss. The extension choice is not the agent's (rollout_policy's `extension`).
+is off unless --clip-vloss asks for the reference's clipped value loss. Without --extension the extension choice is not
+the agent's (rollout_policy's `extension`). --extension trains the agent the reference trains: an ExtensionBulldozerPolicy
+on an env with enable_extensions=True, whose third head picks the extension and which observes the displayed plane its
+previous choice shaped; per iteration it also prints the reference's two rates (jax_ppo.py:524-538,
+extensions/day_correct_rate): the share of day steps with extension 2 and the share of night steps with extension 1, from
+the `action[..., 2]` and `is_night` records.
 --retardant builds the policy with retardant=True: its observation then holds the env's dousing layer (the share of doused
 cells per block and a flag per window cell), so the shoot head sees where it has doused, as the reference's agent does in
 its RGB frame; without it the agent reads the grid alone. Needs a HIP device."""
@@ -44,6 +49,8 @@ def main():
     ap.add_argument("--gae-lambda", type=float, default=0.95)
     ap.add_argument("--graph", action="store_true", help="capture the rollout and one update as graphs and replay them")
     ap.add_argument("--retardant", action="store_true", help="the policy sees the env's retardant (dousing) layer")
+    ap.add_argument("--extension", action="store_true",
+                    help="the three-headed agent on the displayed plane (enable_extensions=True); not with --retardant")
     ap.add_argument("--clip-vloss", action="store_true",
                     help="the reference's clipped value loss (args.ppo.clip_vloss, on by default THERE; off here)")
     args = ap.parse_args()
@@ -52,7 +59,8 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("train_advanced_ppo.py needs a HIP device")
     from gymca_amd.forest_fire import ppo
-    from gymca_amd.forest_fire.bulldozer import AdvancedForestFireBulldozerEnv, BulldozerPolicy
+    from gymca_amd.forest_fire.bulldozer import (AdvancedForestFireBulldozerEnv, BulldozerPolicy,
+                                                 ExtensionBulldozerPolicy)
     from gymca_amd.forest_fire.bulldozer.policy import WEIGHTS
 
     device = torch.device("cuda", 0)
@@ -62,10 +70,15 @@ def main():
         sys.exit("envs * steps must divide into the minibatches")
     if args.graph and K % 2:
         sys.exit("--graph needs an even number of steps")
+    if args.extension and args.retardant:
+        sys.exit("--extension and --retardant are not combined")
     env = AdvancedForestFireBulldozerEnv(args.rows, args.cols, key=1, num_envs=E, device=device, observation="grid",
-                                         hidden_rng="philox")
+                                         hidden_rng="philox", enable_extensions=args.extension)
     env.reset()
-    policy = BulldozerPolicy(env, radius=5, block=8, hidden=64, seed=0, retardant=args.retardant)
+    if args.extension:
+        policy = ExtensionBulldozerPolicy(env, radius=5, block=8, hidden=64, seed=0)
+    else:
+        policy = BulldozerPolicy(env, radius=5, block=8, hidden=64, seed=0, retardant=args.retardant)
     steps = args.epochs * args.minibatches
     opt = ppo.Adam(policy.state_dict(), lr=args.lr, anneal=(steps, args.iterations))
     N = T // args.minibatches
@@ -116,7 +129,17 @@ def main():
               f"loss {s[0]:+.5f}  pg {s[1]:+.5f}  entropy {s[3]:.4f}  kl {s[4]:.2e}  clip {s[5]:.3f}  "
               f"grad norm {info[0]:.4f}  lr {info[1]:.3e}" +
               ("  U {:.4f}  u-share {:.3f}  v-clip {:.3f}".format(*bufs["vstats_out"][-1].tolist()) if args.clip_vloss
-               else ""))
+               else "") + (_extension_rates(rec) if args.extension else ""))
+
+
+def _extension_rates(rec):
+    """The reference's two rates on one rollout's records (torch ops, not a hot path): the share of day steps whose
+    extension choice is 2 and the share of night steps whose choice is 1; n/a where the rollout has no such step."""
+    choice, night = rec["action"][..., 2], rec["is_night"] != 0
+    day_n, night_n = int((~night).sum().item()), int(night.sum().item())
+    day = f"{int(((choice == 2) & ~night).sum().item()) / day_n:.3f}" if day_n else "n/a"
+    ngt = f"{int(((choice == 1) & night).sum().item()) / night_n:.3f}" if night_n else "n/a"
+    return f"  day ext-2 rate {day}  night ext-1 rate {ngt}"
 
 
 if __name__ == "__main__":
